@@ -13,7 +13,10 @@ one process per GPU, each rank synthesises its OWN independent scenario of the s
 no data-path collective: scenarios shard embarrassingly); torch.distributed (RCCL)
 is used only for the barrier and the max-over-ranks time.
 
-Rank 0 prints ONE JSON line (see README / DESIGN.md for the field meanings).
+Rank 0 prints ONE JSON line (see README / DESIGN.md for the field meanings).  A plain run sets up, warms up, times the K
+steps and prints the line; --full adds everything else the benchmark measures or checks (the kernel alone and the roofline,
+configs.fresh_plan, the CPU baseline and the oracle's verdict on the timed output, the e2e / configs legs).  --dump-outputs DIR
+writes what the last timed step computed (dump_outputs) for an output-by-output comparison of two builds.
 """
 import argparse
 import json
@@ -460,6 +463,28 @@ def measured_issue(kernel_ms, channel_samples):
         return None
 
 
+DUMP_SAMPLES = 1 << 21  # complex samples of the IQ output that --dump-outputs writes: 16 MB of I/Q + 16 MB of positions
+DUMP_SEED = 2026
+
+
+def dump_outputs(torch, path, iq, state):
+    """--dump-outputs: what one step computed, as a caller of execute() / finish() receives it -- the int16 IQ buffer (all of it,
+    or DUMP_SAMPLES complex samples at fixed, seeded positions when it holds more) and the channels' end state -- as float32 /
+    float64 files path/<name>.npy.  The positions depend on the output's size alone, so runs with the same arguments compare."""
+    os.makedirs(path, exist_ok=True)
+    n = iq.numel() // 2
+    if n <= DUMP_SAMPLES:
+        pos = np.arange(n, dtype=np.int64)
+    else:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLES, replace=False))
+    arrays = {"iq": iq.view(-1, 2)[torch.from_numpy(pos).to(iq.device)].to(torch.float32).cpu().numpy(),
+              "iq_position": pos.astype(np.float64)}
+    for name in ("carr_phase", "page", "prn"):
+        arrays["state_" + name] = state[name].astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 # A/B experiments only (tools/): GAL_BENCH_HOOKS=1 runs the GAL_TEST_HOOKS build of the library, whose environment
 # switches (GAL_SYNTH_RW=0 ...) select code paths; such a line carries "hooks_build": true and is never a result.
 HOOKS_BUILD = bool(os.environ.get("GAL_BENCH_HOOKS"))
@@ -532,11 +557,18 @@ def main():
                     help="device wake-up in front of the W warm-up steps: un-timed passes of the same step for this long "
                     "(reported as preroll_steps).  A device that comes out of idle runs its first ~100 ms below its "
                     "sustained clocks, and W = 5 steps are 6 ms of work; 0 = none")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fresh-plan", action="store_true", help="skip configs.fresh_plan (the same step with a new scenario planned every step)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed-for-headline legs (kernel + D2H, CLI file "
-                    "sink, M-DYN, M-SYN24) that the default 1-GPU run reports under e2e / configs")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: the kernel alone and the roofline, "
+                    "configs.fresh_plan, the CPU baseline with the oracle's verdict on the timed output, and (1 GPU, default "
+                    "workload) the e2e / configs legs.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last step computed "
+                    "as DIR/<name>.npy (float32 / float64): a fixed, seeded sample of the IQ output and the channels' end state")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-fresh-plan", action="store_true", help="--full: skip configs.fresh_plan (the same step with a new scenario planned every step)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the untimed-for-headline legs (kernel + D2H, CLI file "
+                    "sink, M-DYN, M-SYN24) that the 1-GPU run reports under e2e / configs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
 
@@ -638,14 +670,17 @@ def main():
             dist.barrier(group=ctl["group"])  # (None = the default group)
         torch.cuda.synchronize()
 
+    last_state = [None]  # the channels' end state that finish() returned for the last step run
+
     def run(n_steps):
-        """n_steps complete passes, `depth` of them in flight; returns the per-step stats."""
+        """n_steps complete passes, `depth` of them in flight; returns the per-step stats.  Step k writes outs[k % depth]."""
         all_stats = []
         inflight = [False] * depth
         for k in range(n_steps):
             j = k % depth
             if inflight[j]:
-                all_stats.append(engines[j].finish()[1])
+                last_state[0], st = engines[j].finish()
+                all_stats.append(st)
                 if step_clock is not None:
                     step_clock.append(time.perf_counter())
             engines[j].execute(outs[j].data_ptr(), e_first, e_count)
@@ -653,7 +688,8 @@ def main():
         for k in range(n_steps, n_steps + depth):
             j = k % depth
             if inflight[j]:
-                all_stats.append(engines[j].finish()[1])
+                last_state[0], st = engines[j].finish()
+                all_stats.append(st)
                 if step_clock is not None:
                     step_clock.append(time.perf_counter())
                 inflight[j] = False
@@ -694,9 +730,11 @@ def main():
     ms_synth = sum(s["ms_synth"] for s in step_stats)
     ms_walk = sum(s["ms_walk"] for s in step_stats)
     assert all(s["chain_mismatch"] == 0 for s in step_stats)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, outs[(args.steps - 1) % depth], last_state[0])
     # outside the timed region: the same kernel without a co-running walker (one handle), for the roofline note
     solo_n = args.steps
-    if depth > 1:
+    if depth > 1 and args.full:
         inflight_stats = []
         solo_n = 10
         for _ in range(solo_n):
@@ -740,15 +778,6 @@ def main():
     value = total_samples / elapsed / 1e6
 
     if rank == 0:
-        avg_synth_ms = ms_synth / args.steps
-        traffic, traffic_src = measured_traffic() if (args.epochs == 1199 and args.workload == "syn12" and args.channels == 12
-                                                          and e_count == args.epochs) else (None, None)
-        achieved = 4.0 * samples_per_step / (avg_synth_ms * 1e-3) / 1e9 if avg_synth_ms > 0 else 0.0
-        step_ms = elapsed / args.steps * 1e3
-        step_achieved = 4.0 * samples_per_step / (step_ms * 1e-3) / 1e9
-        solo_achieved = 4.0 * samples_per_step / (solo_ms * 1e-3) / 1e9
-        prof_ms, prof_src = profiled_kernel_ms("bench") if traffic is not None else (None, None)
-        prof1_ms, prof1_src = profiled_kernel_ms("standalone") if traffic is not None else (None, None)
         line = {
             "metric": METRIC,
             "value": round(value, 3),
@@ -798,7 +827,18 @@ def main():
                 "kernel_family": stats.get("kernel_family"),  # 1: k_synth_g + k_repair_g (galsynth.h: gal_synth_stats_t)
                 "output_checksum": "%08x" % chk,
             },
-            "roofline": {
+        }
+        if args.full:
+            avg_synth_ms = ms_synth / args.steps
+            traffic, traffic_src = measured_traffic() if (args.epochs == 1199 and args.workload == "syn12" and args.channels == 12
+                                                              and e_count == args.epochs) else (None, None)
+            achieved = 4.0 * samples_per_step / (avg_synth_ms * 1e-3) / 1e9 if avg_synth_ms > 0 else 0.0
+            step_ms = elapsed / args.steps * 1e3
+            step_achieved = 4.0 * samples_per_step / (step_ms * 1e-3) / 1e9
+            solo_achieved = 4.0 * samples_per_step / (solo_ms * 1e-3) / 1e9
+            prof_ms, prof_src = profiled_kernel_ms("bench") if traffic is not None else (None, None)
+            prof1_ms, prof1_src = profiled_kernel_ms("standalone") if traffic is not None else (None, None)
+            line["roofline"] = {
                 "bound": "hbm",
                 "kernel": ("k_synth_g<%d,false>%s" % (min(args.channels, 12), " (+ accumulate launch)" if args.channels > 12 else "")
                            if stats.get("kernel_family") == 1 else
@@ -842,21 +882,20 @@ def main():
                 # the bound that binds: issue slots (north_star's HBM-write fraction above stays the headline `frac`)
                 **({"issue": measured_issue(solo_ms, float(samples_per_step) * args.channels)}
                    if traffic is not None and measured_issue(solo_ms, float(samples_per_step) * args.channels) else {}),
-            },
-        }
+            }
         default_run = (world == 1 and args.workload == "syn12" and args.epochs == 1199 and args.channels == 12 and not strong
                        and args.signal == "boc11")
         if args.signal == "cboc":
             line["config"]["signal"] = "CBOC(6,1,1/11), opt-in mode (not the reference's signal, not the headline)"
             args.no_cpu_baseline = True
         pending = []
-        if world == 1 and args.workload in ("syn12", "dyn") and not strong and args.signal == "boc11" and not args.no_fresh_plan:
+        if args.full and world == 1 and args.workload in ("syn12", "dyn") and not strong and args.signal == "boc11" and not args.no_fresh_plan:
             # the same step on FRESH parameters (plan + execute + finish, another scenario every step), on the headline's handles
             fp, pending = leg_fresh_plan(torch, pkg, engines, outs, n_samp, rate, n_slots, args.channels, args.epochs,
                                          args.steps, elapsed / args.steps * 1e3, dyn_track=(args.workload == "dyn"))
             line["configs"] = {"fresh_plan": fp}
             line["config"]["plan_ms"] = fp["plan_ms"]  # host time of one gal_synth_plan of this workload
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # (in front of the extras, which free the timed outputs: the checker's samples are compared with them)
             line["cpu_baseline"] = cpu_baseline(pkg, params, n_samp, rate, gpu_out=out, extra_checks=pending)  # (world 1: the whole scenario)
             v = line["cpu_baseline"].pop("output_vs_oracle", None)
@@ -872,7 +911,7 @@ def main():
                 raise SystemExit("bench: an output differs from the oracle (headline: %s; fresh-plan scenarios: %s)" % (
                     v and v["int16_different"], xc and [c["int16_different"] for c in xc]))
         del pending
-        if default_run and not args.no_extras:
+        if args.full and default_run and not args.no_extras:
             # untimed-for-headline legs (kernel-only above, kernel + D2H and the file sink here; configs 3/4)
             line["e2e"] = {"kernel_plus_d2h": leg_kernel_plus_d2h(torch, engines, outs, streams, e_first, e_count, n_samp)}
             for eng in engines:

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_json_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--epochs", "24", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--epochs", "24", "--steps", "3", "--warmup", "1", "--full"],
                        capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -42,6 +42,41 @@ def test_bench_json_line():
     assert fp["output_equals_oracle"] is True and len(fp["oracle_checks"]) == 2 and fp["distinct_parameter_sets"] >= 3
     assert fp["oracle_checks"][0]["seed"] != fp["oracle_checks"][1]["seed"]
     assert fp["plan_ms"] > 0 and fp["h2d_ms"] > 0 and fp["ms_per_step"] > 0 and d["config"]["plan_ms"] == fp["plan_ms"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """Without --full the line carries the headline alone; --dump-outputs writes what the last timed step computed: a seeded
+    sample of the IQ and the channels' end state, equal to the oracle's on the same inputs."""
+    import numpy as np
+
+    from oracle_binding import oracle_run
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--epochs", "24", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, cwd=ROOT, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["config"]["chain_mismatch"] == 0
+    for k in ("roofline", "cpu_baseline", "configs", "e2e"):
+        assert k not in d, k
+    files = {f: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert set(files) == {"iq.npy", "iq_position.npy", "state_carr_phase.npy", "state_page.npy", "state_prn.npy"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(os.path.getsize(os.path.join(tmp_path, f)) for f in files) <= 64 << 20
+    sys.path.insert(0, ROOT)
+    from __graft_entry__ import load_pkg
+
+    pkg = load_pkg()
+    params = pkg.shard.rank_workload(0, 24, n_chan=12, n_slots=16, samples_per_epoch=260000, sample_rate=2.6e6)
+    ref_iq, ref_state = oracle_run(params, 260000, 2.6e6)
+    pos = files["iq_position.npy"].astype(np.int64)
+    assert len(pos) == 1 << 21 and np.all(np.diff(pos) > 0) and pos[-1] < 24 * 260000
+    assert np.array_equal(files["iq.npy"], ref_iq.reshape(-1, 2)[pos].astype(np.float32))
+    assert np.array_equal(files["state_carr_phase.npy"].view(np.uint64), ref_state["carr_phase"].view(np.uint64))
 
 
 def test_report_exchange_falls_back_to_the_control_group():
