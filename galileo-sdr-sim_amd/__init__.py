@@ -15,9 +15,14 @@ from .synth import (  # noqa: F401
     CHAN_EPOCH_DTYPE,
     CHAN_STATE_DTYPE,
     GAL_CH_RESTART,
+    GAL_IQ_IBIT,
+    GAL_IQ_IBYTE,
+    GAL_IQ_ISHORT,
+    IQ_FORMATS,
     GalSynthError,
     SynthEngine,
     device_count,
+    iq_bytes,
     load_library,
     pack_page,
     tables,

@@ -9,6 +9,8 @@
 // the reference's `ishort` stream: headerless little-endian interleaved int16 I,Q at 2.6 MS/s, exactly
 // ((int)(10 d + 0.5) - 1) * 260000 * 4 bytes (src/galileo-sdr.cpp:438,536-542); default name
 // galileosim.ishort, "-" = stdout.  Errors print a message and exit(1); success exits 0.
+// --iq-format ibyte|ibit (not in the reference; include/galsynth.h GAL_IQ_*): the same stream as 8-bit IQ (--iq-shift N, default 5)
+// or 1-bit packed IQ, converted on the GPU behind each batch (gal_synth_iq_convert); half / a sixteenth of the bytes to move.
 //
 // Pipeline: a producer thread runs the host front-end (libgalscen: orbits, ranges, I/NAV pages) up to two batches
 // ahead -> the main thread plans and executes each batch on the GPU and, after gal_synth_finish(), enqueues the copy
@@ -57,7 +59,7 @@ void usage(const char *prog)
     printf("Usage: %s [options]\n"
            "Options:\n"
            "  -e <Ephemeris>   RINEX navigation file for Galileo ephemerides (required)\n"
-           "  -o <File sink>   File to store IQ samples (default galileosim.ishort, - = stdout)\n"
+           "  -o <File sink>   File to store IQ samples (default galileosim.<format>, - = stdout)\n"
            "  -l <location>    Lat,Lon,Hgt (static mode) e.g. 35.274,137.014,100\n"
            "  -u <user_motion> ECEF user motion file t,x,y,z at 10 Hz (dynamic mode)\n"
            "  -t <date,time>   Scenario start time YYYY/MM/DD,hh:mm:ss\n"
@@ -79,6 +81,9 @@ void usage(const char *prog)
            "  --sites <file>   One line lat,lon,hgt[,outfile] per receiver site: one process per site over the GPUs of the\n"
            "                   node (--gpus N, default all; --per-gpu K processes per GPU, default 1); -o is the name stem;\n"
            "                   -P <port>: site k listens on port + k (default: no position listener)\n"
+           "  --iq-format <f>  Output format: ishort (interleaved int16, the default), ibyte (interleaved int8: rounded\n"
+           "                   x >> shift, clamped to +-127), ibit (1 bit per value, x > 0, packed MSB first)\n"
+           "  --iq-shift <n>   ibyte only: right shift 0..15 before the clamp (default 5)\n"
            "  --writers <n>    Threads that move finished batches into a regular output file (default 0: sequential write(); > 0: mapped file, n copy threads)\n"
            "  -v               Verbose\n"
            "  -U/-b/-a/-G/-p/-n/-g/-i     accepted for compatibility (file sink only)\n",
@@ -261,7 +266,7 @@ struct Site {
 };
 
 int run_sites(const char *self, const std::vector<std::string> &base_args, const char *sites_file, const char *out_stem,
-              int n_gpus, int per_gpu, int udp_base)
+              int n_gpus, int per_gpu, int udp_base, const char *fmt_name, double bytes_per_sample)
 {
     std::vector<Site> sites;
     FILE *fp = fopen(sites_file, "r");
@@ -283,9 +288,9 @@ int run_sites(const char *self, const std::vector<std::string> &base_args, const
         std::string name(rest);
         while (!name.empty() && (name.back() == '\n' || name.back() == '\r' || name.back() == ' ')) name.pop_back();
         if (name.empty()) {
-            snprintf(buf, sizeof(buf), ".site%zu.ishort", sites.size());
+            const std::string ext = std::string(".") + fmt_name;
+            snprintf(buf, sizeof(buf), ".site%zu%s", sites.size(), ext.c_str());
             std::string stem(out_stem[0] ? out_stem : "galileosim");
-            const std::string ext = ".ishort";
             if (stem.size() > ext.size() && stem.compare(stem.size() - ext.size(), ext.size(), ext) == 0)
                 stem.resize(stem.size() - ext.size());
             name = stem + buf;
@@ -367,7 +372,7 @@ int run_sites(const char *self, const std::vector<std::string> &base_args, const
             const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - lane_t0[l]).count();
             // (the child's wall time: HIP start-up, front-end, synthesis, device->host copy, file -- the sink, not the engine, sets it)
             fprintf(stderr, "site %d (%s) on GPU %d -> %s: %s, %lld bytes in %.2f s = %.0f Msamples/s = %.2f GB/s into its file\n", lane_site[l],
-                    s.llh.c_str(), l % n_gpus, s.out.c_str(), ok ? "ok" : "FAILED", bytes, dt, bytes / 4 / dt / 1e6, bytes / dt / 1e9);
+                    s.llh.c_str(), l % n_gpus, s.out.c_str(), ok ? "ok" : "FAILED", bytes, dt, bytes / bytes_per_sample / dt / 1e6, bytes / dt / 1e9);
             if (!ok) ++failed;
             total_bytes += bytes;
             lane_pid[l] = 0;
@@ -381,7 +386,7 @@ int run_sites(const char *self, const std::vector<std::string> &base_args, const
     const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     fprintf(stderr, "\nDone!\nSites = %zu  failed = %d  Process time = %.2f [sec]  (%.1f Msamples/s aggregate over %d GPU%s, incl. process "
                     "start-up; per site the device->host link and the file system bound this figure, not the synthesis engine: see the "
-                    "per-site lines)\n", sites.size(), failed, el, total_bytes / 4 / el / 1e6, n_gpus, n_gpus > 1 ? "s" : "");
+                    "per-site lines)\n", sites.size(), failed, el, total_bytes / bytes_per_sample / el / 1e6, n_gpus, n_gpus > 1 ? "s" : "");
     return failed ? 1 : 0;
 }
 
@@ -418,10 +423,11 @@ int main(int argc, char *argv[])
     sc.n_slots = GAL_MAX_CHAN;
     bool verbose = false, have_batch = false, udp_given = false, realtime = false, cboc = false, exact_replay = false, shift_toe = false, ref_T = false;
     int batch_epochs = 128, n_writers = -1, sites_gpus = 0, sites_per_gpu = 1;
+    const char *iq_format_arg = "ishort", *iq_shift_arg = nullptr;
     sc.udp_port = GAL_SCEN_UDP_PORT;  // the reference always listens for position updates (src/galileo-sdr.cpp:185)
     sc.udp_loopback = 1;              // ... on every interface; the default listener here takes local datagrams only
 
-    enum { OPT_STRICT = 1000, OPT_SITES, OPT_WRITERS, OPT_GPUS, OPT_PER_GPU, OPT_EXACT, OPT_SHIFT_TOE, OPT_REF_T };
+    enum { OPT_STRICT = 1000, OPT_SITES, OPT_WRITERS, OPT_GPUS, OPT_PER_GPU, OPT_EXACT, OPT_SHIFT_TOE, OPT_REF_T, OPT_IQ_FORMAT, OPT_IQ_SHIFT };
     static const struct option long_opts[] = {{"strict", no_argument, nullptr, OPT_STRICT},
                                               {"exact-replay", no_argument, nullptr, OPT_EXACT},
                                               {"shift-toe", no_argument, nullptr, OPT_SHIFT_TOE},
@@ -430,13 +436,16 @@ int main(int argc, char *argv[])
                                               {"writers", required_argument, nullptr, OPT_WRITERS},
                                               {"gpus", required_argument, nullptr, OPT_GPUS},
                                               {"per-gpu", required_argument, nullptr, OPT_PER_GPU},
+                                              {"iq-format", required_argument, nullptr, OPT_IQ_FORMAT},
+                                              {"iq-shift", required_argument, nullptr, OPT_IQ_SHIFT},
                                               {nullptr, 0, nullptr, 0}};
     std::vector<std::string> child_args;  // --sites: everything but -l / -o / --sites / --gpus / --per-gpu goes to the children
     int opt;
     while ((opt = getopt_long(argc, argv, "e:n:o:u:g:l:T:t:d:G:a:p:iI:U:b:vB:P:rC", long_opts, nullptr)) != -1) {
         if (opt != 'l' && opt != 'o' && opt != 'P' && opt != OPT_SITES && opt != OPT_GPUS && opt != OPT_PER_GPU && opt != '?' && opt != ':') {
             if (opt >= 1000) {
-                child_args.push_back(opt == OPT_STRICT ? "--strict" : opt == OPT_EXACT ? "--exact-replay" : opt == OPT_SHIFT_TOE ? "--shift-toe" : opt == OPT_REF_T ? "--ref-T" : "--writers");
+                child_args.push_back(opt == OPT_STRICT ? "--strict" : opt == OPT_EXACT ? "--exact-replay" : opt == OPT_SHIFT_TOE ? "--shift-toe" : opt == OPT_REF_T ? "--ref-T"
+                                     : opt == OPT_IQ_FORMAT ? "--iq-format" : opt == OPT_IQ_SHIFT ? "--iq-shift" : "--writers");
             } else {
                 char name[3] = {'-', (char)opt, 0};
                 child_args.push_back(name);
@@ -488,6 +497,8 @@ int main(int argc, char *argv[])
         case OPT_WRITERS: n_writers = atoi(optarg); break;
         case OPT_GPUS: sites_gpus = atoi(optarg); break;
         case OPT_PER_GPU: sites_per_gpu = atoi(optarg); break;
+        case OPT_IQ_FORMAT: iq_format_arg = optarg; break;
+        case OPT_IQ_SHIFT: iq_shift_arg = optarg; break;
         case 'n': case 'g': case 'G': case 'a': case 'p': case 'i': case 'U': case 'b': break;
         case ':':
         case '?':
@@ -511,6 +522,31 @@ int main(int argc, char *argv[])
         exit(1);
     }
     if (sc.time_overwrite) sc.time_overwrite = shift_toe ? 2 : 1;
+    // output format: checked here, before any device work
+    static const char *const kIqNames[] = {"ishort", "ibyte", "ibit"};  // GAL_IQ_ISHORT, GAL_IQ_IBYTE, GAL_IQ_IBIT
+    int iq_format = -1, iq_shift = 0;
+    for (int f = 0; f < 3; ++f)
+        if (strcmp(iq_format_arg, kIqNames[f]) == 0) iq_format = f;
+    if (iq_format < 0) {
+        fprintf(stderr, "ERROR: unknown --iq-format '%s' (accepted: ishort, ibyte, ibit).\n", iq_format_arg);
+        exit(1);
+    }
+    if (iq_shift_arg) {
+        char *end = nullptr;
+        const long v = strtol(iq_shift_arg, &end, 10);
+        if (iq_format != GAL_IQ_IBYTE) {
+            fprintf(stderr, "ERROR: --iq-shift applies to --iq-format ibyte only.\n");
+            exit(1);
+        }
+        if (!*iq_shift_arg || *end || v < 0 || v > 15) {
+            fprintf(stderr, "ERROR: --iq-shift '%s' out of range (0..15).\n", iq_shift_arg);
+            exit(1);
+        }
+        iq_shift = (int)v;
+    } else if (iq_format == GAL_IQ_IBYTE) {
+        iq_shift = 5;  // sigma of 9-12 channels ~ 750-870 LSB: 23-27 LSB after the shift, the clamp at ~5 sigma
+    }
+    const double iq_bytes_per_sample = (double)gal_synth_iq_bytes(iq_format, 4) / 4.0;
     if (sitesfile[0]) {
         // several listeners cannot share a port: the sites run without the position listener unless -P names a base port, in
         // which case site k (in file order) listens on port + k
@@ -518,11 +554,12 @@ int main(int argc, char *argv[])
         const ssize_t n = readlink("/proc/self/exe", self, sizeof(self) - 1);
         if (n <= 0) snprintf(self, sizeof(self), "%s", argv[0]);
         else self[n] = 0;
-        return run_sites(self, child_args, sitesfile, outfile, sites_gpus, sites_per_gpu, udp_given ? sc.udp_port : 0);
+        return run_sites(self, child_args, sitesfile, outfile, sites_gpus, sites_per_gpu, udp_given ? sc.udp_port : 0,
+                         kIqNames[iq_format], iq_bytes_per_sample);
     }
     if (outfile[0] == 0) {
-        printf("[+] File sink not specified. Using galileosim.ishort\n");
-        snprintf(outfile, sizeof(outfile), "galileosim.ishort");
+        printf("[+] File sink not specified. Using galileosim.%s\n", kIqNames[iq_format]);
+        snprintf(outfile, sizeof(outfile), "galileosim.%s", kIqNames[iq_format]);
     }
     if (realtime && !have_batch) batch_epochs = 1;  // paced output: position updates take effect within 0.1 s
     if (batch_epochs < 1) batch_epochs = 1;
@@ -564,7 +601,13 @@ int main(int argc, char *argv[])
     cfg.device = getenv("GAL_DEVICE") ? atoi(getenv("GAL_DEVICE")) : -1;
     if (cboc) cfg.flags |= GAL_CFG_CBOC;
     if (exact_replay) cfg.flags |= GAL_CFG_EXACT_REPLAY;
-    const size_t epoch_bytes = (size_t)cfg.samples_per_epoch * 4;
+    // bytes per epoch in the output format: the per-batch split of the copies cuts at epoch boundaries, so every piece must be whole
+    // bytes -- for ibit 260 000 % 4 == 0
+    const size_t epoch_bytes = gal_synth_iq_bytes(iq_format, (size_t)cfg.samples_per_epoch);
+    if (iq_format == GAL_IQ_IBIT && cfg.samples_per_epoch % 4 != 0) {
+        fprintf(stderr, "ERROR: ibit needs a multiple of 4 samples per epoch.\n");
+        exit(1);
+    }
 
     if (n_writers < 0) {
         // Default: the sequential sink.  Measured on the MI355X host (256 cores, tmpfs, 1.25 GB): write() stream 0.20 s;
@@ -590,12 +633,21 @@ int main(int argc, char *argv[])
     }
     stage("gal_synth_create");
     if (batch_epochs > total) batch_epochs = total > 0 ? total : 1;
-    const size_t batch_bytes = epoch_bytes * batch_epochs;
+    const size_t batch_bytes = epoch_bytes * batch_epochs;  // in the output format
+    // d_iq: the engine's int16 output; d_out: what the copies read -- d_iq itself for ishort, the converted batch otherwise
     int16_t *d_iq[2] = {nullptr, nullptr};
+    void *d_out[2] = {nullptr, nullptr};
+    hipEvent_t converted[2] = {nullptr, nullptr};
     Slot slot[2];
     for (int i = 0; i < 2; ++i) {
-        if (hipMalloc((void **)&d_iq[i], batch_bytes) != hipSuccess ||
+        if (hipMalloc((void **)&d_iq[i], (size_t)cfg.samples_per_epoch * 4 * batch_epochs) != hipSuccess ||
             hipHostMalloc((void **)&slot[i].host, batch_bytes, hipHostMallocDefault) != hipSuccess) {
+            fprintf(stderr, "ERROR: buffer allocation failed\n");
+            exit(1);
+        }
+        d_out[i] = d_iq[i];
+        if (iq_format != GAL_IQ_ISHORT &&
+            (hipMalloc(&d_out[i], batch_bytes) != hipSuccess || hipEventCreateWithFlags(&converted[i], hipEventDisableTiming) != hipSuccess)) {
             fprintf(stderr, "ERROR: buffer allocation failed\n");
             exit(1);
         }
@@ -619,7 +671,7 @@ int main(int argc, char *argv[])
         for (int i = 0; i < 2; ++i)
             for (int k = 0; k < 2; ++k) {
                 const size_t off = k ? batch_bytes / 2 : 0, nb = batch_bytes / 2 < ((size_t)1 << 20) ? batch_bytes / 2 : ((size_t)1 << 20);
-                if (nb) hipMemcpyAsync((char *)slot[i].host + off, (const char *)d_iq[i] + off, nb, hipMemcpyDeviceToHost, copy_stream[k]);
+                if (nb) hipMemcpyAsync((char *)slot[i].host + off, (const char *)d_out[i] + off, nb, hipMemcpyDeviceToHost, copy_stream[k]);
             }
         hipStreamSynchronize(copy_stream[0]);
         hipStreamSynchronize(copy_stream[1]);
@@ -745,14 +797,29 @@ int main(int argc, char *argv[])
             fprintf(stderr, "[timing] batch at %7.2f ms: %3d epochs, waited %.2f ms for rows, %.2f for a free slot, plan + execute + finish %.2f\n",
                     std::chrono::duration<double, std::milli>(tb0 - t_start).count(), n, tb_rows, tb_slot - tb_rows, tb_synth - tb_slot);
         slot[cur].bytes = epoch_bytes * n;
+        if (iq_format != GAL_IQ_ISHORT) {
+            // the conversion of the final int16 batch, on the engine's stream; both copy streams wait for it
+            if (gal_synth_iq_convert(eng, d_iq[cur], (size_t)n * cfg.samples_per_epoch, iq_format, iq_shift, d_out[cur]) != GAL_OK) {
+                fprintf(stderr, "\nERROR: %s\n", gal_synth_last_error());
+                rc = 1;
+                break;
+            }
+            if (hipEventRecord(converted[cur], stream) != hipSuccess || hipStreamWaitEvent(copy_stream[0], converted[cur], 0) != hipSuccess ||
+                hipStreamWaitEvent(copy_stream[1], converted[cur], 0) != hipSuccess) {
+                fprintf(stderr, "\nERROR: event after the IQ conversion failed\n");
+                rc = 1;
+                break;
+            }
+        }
         {
+            // split at an epoch boundary: epoch_bytes is whole bytes in every format (see above)
             const size_t half = epoch_bytes * (size_t)((n + 1) / 2);
             const size_t part[2] = {half, slot[cur].bytes - half};
             size_t off = 0;
             hipError_t cerr = hipSuccess;
             for (int k = 0; k < 2; ++k) {
                 if (part[k] && cerr == hipSuccess)
-                    cerr = hipMemcpyAsync((char *)slot[cur].host + off, (const char *)d_iq[cur] + off, part[k],
+                    cerr = hipMemcpyAsync((char *)slot[cur].host + off, (const char *)d_out[cur] + off, part[k],
                                           hipMemcpyDeviceToHost, copy_stream[k]);
                 if (cerr == hipSuccess) cerr = hipEventRecord(slot[cur].copied[k], copy_stream[k]);
                 off += part[k];
@@ -799,6 +866,20 @@ int main(int argc, char *argv[])
     if (gal_scen_eph_gaps(scen) > 0)
         fprintf(stderr, "NOTE: %d (satellite, refresh) pairs ran on a stale ephemeris record (see the warning above)\n",
                 gal_scen_eph_gaps(scen));
+    if (iq_format == GAL_IQ_IBYTE) {
+        // (stderr: with -o - the data go to stdout)
+        uint64_t n_sat = 0;
+        const double n_val = (double)emitted * cfg.samples_per_epoch * 2;
+        if (gal_synth_iq_saturated(eng, &n_sat, 0) != GAL_OK) {
+            fprintf(stderr, "ERROR: %s\n", gal_synth_last_error());
+            rc = 1;
+        } else if (n_sat > 0) {
+            fprintf(stderr, "WARNING: %llu of %.0f IQ values (%.3g %%) saturated at --iq-shift %d; a larger --iq-shift avoids the clipping\n",
+                    (unsigned long long)n_sat, n_val, n_val > 0 ? 100.0 * (double)n_sat / n_val : 0.0, iq_shift);
+        } else if (verbose) {
+            fprintf(stderr, "IQ values saturated at --iq-shift %d: 0 of %.0f\n", iq_shift, n_val);
+        }
+    }
     gal_synth_destroy(eng);
     gal_scen_close(scen);
     stage("teardown");

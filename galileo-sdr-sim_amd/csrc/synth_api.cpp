@@ -90,6 +90,7 @@ int galk_scanm_blocks(int legs);
 size_t galk_scanm_bytes(int S, int legs);
 int galk_launch_synth(const DevPlan *P, const DevPlan *Pd, int nch, int accumulate, const uint8_t *act,
                       const int *nact, uint32_t *iq, int e0, int ne, hipStream_t st);
+hipError_t galk_launch_iq(int format, const int16_t *in, uint64_t n_val, int shift, void *out, unsigned long long *sat, hipStream_t st);
 }
 
 namespace {
@@ -314,6 +315,7 @@ struct gal_synth {
     float ms_plan = 0.0f;         // host time of the last gal_synth_plan (validation, lists, staging; without the wait for the upload)
     double prev_wait_us = 0.0;  // how long the last gal_synth_finish waited for its batch (paces the next one's naps)
     int g_holdoff = 0;  // batches for which k_synth_g is not used although it could be: its last batch listed too many groups
+    unsigned long long *d_iq_sat = nullptr;  // gal_synth_iq_convert: saturated ibyte values (device; made at the first conversion)
 };
 
 // The stream the handle works on: the caller's (gal_synth_set_stream), or one of its own, made at first need.
@@ -540,6 +542,7 @@ int gal_synth_destroy(gal_synth_t *h)
     if (h->arena) hipFree(h->arena);
     if (h->own_iq) hipFree(h->own_iq);
     if (h->own_pin) hipHostFree(h->own_pin);
+    if (h->d_iq_sat) hipFree(h->d_iq_sat);
     if (h->d_lut) hipFree(h->d_lut);
     if (h->d_str) hipFree(h->d_str);
     if (h->h_up) hipHostFree(h->h_up);
@@ -1699,6 +1702,77 @@ int gal_synth_run_host_n(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t
     if (h->stats.synth_runs != 1) HIP_TRY(hipMemcpyAsync(h->own_pin, h->own_iq, bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     memcpy(iq_host, h->own_pin, bytes);
+    return GAL_OK;
+}
+
+// ---- output formats (iq_format.hip) ------------------------------------------------------------------------------------------
+size_t gal_synth_iq_bytes(int32_t format, size_t n_samples)
+{
+    switch (format) {
+    case GAL_IQ_ISHORT: return 4 * n_samples;
+    case GAL_IQ_IBYTE: return 2 * n_samples;
+    case GAL_IQ_IBIT: return (n_samples + 3) / 4;
+    default: return 0;
+    }
+}
+
+int gal_synth_iq_convert(gal_synth_t *h, const int16_t *iq_dev, size_t n_samples, int32_t format, int32_t shift, void *out_dev)
+{
+    if (!h) return fail(GAL_E_INVAL, "null handle");
+    if (format != GAL_IQ_ISHORT && format != GAL_IQ_IBYTE && format != GAL_IQ_IBIT)
+        return fail(GAL_E_INVAL, "gal_synth_iq_convert: unknown format %d (GAL_IQ_ISHORT 0, GAL_IQ_IBYTE 1, GAL_IQ_IBIT 2)", format);
+    if (format == GAL_IQ_IBYTE ? (shift < 0 || shift > 15) : shift != 0)
+        return fail(GAL_E_INVAL, "gal_synth_iq_convert: shift %d (0..15 for GAL_IQ_IBYTE, 0 otherwise)", shift);
+    if (!iq_dev || !out_dev || ((uintptr_t)iq_dev & 15) || ((uintptr_t)out_dev & 15))
+        return fail(GAL_E_INVAL, "gal_synth_iq_convert: device pointers must be non-null and 16-byte aligned");
+    if (n_samples == 0) return GAL_OK;
+    {  // in place would race (ibyte: lane i writes where lane i / 2 reads), and the kernels take both as __restrict__
+        const char *x = (const char *)iq_dev, *y = x + 4 * n_samples;
+        const char *o = (const char *)out_dev, *e = o + gal_synth_iq_bytes(format, n_samples);
+        if (x < e && o < y) return fail(GAL_E_INVAL, "gal_synth_iq_convert: input and output overlap");
+    }
+    if (h->in_flight && h->last_iq) {  // the batch in flight may still be synthesised again by gal_synth_finish
+        const char *a = (const char *)h->last_iq, *b = a + (size_t)h->range_ne * (size_t)h->P.N * 4;
+        const char *x = (const char *)iq_dev, *y = x + 4 * n_samples;
+        if (x < b && a < y) return fail(GAL_E_STATE, "gal_synth_iq_convert: input of the batch in flight (call gal_synth_finish first)");
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = handle_stream(h);
+    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
+    if (format == GAL_IQ_ISHORT) {
+        HIP_TRY(hipMemcpyAsync(out_dev, iq_dev, 4 * n_samples, hipMemcpyDeviceToDevice, st));
+        return GAL_OK;
+    }
+    if (!h->d_iq_sat) {
+        unsigned long long *c = nullptr;
+        HIP_TRY(hipMalloc((void **)&c, sizeof(unsigned long long)));
+        const hipError_t err = hipMemsetAsync(c, 0, sizeof(unsigned long long), st);
+        if (err != hipSuccess) {  // (never keep a counter that was not zeroed)
+            hipFree(c);
+            return fail(GAL_E_DEVICE, "gal_synth_iq_convert: hipMemsetAsync of the counter failed: %s", hipGetErrorString(err));
+        }
+        h->d_iq_sat = c;
+    }
+    HIP_TRY(galk_launch_iq(format, iq_dev, 2 * (uint64_t)n_samples, shift, out_dev, h->d_iq_sat, st));
+    return GAL_OK;
+}
+
+int gal_synth_iq_saturated(gal_synth_t *h, uint64_t *n_saturated, int32_t reset)
+{
+    if (!h || !n_saturated) return fail(GAL_E_INVAL, "gal_synth_iq_saturated: null argument");
+    *n_saturated = 0;
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = handle_stream(h);
+    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
+    if (!h->d_iq_sat) {  // no ibyte conversion yet (the counter is made by the first): still the fence for ibit / ishort conversions
+        HIP_TRY(hipStreamSynchronize(st));
+        return GAL_OK;
+    }
+    unsigned long long v = 0;
+    HIP_TRY(hipMemcpyAsync(&v, h->d_iq_sat, sizeof(v), hipMemcpyDeviceToHost, st));
+    if (reset) HIP_TRY(hipMemsetAsync(h->d_iq_sat, 0, sizeof(v), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *n_saturated = (uint64_t)v;
     return GAL_OK;
 }
 

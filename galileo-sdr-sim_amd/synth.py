@@ -21,6 +21,12 @@ GAL_CFG_VERIFY_SAMPLED = 16  # k_synth_g batches: re-walk a rotating eighth of t
 GAL_CFG_CBOC = 2  # opt-in CBOC(6,1,1/11) sub-carrier (not in the reference; defined by the oracle's CBOC mode)
 
 GAL_CH_RESTART = 1
+# output formats (gal_synth_iq_convert): interleaved int16, int8 (rounded shift, symmetric clamp), 1 bit (MSB first)
+GAL_IQ_ISHORT = 0
+GAL_IQ_IBYTE = 1
+GAL_IQ_IBIT = 2
+IQ_FORMATS = {"ishort": GAL_IQ_ISHORT, "ibyte": GAL_IQ_IBYTE, "ibit": GAL_IQ_IBIT}
+IQ_SHIFT_DEFAULT = 5  # ibyte: the CLI's default --iq-shift
 GAL_PAGE_WORDS = 16
 GAL_N_SYM_PAGE = 500
 
@@ -108,6 +114,9 @@ EXPORTED_SYMBOLS = (
     "gal_synth_stats_size",
     "gal_synth_run_host",
     "gal_synth_run_host_n",
+    "gal_synth_iq_bytes",
+    "gal_synth_iq_convert",
+    "gal_synth_iq_saturated",
     "gal_tables_e1b",
     "gal_tables_e1c",
     "gal_tables_cos512",
@@ -157,6 +166,12 @@ def load_library(hooks=False):
     lib.gal_synth_finish_n.argtypes = [vp, vp, ctypes.POINTER(_Stats), ctypes.c_size_t]
     lib.gal_synth_run_host_n.argtypes = [vp, vp, i32, vp, vp, vp, ctypes.POINTER(_Stats), ctypes.c_size_t]
     lib.gal_synth_stats_size.restype = ctypes.c_size_t
+    lib.gal_synth_iq_bytes.argtypes = [i32, ctypes.c_size_t]
+    lib.gal_synth_iq_bytes.restype = ctypes.c_size_t
+    lib.gal_synth_iq_convert.argtypes = [vp, vp, ctypes.c_size_t, i32, i32, vp]
+    lib.gal_synth_iq_convert.restype = ctypes.c_int
+    lib.gal_synth_iq_saturated.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), i32]
+    lib.gal_synth_iq_saturated.restype = ctypes.c_int
     for name in ("gal_tables_e1b", "gal_tables_e1c", "gal_tables_cos512", "gal_tables_sin512"):
         getattr(lib, name).restype = vp
     lib.gal_tables_cs25.restype = ctypes.c_uint32
@@ -166,6 +181,20 @@ def load_library(hooks=False):
 
 def device_count():
     return int(load_library().gal_synth_device_count())
+
+
+def iq_format_code(fmt):
+    """"ishort" | "ibyte" | "ibit" (or the GAL_IQ_* integer) -> the GAL_IQ_* integer."""
+    if isinstance(fmt, str):
+        if fmt not in IQ_FORMATS:
+            raise ValueError("unknown IQ format %r (accepted: %s)" % (fmt, ", ".join(IQ_FORMATS)))
+        return IQ_FORMATS[fmt]
+    return int(fmt)
+
+
+def iq_bytes(fmt, n_samples):
+    """Bytes that n_samples complex samples take in `fmt`: 4 n, 2 n, ceil(n / 4); 0 for an unknown integer format (no GPU needed)."""
+    return int(load_library().gal_synth_iq_bytes(iq_format_code(fmt), int(n_samples)))
 
 
 def tables():
@@ -302,3 +331,20 @@ class SynthEngine:
         )
         self.n_epochs = p.shape[0]
         return iq, st, {k: getattr(stats, k) for k, _ in _Stats._fields_}
+
+    def iq_convert(self, iq_ptr, n_samples, fmt, shift=None, out_ptr=None):
+        """Enqueue on the handle's stream: n_samples complex int16 samples at device address iq_ptr (final output: behind finish())
+        -> `fmt` ("ishort" | "ibyte" | "ibit") at device address out_ptr (iq_bytes(fmt, n_samples) bytes, not overlapping the input).
+        Both 16-byte aligned; shift 0..15 for "ibyte" (None: IQ_SHIFT_DEFAULT), 0 (or None) otherwise.  iq_saturated() is the fence."""
+        if out_ptr is None:
+            raise ValueError("iq_convert: out_ptr is required")
+        if shift is None:
+            shift = IQ_SHIFT_DEFAULT if iq_format_code(fmt) == GAL_IQ_IBYTE else 0
+        self._check(self._lib.gal_synth_iq_convert(self._h, ctypes.c_void_p(int(iq_ptr)), int(n_samples), iq_format_code(fmt),
+                                                   int(shift), ctypes.c_void_p(int(out_ptr))))
+
+    def iq_saturated(self, reset=False):
+        """Waits for the conversions enqueued so far; int16 values saturated by "ibyte" conversions since create (or the last reset)."""
+        n = ctypes.c_uint64(0)
+        self._check(self._lib.gal_synth_iq_saturated(self._h, ctypes.byref(n), 1 if reset else 0))
+        return int(n.value)

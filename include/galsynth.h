@@ -253,6 +253,29 @@ int gal_synth_run_host_n(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t
     gal_synth_run_host_n((h), (params), (n_epochs), (state_in), (iq_host), (state_out), (stats), sizeof(gal_synth_stats_t))
 #endif
 
+/*
+ * Output formats.  x[j] = the interleaved int16 stream gal_synth_execute writes (I0, Q0, I1, Q1, ...):
+ *   GAL_IQ_ISHORT  x itself, 4 bytes per complex sample (the reference's format)
+ *   GAL_IQ_IBYTE   out[j] = (int8) clamp((x[j] + r) >> shift, -127, 127), r = shift ? 1 << (shift - 1) : 0 (int32 arithmetic shift:
+ *                  round to nearest), 2 bytes per complex sample; a value whose shifted v lies outside [-127, 127] is SATURATED
+ *   GAL_IQ_IBIT    bit = x[j] > 0, byte k holds x[8k] .. x[8k+7] with x[8k] in bit 7 (MSB first: numpy.packbits(x > 0)), the unused
+ *                  low bits of the last byte 0; ceil(n / 4) bytes for n complex samples; nothing saturates
+ */
+#define GAL_IQ_ISHORT 0
+#define GAL_IQ_IBYTE 1
+#define GAL_IQ_IBIT 2
+/* Bytes that n_samples complex samples take in `format`: 4 n, 2 n, ceil(n / 4); 0 for an unknown format.  Needs no GPU. */
+size_t gal_synth_iq_bytes(int32_t format, size_t n_samples);
+/* Enqueue on the handle's stream: convert n_samples interleaved int16 complex samples at iq_dev into `format` at out_dev (both DEVICE
+ * memory, 16-byte aligned, not overlapping; out_dev holds gal_synth_iq_bytes(format, n_samples) bytes).  iq_dev must be FINAL
+ * output: enqueue this behind gal_synth_finish of the batch that wrote it (GAL_E_STATE for a buffer of the batch in flight).
+ * shift: 0..15 for GAL_IQ_IBYTE, 0 otherwise.  GAL_IQ_ISHORT is a device copy.  Saturated values add to the handle's counter.
+ * GAL_E_INVAL for a null handle, an unknown format, a bad shift, a null or misaligned pointer, input and output that overlap. */
+int gal_synth_iq_convert(gal_synth_t *h, const int16_t *iq_dev, size_t n_samples, int32_t format, int32_t shift, void *out_dev);
+/* Wait for the conversions enqueued so far (whatever their format: this is their fence); *n_saturated = int16 values saturated since create (or since the last reset);
+ * reset != 0 sets the counter back to 0. */
+int gal_synth_iq_saturated(gal_synth_t *h, uint64_t *n_saturated, int32_t reset);
+
 /* Signal tables as the engine uses them (for tests and for the oracle to share DATA, not code). */
 const uint32_t *gal_tables_e1b(void);   /* [50][128] */
 const uint32_t *gal_tables_e1c(void);   /* [50][128] */
