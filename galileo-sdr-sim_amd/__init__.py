@@ -24,6 +24,7 @@ from .synth import (  # noqa: F401
     device_count,
     iq_bytes,
     load_library,
+    noise_from_cn0,
     pack_page,
     tables,
     unpack_page,

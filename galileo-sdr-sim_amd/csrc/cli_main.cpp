@@ -11,6 +11,8 @@
 // galileosim.ishort, "-" = stdout.  Errors print a message and exit(1); success exits 0.
 // --iq-format ibyte|ibit (not in the reference; include/galsynth.h GAL_IQ_*): the same stream as 8-bit IQ (--iq-shift N, default 5)
 // or 1-bit packed IQ, converted on the GPU behind each batch (gal_synth_iq_convert); half / a sixteenth of the bytes to move.
+// --cn0 <dBHz> (not in the reference either): a seeded white Gaussian noise floor under the signals, in every format, mixed in on the
+// GPU in the same pass (gal_synth_iq_convert_noise); the file is a fixed function of the command line, whatever the batch length.
 //
 // Pipeline: a producer thread runs the host front-end (libgalscen: orbits, ranges, I/NAV pages) up to two batches
 // ahead -> the main thread plans and executes each batch on the GPU and, after gal_synth_finish(), enqueues the copy
@@ -84,6 +86,12 @@ void usage(const char *prog)
            "  --iq-format <f>  Output format: ishort (interleaved int16, the default), ibyte (interleaved int8: rounded\n"
            "                   x >> shift, clamped to +-127), ibit (1 bit per value, x > 0, packed MSB first)\n"
            "  --iq-shift <n>   ibyte only: right shift 0..15 before the clamp (default 5)\n"
+           "  --cn0 <dBHz>     Add a white Gaussian noise floor: C/N0 of one satellite's composite E1B + E1C signal (E1B alone is\n"
+           "                   3 dB lower); every format; the same bytes for the same options on any machine (default: no noise)\n"
+           "  --noise-seed <n> with --cn0: seed of the noise, 0 .. 2^64 - 1 (default 1)\n"
+           "  --noise-stream <n> with --cn0: independent noise under the same seed, 0 .. 2^32 - 1 (default 0; --sites: the site's index)\n"
+           "  --signal-gain <g> with --cn0: gain on the signals, 0 < g <= 16 (default: the largest power of two <= 1 that keeps\n"
+           "                   5 sigma of noise + the largest signal sum inside int16)\n"
            "  --writers <n>    Threads that move finished batches into a regular output file (default 0: sequential write(); > 0: mapped file, n copy threads)\n"
            "  -v               Verbose\n"
            "  -U/-b/-a/-G/-p/-n/-g/-i     accepted for compatibility (file sink only)\n",
@@ -266,7 +274,7 @@ struct Site {
 };
 
 int run_sites(const char *self, const std::vector<std::string> &base_args, const char *sites_file, const char *out_stem,
-              int n_gpus, int per_gpu, int udp_base, const char *fmt_name, double bytes_per_sample)
+              int n_gpus, int per_gpu, int udp_base, const char *fmt_name, double bytes_per_sample, bool noise_on)
 {
     std::vector<Site> sites;
     FILE *fp = fopen(sites_file, "r");
@@ -335,6 +343,10 @@ int run_sites(const char *self, const std::vector<std::string> &base_args, const
             args.push_back(s.out);
             args.push_back("-P");
             args.push_back(std::to_string(udp_base > 0 ? udp_base + (int)next : 0));
+            if (noise_on) {  // site i: noise stream i -- two sites never share their noise
+                args.push_back("--noise-stream");
+                args.push_back(std::to_string(next));
+            }
             const pid_t pid = fork();
             if (pid < 0) {
                 perror("fork");
@@ -424,10 +436,12 @@ int main(int argc, char *argv[])
     bool verbose = false, have_batch = false, udp_given = false, realtime = false, cboc = false, exact_replay = false, shift_toe = false, ref_T = false;
     int batch_epochs = 128, n_writers = -1, sites_gpus = 0, sites_per_gpu = 1;
     const char *iq_format_arg = "ishort", *iq_shift_arg = nullptr;
+    const char *cn0_arg = nullptr, *noise_seed_arg = nullptr, *noise_stream_arg = nullptr, *signal_gain_arg = nullptr;
     sc.udp_port = GAL_SCEN_UDP_PORT;  // the reference always listens for position updates (src/galileo-sdr.cpp:185)
     sc.udp_loopback = 1;              // ... on every interface; the default listener here takes local datagrams only
 
-    enum { OPT_STRICT = 1000, OPT_SITES, OPT_WRITERS, OPT_GPUS, OPT_PER_GPU, OPT_EXACT, OPT_SHIFT_TOE, OPT_REF_T, OPT_IQ_FORMAT, OPT_IQ_SHIFT };
+    enum { OPT_STRICT = 1000, OPT_SITES, OPT_WRITERS, OPT_GPUS, OPT_PER_GPU, OPT_EXACT, OPT_SHIFT_TOE, OPT_REF_T, OPT_IQ_FORMAT, OPT_IQ_SHIFT, OPT_CN0, OPT_NOISE_SEED,
+           OPT_NOISE_STREAM, OPT_SIGNAL_GAIN };
     static const struct option long_opts[] = {{"strict", no_argument, nullptr, OPT_STRICT},
                                               {"exact-replay", no_argument, nullptr, OPT_EXACT},
                                               {"shift-toe", no_argument, nullptr, OPT_SHIFT_TOE},
@@ -438,14 +452,19 @@ int main(int argc, char *argv[])
                                               {"per-gpu", required_argument, nullptr, OPT_PER_GPU},
                                               {"iq-format", required_argument, nullptr, OPT_IQ_FORMAT},
                                               {"iq-shift", required_argument, nullptr, OPT_IQ_SHIFT},
+                                              {"cn0", required_argument, nullptr, OPT_CN0},
+                                              {"noise-seed", required_argument, nullptr, OPT_NOISE_SEED},
+                                              {"noise-stream", required_argument, nullptr, OPT_NOISE_STREAM},
+                                              {"signal-gain", required_argument, nullptr, OPT_SIGNAL_GAIN},
                                               {nullptr, 0, nullptr, 0}};
-    std::vector<std::string> child_args;  // --sites: everything but -l / -o / --sites / --gpus / --per-gpu goes to the children
+    std::vector<std::string> child_args;  // --sites: everything but -l / -o / --sites / --gpus / --per-gpu / --noise-stream goes to the children
     int opt;
     while ((opt = getopt_long(argc, argv, "e:n:o:u:g:l:T:t:d:G:a:p:iI:U:b:vB:P:rC", long_opts, nullptr)) != -1) {
-        if (opt != 'l' && opt != 'o' && opt != 'P' && opt != OPT_SITES && opt != OPT_GPUS && opt != OPT_PER_GPU && opt != '?' && opt != ':') {
+        if (opt != 'l' && opt != 'o' && opt != 'P' && opt != OPT_SITES && opt != OPT_GPUS && opt != OPT_PER_GPU && opt != OPT_NOISE_STREAM && opt != '?' && opt != ':') {
             if (opt >= 1000) {
                 child_args.push_back(opt == OPT_STRICT ? "--strict" : opt == OPT_EXACT ? "--exact-replay" : opt == OPT_SHIFT_TOE ? "--shift-toe" : opt == OPT_REF_T ? "--ref-T"
-                                     : opt == OPT_IQ_FORMAT ? "--iq-format" : opt == OPT_IQ_SHIFT ? "--iq-shift" : "--writers");
+                                     : opt == OPT_IQ_FORMAT ? "--iq-format" : opt == OPT_IQ_SHIFT ? "--iq-shift" : opt == OPT_CN0 ? "--cn0"
+                                     : opt == OPT_NOISE_SEED ? "--noise-seed" : opt == OPT_SIGNAL_GAIN ? "--signal-gain" : "--writers");
             } else {
                 char name[3] = {'-', (char)opt, 0};
                 child_args.push_back(name);
@@ -499,6 +518,10 @@ int main(int argc, char *argv[])
         case OPT_PER_GPU: sites_per_gpu = atoi(optarg); break;
         case OPT_IQ_FORMAT: iq_format_arg = optarg; break;
         case OPT_IQ_SHIFT: iq_shift_arg = optarg; break;
+        case OPT_CN0: cn0_arg = optarg; break;
+        case OPT_NOISE_SEED: noise_seed_arg = optarg; break;
+        case OPT_NOISE_STREAM: noise_stream_arg = optarg; break;
+        case OPT_SIGNAL_GAIN: signal_gain_arg = optarg; break;
         case 'n': case 'g': case 'G': case 'a': case 'p': case 'i': case 'U': case 'b': break;
         case ':':
         case '?':
@@ -546,6 +569,75 @@ int main(int argc, char *argv[])
     } else if (iq_format == GAL_IQ_IBYTE) {
         iq_shift = 5;  // sigma of 9-12 channels ~ 750-870 LSB: 23-27 LSB after the shift, the clamp at ~5 sigma
     }
+    // noise floor: checked here too.  Without --cn0 nothing below differs from a build without it.
+    const double kSampleRate = 2.6e6;
+    bool noise_on = false;
+    gal_iq_noise_t noise;
+    memset(&noise, 0, sizeof(noise));
+    if (!cn0_arg && (noise_seed_arg || noise_stream_arg || signal_gain_arg)) {
+        fprintf(stderr, "ERROR: --noise-seed, --noise-stream and --signal-gain need --cn0 <dBHz>.\n");
+        exit(1);
+    }
+    if (cn0_arg) {
+        char *end = nullptr;
+        const double cn0 = strtod(cn0_arg, &end);
+        if (!*cn0_arg || *end) {
+            fprintf(stderr, "ERROR: --cn0 '%s' is not a number (dB-Hz).\n", cn0_arg);
+            exit(1);
+        }
+        double gain = 0.0;
+        if (signal_gain_arg) {
+            gain = strtod(signal_gain_arg, &end);
+            if (!*signal_gain_arg || *end || !(gain > 0.0 && gain <= 16.0)) {
+                fprintf(stderr, "ERROR: --signal-gain '%s' out of range (0 < g <= 16).\n", signal_gain_arg);
+                exit(1);
+            }
+        } else {
+            // the largest power of two <= 1 with 5 sigma + 4100 g <= 32767 (4100: the largest |x| of the reference's scenarios,
+            // DESIGN.md section 10); sigma is proportional to g
+            gal_iq_noise_t unit;
+            if (gal_synth_noise_from_cn0(cn0, kSampleRate, 1.0, &unit) != GAL_OK) {
+                fprintf(stderr, "ERROR: --cn0 %s: %s\n", cn0_arg, gal_synth_last_error());
+                exit(1);
+            }
+            gain = 1.0;
+            while (gain > 1.0 / 65536.0 && (5.0 * (unit.sigma_q4 / 16.0) + 4100.0) * gain > 32767.0) gain *= 0.5;
+        }
+        if (gal_synth_noise_from_cn0(cn0, kSampleRate, gain, &noise) != GAL_OK) {
+            fprintf(stderr, "ERROR: --cn0 %s: %s\n", cn0_arg, gal_synth_last_error());
+            exit(1);
+        }
+        noise.seed = 1;
+        if (noise_seed_arg) {
+            errno = 0;
+            noise.seed = strtoull(noise_seed_arg, &end, 0);
+            if (!*noise_seed_arg || *end || errno || noise_seed_arg[0] == '-') {
+                fprintf(stderr, "ERROR: --noise-seed '%s' is not an unsigned 64-bit integer.\n", noise_seed_arg);
+                exit(1);
+            }
+        }
+        if (noise_stream_arg) {
+            errno = 0;
+            const unsigned long long v = strtoull(noise_stream_arg, &end, 0);
+            if (!*noise_stream_arg || *end || errno || noise_stream_arg[0] == '-' || v > 0xffffffffull) {
+                fprintf(stderr, "ERROR: --noise-stream '%s' is not an unsigned 32-bit integer.\n", noise_stream_arg);
+                exit(1);
+            }
+            noise.stream = (uint32_t)v;
+        }
+        noise_on = true;
+        const double sigma = noise.sigma_q4 / 16.0;
+        if (iq_format == GAL_IQ_IBYTE && !iq_shift_arg) {  // the smallest shift with 127 x 2^s >= 4 sigma
+            iq_shift = 0;
+            while (iq_shift < 15 && 127.0 * (double)(1 << iq_shift) < 4.0 * sigma) ++iq_shift;
+        }
+        if (!sitesfile[0]) {  // (--sites: every child prints its own)
+            fprintf(stderr, "Noise floor: C/N0 %g dB-Hz -> sigma %.1f LSB, signal gain %g%s, seed %llu, stream %u", cn0, sigma, gain,
+                    signal_gain_arg ? "" : " (chosen)", (unsigned long long)noise.seed, noise.stream);
+            if (iq_format == GAL_IQ_IBYTE) fprintf(stderr, ", --iq-shift %d%s", iq_shift, iq_shift_arg ? "" : " (chosen)");
+            fprintf(stderr, "\n");
+        }
+    }
     const double iq_bytes_per_sample = (double)gal_synth_iq_bytes(iq_format, 4) / 4.0;
     if (sitesfile[0]) {
         // several listeners cannot share a port: the sites run without the position listener unless -P names a base port, in
@@ -555,7 +647,7 @@ int main(int argc, char *argv[])
         if (n <= 0) snprintf(self, sizeof(self), "%s", argv[0]);
         else self[n] = 0;
         return run_sites(self, child_args, sitesfile, outfile, sites_gpus, sites_per_gpu, udp_given ? sc.udp_port : 0,
-                         kIqNames[iq_format], iq_bytes_per_sample);
+                         kIqNames[iq_format], iq_bytes_per_sample, noise_on);
     }
     if (outfile[0] == 0) {
         printf("[+] File sink not specified. Using galileosim.%s\n", kIqNames[iq_format]);
@@ -595,7 +687,7 @@ int main(int argc, char *argv[])
 
     gal_synth_cfg_t cfg;
     memset(&cfg, 0, sizeof(cfg));
-    cfg.sample_rate = 2.6e6;
+    cfg.sample_rate = kSampleRate;
     cfg.samples_per_epoch = 260000;
     cfg.n_slots = sc.n_slots;
     cfg.device = getenv("GAL_DEVICE") ? atoi(getenv("GAL_DEVICE")) : -1;
@@ -634,7 +726,8 @@ int main(int argc, char *argv[])
     stage("gal_synth_create");
     if (batch_epochs > total) batch_epochs = total > 0 ? total : 1;
     const size_t batch_bytes = epoch_bytes * batch_epochs;  // in the output format
-    // d_iq: the engine's int16 output; d_out: what the copies read -- d_iq itself for ishort, the converted batch otherwise
+    // d_iq: the engine's int16 output; d_out: what the copies read -- d_iq itself for ishort (with --cn0: after the noise pass has
+    // run in place), the converted batch otherwise
     int16_t *d_iq[2] = {nullptr, nullptr};
     void *d_out[2] = {nullptr, nullptr};
     hipEvent_t converted[2] = {nullptr, nullptr};
@@ -646,8 +739,11 @@ int main(int argc, char *argv[])
             exit(1);
         }
         d_out[i] = d_iq[i];
-        if (iq_format != GAL_IQ_ISHORT &&
-            (hipMalloc(&d_out[i], batch_bytes) != hipSuccess || hipEventCreateWithFlags(&converted[i], hipEventDisableTiming) != hipSuccess)) {
+        if (iq_format != GAL_IQ_ISHORT && hipMalloc(&d_out[i], batch_bytes) != hipSuccess) {
+            fprintf(stderr, "ERROR: buffer allocation failed\n");
+            exit(1);
+        }
+        if ((iq_format != GAL_IQ_ISHORT || noise_on) && hipEventCreateWithFlags(&converted[i], hipEventDisableTiming) != hipSuccess) {
             fprintf(stderr, "ERROR: buffer allocation failed\n");
             exit(1);
         }
@@ -797,9 +893,15 @@ int main(int argc, char *argv[])
             fprintf(stderr, "[timing] batch at %7.2f ms: %3d epochs, waited %.2f ms for rows, %.2f for a free slot, plan + execute + finish %.2f\n",
                     std::chrono::duration<double, std::milli>(tb0 - t_start).count(), n, tb_rows, tb_slot - tb_rows, tb_synth - tb_slot);
         slot[cur].bytes = epoch_bytes * n;
-        if (iq_format != GAL_IQ_ISHORT) {
-            // the conversion of the final int16 batch, on the engine's stream; both copy streams wait for it
-            if (gal_synth_iq_convert(eng, d_iq[cur], (size_t)n * cfg.samples_per_epoch, iq_format, iq_shift, d_out[cur]) != GAL_OK) {
+        if (iq_format != GAL_IQ_ISHORT || noise_on) {
+            // the conversion of the final int16 batch, on the engine's stream; both copy streams wait for it.  With --cn0 the noise
+            // goes in in the same pass (ishort: in place in d_iq[cur]); first_sample is the running sample count, so the file does
+            // not depend on the batch length
+            const size_t n_samples = (size_t)n * cfg.samples_per_epoch;
+            const int crc = noise_on ? gal_synth_iq_convert_noise(eng, d_iq[cur], n_samples, (uint64_t)emitted * (uint64_t)cfg.samples_per_epoch,
+                                                                  &noise, iq_format, iq_shift, d_out[cur])
+                                     : gal_synth_iq_convert(eng, d_iq[cur], n_samples, iq_format, iq_shift, d_out[cur]);
+            if (crc != GAL_OK) {
                 fprintf(stderr, "\nERROR: %s\n", gal_synth_last_error());
                 rc = 1;
                 break;
@@ -866,17 +968,20 @@ int main(int argc, char *argv[])
     if (gal_scen_eph_gaps(scen) > 0)
         fprintf(stderr, "NOTE: %d (satellite, refresh) pairs ran on a stale ephemeris record (see the warning above)\n",
                 gal_scen_eph_gaps(scen));
-    if (iq_format == GAL_IQ_IBYTE) {
+    if (iq_format == GAL_IQ_IBYTE || noise_on) {
         // (stderr: with -o - the data go to stdout)
         uint64_t n_sat = 0;
         const double n_val = (double)emitted * cfg.samples_per_epoch * 2;
         if (gal_synth_iq_saturated(eng, &n_sat, 0) != GAL_OK) {
             fprintf(stderr, "ERROR: %s\n", gal_synth_last_error());
             rc = 1;
+        } else if (n_sat > 0 && iq_format != GAL_IQ_IBYTE) {
+            fprintf(stderr, "WARNING: %llu of %.0f IQ values (%.3g %%) saturated at int16; a smaller --signal-gain avoids the clipping\n",
+                    (unsigned long long)n_sat, n_val, n_val > 0 ? 100.0 * (double)n_sat / n_val : 0.0);
         } else if (n_sat > 0) {
             fprintf(stderr, "WARNING: %llu of %.0f IQ values (%.3g %%) saturated at --iq-shift %d; a larger --iq-shift avoids the clipping\n",
                     (unsigned long long)n_sat, n_val, n_val > 0 ? 100.0 * (double)n_sat / n_val : 0.0, iq_shift);
-        } else if (verbose) {
+        } else if (verbose && iq_format == GAL_IQ_IBYTE) {
             fprintf(stderr, "IQ values saturated at --iq-shift %d: 0 of %.0f\n", iq_shift, n_val);
         }
     }

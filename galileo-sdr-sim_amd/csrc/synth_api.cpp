@@ -91,6 +91,8 @@ size_t galk_scanm_bytes(int S, int legs);
 int galk_launch_synth(const DevPlan *P, const DevPlan *Pd, int nch, int accumulate, const uint8_t *act,
                       const int *nact, uint32_t *iq, int e0, int ne, hipStream_t st);
 hipError_t galk_launch_iq(int format, const int16_t *in, uint64_t n_val, int shift, void *out, unsigned long long *sat, hipStream_t st);
+hipError_t galk_launch_iq_noise(int format, const int16_t *in, uint64_t n_val, uint64_t first_sample, uint64_t seed, uint32_t stream,
+                                uint32_t gain_q16, uint32_t sigma_q4, int shift, void *out, unsigned long long *sat, hipStream_t st);
 }
 
 namespace {
@@ -1754,6 +1756,66 @@ int gal_synth_iq_convert(gal_synth_t *h, const int16_t *iq_dev, size_t n_samples
         h->d_iq_sat = c;
     }
     HIP_TRY(galk_launch_iq(format, iq_dev, 2 * (uint64_t)n_samples, shift, out_dev, h->d_iq_sat, st));
+    return GAL_OK;
+}
+
+// ---- noise floor (iq_noise.hip) ----------------------------------------------------------------------------------------------
+int gal_synth_iq_convert_noise(gal_synth_t *h, const int16_t *iq_dev, size_t n_samples, uint64_t first_sample, const gal_iq_noise_t *noise,
+                               int32_t format, int32_t shift, void *out_dev)
+{
+    if (!noise) return gal_synth_iq_convert(h, iq_dev, n_samples, format, shift, out_dev);
+    if (!h) return fail(GAL_E_INVAL, "null handle");
+    if (format != GAL_IQ_ISHORT && format != GAL_IQ_IBYTE && format != GAL_IQ_IBIT)
+        return fail(GAL_E_INVAL, "gal_synth_iq_convert_noise: unknown format %d (GAL_IQ_ISHORT 0, GAL_IQ_IBYTE 1, GAL_IQ_IBIT 2)", format);
+    if (format == GAL_IQ_IBYTE ? (shift < 0 || shift > 15) : shift != 0)
+        return fail(GAL_E_INVAL, "gal_synth_iq_convert_noise: shift %d (0..15 for GAL_IQ_IBYTE, 0 otherwise)", shift);
+    if (noise->gain_q16 > (1u << 20) || noise->sigma_q4 > (1u << 20) || noise->reserved != 0)
+        return fail(GAL_E_INVAL, "gal_synth_iq_convert_noise: gain_q16 %u, sigma_q4 %u (both 0..2^20), reserved %u (0)", noise->gain_q16,
+                    noise->sigma_q4, noise->reserved);
+    if (first_sample >> 62) return fail(GAL_E_INVAL, "gal_synth_iq_convert_noise: first_sample must be below 2^62");
+    if (!iq_dev || !out_dev || ((uintptr_t)iq_dev & 15) || ((uintptr_t)out_dev & 15))
+        return fail(GAL_E_INVAL, "gal_synth_iq_convert_noise: device pointers must be non-null and 16-byte aligned");
+    if (n_samples == 0) return GAL_OK;
+    if (!(format == GAL_IQ_ISHORT && (const void *)iq_dev == out_dev)) {  // exactly in place: every lane rewrites the vector it has read
+        const char *x = (const char *)iq_dev, *y = x + 4 * n_samples;
+        const char *o = (const char *)out_dev, *e = o + gal_synth_iq_bytes(format, n_samples);
+        if (x < e && o < y) return fail(GAL_E_INVAL, "gal_synth_iq_convert_noise: input and output overlap (only ishort exactly in place may)");
+    }
+    if (h->in_flight && h->last_iq) {  // the batch in flight may still be synthesised again by gal_synth_finish
+        const char *a = (const char *)h->last_iq, *b = a + (size_t)h->range_ne * (size_t)h->P.N * 4;
+        const char *x = (const char *)iq_dev, *y = x + 4 * n_samples;
+        if (x < b && a < y) return fail(GAL_E_STATE, "gal_synth_iq_convert_noise: input of the batch in flight (call gal_synth_finish first)");
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = handle_stream(h);
+    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
+    if (!h->d_iq_sat) {
+        unsigned long long *c = nullptr;
+        HIP_TRY(hipMalloc((void **)&c, sizeof(unsigned long long)));
+        const hipError_t err = hipMemsetAsync(c, 0, sizeof(unsigned long long), st);
+        if (err != hipSuccess) {  // (never keep a counter that was not zeroed)
+            hipFree(c);
+            return fail(GAL_E_DEVICE, "gal_synth_iq_convert_noise: hipMemsetAsync of the counter failed: %s", hipGetErrorString(err));
+        }
+        h->d_iq_sat = c;
+    }
+    HIP_TRY(galk_launch_iq_noise(format, iq_dev, 2 * (uint64_t)n_samples, first_sample, noise->seed, noise->stream, noise->gain_q16,
+                                 noise->sigma_q4, shift, out_dev, h->d_iq_sat, st));
+    return GAL_OK;
+}
+
+int gal_synth_noise_from_cn0(double cn0_dbhz, double sample_rate, double gain, gal_iq_noise_t *out)
+{
+    if (!out) return fail(GAL_E_INVAL, "gal_synth_noise_from_cn0: null argument");
+    if (!std::isfinite(cn0_dbhz) || !std::isfinite(sample_rate) || !std::isfinite(gain) || sample_rate <= 0.0 || gain < 0.0 || gain > 16.0)
+        return fail(GAL_E_INVAL, "gal_synth_noise_from_cn0: C/N0 %g dB-Hz, sample rate %g Hz (> 0), gain %g (0..16)", cn0_dbhz, sample_rate, gain);
+    // sigma of one rail in int16 LSB for a composite E1B + E1C signal of amplitude 250 per component (include/galsynth.h)
+    const double sigma_q4 = 16.0 * 250.0 * gain * sqrt(sample_rate / pow(10.0, cn0_dbhz / 10.0));
+    if (!(sigma_q4 <= 1048576.0))
+        return fail(GAL_E_INVAL, "gal_synth_noise_from_cn0: sigma %g LSB at %g dB-Hz is beyond the 65536 LSB sigma_q4 holds", sigma_q4 / 16.0, cn0_dbhz);
+    memset(out, 0, sizeof(*out));
+    out->gain_q16 = (uint32_t)llround(gain * 65536.0);
+    out->sigma_q4 = (uint32_t)llround(sigma_q4);
     return GAL_OK;
 }
 

@@ -89,6 +89,16 @@ class _Stats(ctypes.Structure):
     ]
 
 
+class _Noise(ctypes.Structure):  # gal_iq_noise_t
+    _fields_ = [
+        ("seed", ctypes.c_uint64),
+        ("stream", ctypes.c_uint32),
+        ("gain_q16", ctypes.c_uint32),
+        ("sigma_q4", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
 class GalSynthError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("galsynth error %d: %s" % (code, msg))
@@ -117,11 +127,14 @@ EXPORTED_SYMBOLS = (
     "gal_synth_iq_bytes",
     "gal_synth_iq_convert",
     "gal_synth_iq_saturated",
+    "gal_synth_iq_convert_noise",
+    "gal_synth_noise_from_cn0",
     "gal_tables_e1b",
     "gal_tables_e1c",
     "gal_tables_cos512",
     "gal_tables_sin512",
     "gal_tables_cs25",
+    "gal_tables_gauss",
 )
 
 _libs = {}
@@ -172,7 +185,11 @@ def load_library(hooks=False):
     lib.gal_synth_iq_convert.restype = ctypes.c_int
     lib.gal_synth_iq_saturated.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), i32]
     lib.gal_synth_iq_saturated.restype = ctypes.c_int
-    for name in ("gal_tables_e1b", "gal_tables_e1c", "gal_tables_cos512", "gal_tables_sin512"):
+    lib.gal_synth_iq_convert_noise.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_uint64, ctypes.POINTER(_Noise), i32, i32, vp]
+    lib.gal_synth_iq_convert_noise.restype = ctypes.c_int
+    lib.gal_synth_noise_from_cn0.argtypes = [ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(_Noise)]
+    lib.gal_synth_noise_from_cn0.restype = ctypes.c_int
+    for name in ("gal_tables_e1b", "gal_tables_e1c", "gal_tables_cos512", "gal_tables_sin512", "gal_tables_gauss"):
         getattr(lib, name).restype = vp
     lib.gal_tables_cs25.restype = ctypes.c_uint32
     _libs[hooks] = lib
@@ -197,6 +214,28 @@ def iq_bytes(fmt, n_samples):
     return int(load_library().gal_synth_iq_bytes(iq_format_code(fmt), int(n_samples)))
 
 
+def noise_from_cn0(cn0_dbhz, sample_rate, gain=1.0):
+    """gal_synth_noise_from_cn0 (no GPU needed): the `noise` dict of SynthEngine.iq_convert for a C/N0 in dB-Hz of one satellite's
+    composite E1B + E1C signal -- seed 0, stream 0, gain_q16 = round(gain 65536), sigma_q4 = round(16 x 250 gain sqrt(rate / cn0))."""
+    lib = load_library()
+    n = _Noise()
+    rc = lib.gal_synth_noise_from_cn0(float(cn0_dbhz), float(sample_rate), float(gain), ctypes.byref(n))
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+    return {"seed": int(n.seed), "stream": int(n.stream), "gain_q16": int(n.gain_q16), "sigma_q4": int(n.sigma_q4)}
+
+
+def _noise_struct(noise):
+    """dict with the keys seed, stream, gain_q16, sigma_q4 (seed and stream default to 0), or a tuple in that order."""
+    if isinstance(noise, dict):
+        unknown = set(noise) - {"seed", "stream", "gain_q16", "sigma_q4"}
+        if unknown:
+            raise ValueError("noise: unknown keys %s" % sorted(unknown))
+        noise = (noise.get("seed", 0), noise.get("stream", 0), noise["gain_q16"], noise["sigma_q4"])
+    seed, stream, gain_q16, sigma_q4 = (int(v) for v in noise)
+    return _Noise(seed, stream, gain_q16, sigma_q4, 0)
+
+
 def tables():
     """The signal tables exactly as the engine uses them (numpy copies)."""
     lib = load_library()
@@ -211,6 +250,7 @@ def tables():
         "cos512": arr(lib.gal_tables_cos512(), ctypes.c_int16, 512, (512,)),
         "sin512": arr(lib.gal_tables_sin512(), ctypes.c_int16, 512, (512,)),
         "cs25": int(lib.gal_tables_cs25()),
+        "gauss": arr(lib.gal_tables_gauss(), ctypes.c_int32, 32 * 32 * 2, (32, 32, 2)),
     }
 
 
@@ -332,16 +372,25 @@ class SynthEngine:
         self.n_epochs = p.shape[0]
         return iq, st, {k: getattr(stats, k) for k, _ in _Stats._fields_}
 
-    def iq_convert(self, iq_ptr, n_samples, fmt, shift=None, out_ptr=None):
+    def iq_convert(self, iq_ptr, n_samples, fmt, shift=None, out_ptr=None, noise=None, first_sample=0):
         """Enqueue on the handle's stream: n_samples complex int16 samples at device address iq_ptr (final output: behind finish())
         -> `fmt` ("ishort" | "ibyte" | "ibit") at device address out_ptr (iq_bytes(fmt, n_samples) bytes, not overlapping the input).
-        Both 16-byte aligned; shift 0..15 for "ibyte" (None: IQ_SHIFT_DEFAULT), 0 (or None) otherwise.  iq_saturated() is the fence."""
+        Both 16-byte aligned; shift 0..15 for "ibyte" (None: IQ_SHIFT_DEFAULT), 0 (or None) otherwise.  iq_saturated() is the fence.
+        noise: a dict (seed, stream, gain_q16, sigma_q4; noise_from_cn0 makes one) or a tuple in that order -- the seeded noise floor
+        of gal_synth_iq_convert_noise in front of the format; first_sample is then the index of the call's first complex sample in
+        the whole output stream, and "ishort" may run in place (out_ptr == iq_ptr)."""
         if out_ptr is None:
             raise ValueError("iq_convert: out_ptr is required")
         if shift is None:
             shift = IQ_SHIFT_DEFAULT if iq_format_code(fmt) == GAL_IQ_IBYTE else 0
-        self._check(self._lib.gal_synth_iq_convert(self._h, ctypes.c_void_p(int(iq_ptr)), int(n_samples), iq_format_code(fmt),
-                                                   int(shift), ctypes.c_void_p(int(out_ptr))))
+        if noise is None:
+            self._check(self._lib.gal_synth_iq_convert(self._h, ctypes.c_void_p(int(iq_ptr)), int(n_samples), iq_format_code(fmt),
+                                                       int(shift), ctypes.c_void_p(int(out_ptr))))
+            return
+        nz = _noise_struct(noise)
+        self._check(self._lib.gal_synth_iq_convert_noise(self._h, ctypes.c_void_p(int(iq_ptr)), int(n_samples), int(first_sample),
+                                                         ctypes.byref(nz), iq_format_code(fmt), int(shift),
+                                                         ctypes.c_void_p(int(out_ptr))))
 
     def iq_saturated(self, reset=False):
         """Waits for the conversions enqueued so far; int16 values saturated by "ibyte" conversions since create (or the last reset)."""

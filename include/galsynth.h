@@ -276,12 +276,57 @@ int gal_synth_iq_convert(gal_synth_t *h, const int16_t *iq_dev, size_t n_samples
  * reset != 0 sets the counter back to 0. */
 int gal_synth_iq_saturated(gal_synth_t *h, uint64_t *n_saturated, int32_t reset);
 
+/*
+ * Noise floor (not in the reference, which writes the bare sum of the satellite signals): seeded white Gaussian noise and a signal
+ * gain, mixed into the final int16 stream in front of the format conversion, in one pass on the device.  It is a FIXED INTEGER
+ * FUNCTION of (seed, stream, index of the value in the whole output stream, int16 input): the same bits on any machine, however the
+ * stream is cut into batches and calls (tests/noise_model.py states it in numpy).
+ *
+ * x[j] = the interleaved int16 stream of one call (I0, Q0, I1, Q1, ...), first_sample = the index, counted from the start of the
+ * whole output stream, of the call's first complex sample.
+ *   J   = 2 (first_sample + j / 2) + (j & 1), 64-bit: the global value index
+ *   u   = output word J & 3 of Philox4x32-10 (Salmon et al., Random123: multipliers 0xD2511F53, 0xCD9E8D57, key increments
+ *         0x9E3779B9, 0xBB67AE85, ten rounds) with B = J >> 2, counter = (B & 0xffffffff, B >> 32, stream, 0),
+ *         key = (seed & 0xffffffff, seed >> 32)
+ *   z   = Gaussian in Q12 (unit variance at 4096; tails to 6.3 sigma), an inverse CDF over octave segments, integers only:
+ *         neg = u >> 31; w = u & 0x7fffffff; o = leading zeros of w as a 31-bit number (0..30; 31 for w = 0);
+ *         wn = w << o (0 for w = 0); s = (wn >> 25) & 31; f = (wn >> 17) & 255; (a, b) = T[o][s];
+ *         mag = a - (((a - b) f + 128) >> 8); z = neg ? -mag : mag
+ *         T = gal_tables_gauss(): with q(v) = -Phi^-1(v / 2^32), T[o][s] = (round(4096 q(2^(30-o) (1 + s/32))),
+ *         round(4096 q(2^(30-o) (1 + (s+1)/32)))) for o <= 30 and T[31][.] = (t0, t0), t0 = round(4096 q(0.5)) = 25960
+ *   y[j] = clamp((int64(x[j]) G + int64(z) S + 32768) >> 16, -32768, 32767)   (arithmetic shift), G = gain_q16, S = sigma_q4
+ * y then takes the format definitions above unchanged (GAL_IQ_ISHORT: y; GAL_IQ_IBYTE: shift, round, clamp to +-127;
+ * GAL_IQ_IBIT: y > 0).  A value counts ONCE as saturated if either clamp changed it.  G = 65536, S = 0 gives y = x exactly.
+ */
+typedef struct gal_iq_noise {
+    uint64_t seed;      /* Philox key                                                                                    */
+    uint32_t stream;    /* Philox counter word 2: independent noise for the same seed (the CLI: the site index of --sites) */
+    uint32_t gain_q16;  /* G = round(signal gain x 2^16), 0 .. 2^20                                                        */
+    uint32_t sigma_q4;  /* S = round(noise sigma in int16 LSB x 2^4), 0 .. 2^20                                            */
+    uint32_t reserved;  /* 0                                                                                             */
+} gal_iq_noise_t;
+/* gal_synth_iq_convert with the noise floor in front of the format: the same rules (enqueued on the handle's stream, behind
+ * gal_synth_finish of the batch that wrote iq_dev, 16-byte alignment, overlap refused, gal_synth_iq_saturated as fence and counter),
+ * and: GAL_IQ_ISHORT may run exactly IN PLACE (out_dev == iq_dev; any other overlap is refused); noise == NULL behaves as
+ * gal_synth_iq_convert (first_sample is then not looked at); GAL_E_INVAL also for gain_q16 or sigma_q4 above 2^20, reserved != 0,
+ * first_sample >= 2^62.  Any first_sample gives the defined output; an even one (every batch of whole epochs) is the fast case. */
+int gal_synth_iq_convert_noise(gal_synth_t *h, const int16_t *iq_dev, size_t n_samples, uint64_t first_sample,
+                               const gal_iq_noise_t *noise, int32_t format, int32_t shift, void *out_dev);
+/* Noise parameters for a carrier-to-noise-density ratio; needs no GPU.  gain_q16 = round(gain 65536),
+ * sigma_q4 = round(16 x 250 gain sqrt(sample_rate / 10^(cn0_dbhz / 10))); seed, stream and reserved are set to 0.
+ * 250 is the carrier-table amplitude of ONE E1 component (gal_tables_cos512()[0]); a satellite's E1B and E1C components are
+ * orthogonal in I/Q, each of power 250^2 per rail, and the noise has sigma^2 per rail: cn0_dbhz is the C/N0 of the COMPOSITE
+ * E1B + E1C signal of one satellite.  E1B alone (what a data-channel tracker sees) is 3 dB lower.
+ * GAL_E_INVAL for a null `out`, a non-finite argument, sample_rate <= 0, gain outside [0, 16], or a sigma_q4 above 2^20. */
+int gal_synth_noise_from_cn0(double cn0_dbhz, double sample_rate, double gain, gal_iq_noise_t *out);
+
 /* Signal tables as the engine uses them (for tests and for the oracle to share DATA, not code). */
 const uint32_t *gal_tables_e1b(void);   /* [50][128] */
 const uint32_t *gal_tables_e1c(void);   /* [50][128] */
 const int16_t  *gal_tables_cos512(void);/* [512]     */
 const int16_t  *gal_tables_sin512(void);/* [512]     */
 uint32_t        gal_tables_cs25(void);
+const int32_t  *gal_tables_gauss(void); /* [32][32][2] = T of the noise floor (above); needs no GPU */
 
 #ifdef __cplusplus
 }
