@@ -21,6 +21,9 @@ from .synth import (  # noqa: F401
     IQ_FORMATS,
     GalSynthError,
     SynthEngine,
+    corr_cn0,
+    corr_from_epoch,
+    corr_out_bytes,
     device_count,
     iq_bytes,
     load_library,

@@ -14,6 +14,10 @@
 // --cn0 <dBHz> (not in the reference either): a seeded white Gaussian noise floor under the signals, in every format, mixed in on the
 // GPU in the same pass (gal_synth_iq_convert_noise); the file is a fixed function of the command line, whatever the batch length.
 //
+// --monitor <file> (not in the reference): the built-in receiver check -- every --monitor-every'th epoch (default 10) the first 25 code
+// periods of every active channel are despread, in the buffer as it is written (behind noise and format), with the planned replica
+// (gal_synth_correlate); one CSV line per (epoch, PRN) with the measured C/N0 and where the peak lies.  Read-only: the IQ is the same.
+//
 // Pipeline: a producer thread runs the host front-end (libgalscen: orbits, ranges, I/NAV pages) up to two batches
 // ahead -> the main thread plans and executes each batch on the GPU and, after gal_synth_finish(), enqueues the copy
 // into one of two pinned buffers on two copy streams -> the sink moves full buffers into the output with sequential
@@ -38,6 +42,7 @@
 
 #include <atomic>
 #include <cerrno>
+#include <cmath>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -92,6 +97,10 @@ void usage(const char *prog)
            "  --noise-stream <n> with --cn0: independent noise under the same seed, 0 .. 2^32 - 1 (default 0; --sites: the site's index)\n"
            "  --signal-gain <g> with --cn0: gain on the signals, 0 < g <= 16 (default: the largest power of two <= 1 that keeps\n"
            "                   5 sigma of noise + the largest signal sum inside int16)\n"
+           "  --monitor <file> Despread the output with the planned replicas and write one CSV line per monitored epoch and PRN:\n"
+           "                   time, PRN, planned Doppler, measured C/N0 (composite E1B + E1C), peak ratio, strongest of the delays\n"
+           "                   -1 / 0 / +1 half chip and of the Doppler offsets -1 / 0 / +1 bin of 250 Hz; a summary per PRN on stderr\n"
+           "  --monitor-every <n> with --monitor: every n-th epoch of 0.1 s (default 10)\n"
            "  --writers <n>    Threads that move finished batches into a regular output file (default 0: sequential write(); > 0: mapped file, n copy threads)\n"
            "  -v               Verbose\n"
            "  -U/-b/-a/-G/-p/-n/-g/-i     accepted for compatibility (file sink only)\n",
@@ -274,7 +283,7 @@ struct Site {
 };
 
 int run_sites(const char *self, const std::vector<std::string> &base_args, const char *sites_file, const char *out_stem,
-              int n_gpus, int per_gpu, int udp_base, const char *fmt_name, double bytes_per_sample, bool noise_on)
+              int n_gpus, int per_gpu, int udp_base, const char *fmt_name, double bytes_per_sample, bool noise_on, const char *monitor_file)
 {
     std::vector<Site> sites;
     FILE *fp = fopen(sites_file, "r");
@@ -347,6 +356,10 @@ int run_sites(const char *self, const std::vector<std::string> &base_args, const
                 args.push_back("--noise-stream");
                 args.push_back(std::to_string(next));
             }
+            if (monitor_file) {  // site i: <file>.site<i>
+                args.push_back("--monitor");
+                args.push_back(std::string(monitor_file) + ".site" + std::to_string(next));
+            }
             const pid_t pid = fork();
             if (pid < 0) {
                 perror("fork");
@@ -402,6 +415,71 @@ int run_sites(const char *self, const std::vector<std::string> &base_args, const
     return failed ? 1 : 0;
 }
 
+// ---- --monitor ----------------------------------------------------------------------------------------------------
+constexpr int kMonPeriods = 25;     // code periods looked at per monitored epoch (4 ms each: the epoch's first 0.1 s)
+constexpr int kMonFarDelay = 2046;  // half chips: the noise tap, a quarter of a code period from the peak
+constexpr double kMonBinHz = 250.0; // 1 / (4 ms)
+
+struct MonEntry {  // one (epoch, channel): two requests -- delays -1, 0, +1 and the far delay, three Doppler bins each
+    double t, f_carr;
+    int prn;
+    size_t off;  // of its sums in the batch's buffer, in int64
+};
+struct MonBatch {
+    std::vector<MonEntry> entries;
+    long long *dev = nullptr, *host = nullptr;  // sums: per entry [25][3][3][4] then [25][3][1][4]
+    bool pending = false;
+};
+constexpr size_t kMonNear = (size_t)kMonPeriods * 3 * 3 * 4, kMonFar = (size_t)kMonPeriods * 3 * 1 * 4;  // int64 per request
+struct MonSummary {
+    int n = 0, off_peak = 0, no_peak = 0;
+    double sum = 0.0, lo = 1e300, hi = -1e300;
+};
+
+// the lines of a batch whose sums have arrived (the stream has been waited for)
+void monitor_flush(MonBatch &mb, FILE *fp, double sample_rate, const gal_corr_req_t &shape, MonSummary (&sum)[GAL_NUM_PRN + 1])
+{
+    for (const MonEntry &e : mb.entries) {
+        // one [25][3][4][4] array: delays -1, 0, +1 and the far one
+        std::vector<int64_t> all((size_t)kMonPeriods * 3 * 4 * 4);
+        const long long *near = mb.host + e.off, *far = near + kMonNear;
+        for (int m = 0; m < kMonPeriods; ++m)
+            for (int d = 0; d < 3; ++d)
+                for (int r = 0; r < 4; ++r) {
+                    for (int k = 0; k < 3; ++k) all[(((size_t)m * 3 + d) * 4 + k) * 4 + r] = near[(((size_t)m * 3 + d) * 3 + k) * 4 + r];
+                    all[(((size_t)m * 3 + d) * 4 + 3) * 4 + r] = far[((size_t)m * 3 + d) * 4 + r];
+                }
+        gal_corr_req_t q = shape;
+        q.n_delay = 4;
+        double cn0 = 0.0, ratio = 0.0, best = -1.0;
+        const bool peak = gal_corr_cn0(all.data(), &q, 1, 3, 1, sample_rate, &cn0, &ratio) == GAL_OK;
+        int bk = 0, bd = 0;
+        for (int d = 0; d < 3; ++d)
+            for (int k = 0; k < 3; ++k) {
+                double p = 0.0;
+                for (int m = 1; m < kMonPeriods - 1; ++m)
+                    for (int r = 0; r < 4; ++r) {
+                        const double v = (double)all[(((size_t)m * 3 + d) * 4 + k) * 4 + r];
+                        p += v * v;
+                    }
+                if (p > best) best = p, bk = k - 1, bd = d - 1;
+            }
+        if (peak) fprintf(fp, "%.1f,%d,%.3f,%.2f,%.3f,%d,%d\n", e.t, e.prn, e.f_carr, cn0, ratio, bk, bd);
+        else fprintf(fp, "%.1f,%d,%.3f,nan,%.3f,%d,%d\n", e.t, e.prn, e.f_carr, ratio, bk, bd);
+        MonSummary &s = sum[e.prn];
+        ++s.n;
+        if (bk || bd) ++s.off_peak;
+        if (!peak) ++s.no_peak;
+        else {
+            s.sum += cn0;
+            s.lo = cn0 < s.lo ? cn0 : s.lo;
+            s.hi = cn0 > s.hi ? cn0 : s.hi;
+        }
+    }
+    mb.entries.clear();
+    mb.pending = false;
+}
+
 }  // namespace
 
 // GAL_CLI_TIMING=1: where the start-up goes (stage times on stderr)
@@ -436,12 +514,13 @@ int main(int argc, char *argv[])
     bool verbose = false, have_batch = false, udp_given = false, realtime = false, cboc = false, exact_replay = false, shift_toe = false, ref_T = false;
     int batch_epochs = 128, n_writers = -1, sites_gpus = 0, sites_per_gpu = 1;
     const char *iq_format_arg = "ishort", *iq_shift_arg = nullptr;
+    const char *monitor_arg = nullptr, *monitor_every_arg = nullptr;
     const char *cn0_arg = nullptr, *noise_seed_arg = nullptr, *noise_stream_arg = nullptr, *signal_gain_arg = nullptr;
     sc.udp_port = GAL_SCEN_UDP_PORT;  // the reference always listens for position updates (src/galileo-sdr.cpp:185)
     sc.udp_loopback = 1;              // ... on every interface; the default listener here takes local datagrams only
 
     enum { OPT_STRICT = 1000, OPT_SITES, OPT_WRITERS, OPT_GPUS, OPT_PER_GPU, OPT_EXACT, OPT_SHIFT_TOE, OPT_REF_T, OPT_IQ_FORMAT, OPT_IQ_SHIFT, OPT_CN0, OPT_NOISE_SEED,
-           OPT_NOISE_STREAM, OPT_SIGNAL_GAIN };
+           OPT_NOISE_STREAM, OPT_SIGNAL_GAIN, OPT_MONITOR, OPT_MONITOR_EVERY };
     static const struct option long_opts[] = {{"strict", no_argument, nullptr, OPT_STRICT},
                                               {"exact-replay", no_argument, nullptr, OPT_EXACT},
                                               {"shift-toe", no_argument, nullptr, OPT_SHIFT_TOE},
@@ -456,15 +535,17 @@ int main(int argc, char *argv[])
                                               {"noise-seed", required_argument, nullptr, OPT_NOISE_SEED},
                                               {"noise-stream", required_argument, nullptr, OPT_NOISE_STREAM},
                                               {"signal-gain", required_argument, nullptr, OPT_SIGNAL_GAIN},
+                                              {"monitor", required_argument, nullptr, OPT_MONITOR},
+                                              {"monitor-every", required_argument, nullptr, OPT_MONITOR_EVERY},
                                               {nullptr, 0, nullptr, 0}};
     std::vector<std::string> child_args;  // --sites: everything but -l / -o / --sites / --gpus / --per-gpu / --noise-stream goes to the children
     int opt;
     while ((opt = getopt_long(argc, argv, "e:n:o:u:g:l:T:t:d:G:a:p:iI:U:b:vB:P:rC", long_opts, nullptr)) != -1) {
-        if (opt != 'l' && opt != 'o' && opt != 'P' && opt != OPT_SITES && opt != OPT_GPUS && opt != OPT_PER_GPU && opt != OPT_NOISE_STREAM && opt != '?' && opt != ':') {
+        if (opt != 'l' && opt != 'o' && opt != 'P' && opt != OPT_SITES && opt != OPT_GPUS && opt != OPT_PER_GPU && opt != OPT_NOISE_STREAM && opt != OPT_MONITOR && opt != '?' && opt != ':') {
             if (opt >= 1000) {
                 child_args.push_back(opt == OPT_STRICT ? "--strict" : opt == OPT_EXACT ? "--exact-replay" : opt == OPT_SHIFT_TOE ? "--shift-toe" : opt == OPT_REF_T ? "--ref-T"
                                      : opt == OPT_IQ_FORMAT ? "--iq-format" : opt == OPT_IQ_SHIFT ? "--iq-shift" : opt == OPT_CN0 ? "--cn0"
-                                     : opt == OPT_NOISE_SEED ? "--noise-seed" : opt == OPT_SIGNAL_GAIN ? "--signal-gain" : "--writers");
+                                     : opt == OPT_NOISE_SEED ? "--noise-seed" : opt == OPT_SIGNAL_GAIN ? "--signal-gain" : opt == OPT_MONITOR_EVERY ? "--monitor-every" : "--writers");
             } else {
                 char name[3] = {'-', (char)opt, 0};
                 child_args.push_back(name);
@@ -522,6 +603,8 @@ int main(int argc, char *argv[])
         case OPT_NOISE_SEED: noise_seed_arg = optarg; break;
         case OPT_NOISE_STREAM: noise_stream_arg = optarg; break;
         case OPT_SIGNAL_GAIN: signal_gain_arg = optarg; break;
+        case OPT_MONITOR: monitor_arg = optarg; break;
+        case OPT_MONITOR_EVERY: monitor_every_arg = optarg; break;
         case 'n': case 'g': case 'G': case 'a': case 'p': case 'i': case 'U': case 'b': break;
         case ':':
         case '?':
@@ -638,6 +721,40 @@ int main(int argc, char *argv[])
             fprintf(stderr, "\n");
         }
     }
+    // monitor: checked here too, before any device work.  Without --monitor nothing below differs from a build without it.
+    int monitor_every = 10;
+    FILE *monitor_fp = nullptr;
+    if (monitor_every_arg) {
+        char *end = nullptr;
+        const long v = strtol(monitor_every_arg, &end, 10);
+        if (!monitor_arg) {
+            fprintf(stderr, "ERROR: --monitor-every needs --monitor <file>.\n");
+            exit(1);
+        }
+        if (!*monitor_every_arg || *end || v < 1 || v > 1000000) {
+            fprintf(stderr, "ERROR: --monitor-every '%s' out of range (1..1000000 epochs).\n", monitor_every_arg);
+            exit(1);
+        }
+        monitor_every = (int)v;
+    }
+    if (monitor_arg) {
+        if (!*monitor_arg || strcmp(monitor_arg, "-") == 0) {
+            fprintf(stderr, "ERROR: --monitor needs a file name.\n");
+            exit(1);
+        }
+        if (cboc) {
+            fprintf(stderr, "ERROR: --monitor despreads with the BOC(1,1) replica; it does not go with -C.\n");
+            exit(1);
+        }
+        if (!sitesfile[0]) {  // (--sites: every child opens its own <file>.site<i>)
+            monitor_fp = fopen(monitor_arg, "w");
+            if (!monitor_fp) {
+                fprintf(stderr, "ERROR: cannot write the monitor file %s.\n", monitor_arg);
+                exit(1);
+            }
+            fprintf(monitor_fp, "time_s,prn,doppler_hz,cn0_dbhz,peak_ratio,best_delay_halfchips,best_doppler_bins\n");
+        }
+    }
     const double iq_bytes_per_sample = (double)gal_synth_iq_bytes(iq_format, 4) / 4.0;
     if (sitesfile[0]) {
         // several listeners cannot share a port: the sites run without the position listener unless -P names a base port, in
@@ -647,7 +764,7 @@ int main(int argc, char *argv[])
         if (n <= 0) snprintf(self, sizeof(self), "%s", argv[0]);
         else self[n] = 0;
         return run_sites(self, child_args, sitesfile, outfile, sites_gpus, sites_per_gpu, udp_given ? sc.udp_port : 0,
-                         kIqNames[iq_format], iq_bytes_per_sample, noise_on);
+                         kIqNames[iq_format], iq_bytes_per_sample, noise_on, monitor_arg);
     }
     if (outfile[0] == 0) {
         printf("[+] File sink not specified. Using galileosim.%s\n", kIqNames[iq_format]);
@@ -750,6 +867,25 @@ int main(int argc, char *argv[])
         hipEventCreate(&slot[i].copied[0]);
         hipEventCreate(&slot[i].copied[1]);
     }
+    // --monitor: per batch slot the sums of its monitored epochs, on the device and pinned on the host
+    MonBatch mon[2];
+    MonSummary mon_sum[GAL_NUM_PRN + 1];
+    gal_corr_req_t mon_shape;  // what every monitor request shares
+    memset(&mon_shape, 0, sizeof(mon_shape));
+    mon_shape.max_periods = kMonPeriods;
+    mon_shape.delay_step = 1;
+    mon_shape.dopp_step = (int32_t)llround(kMonBinHz / kSampleRate * 4294967296.0);
+    mon_shape.dopp0 = -mon_shape.dopp_step;
+    mon_shape.n_dopp = 3;
+    const size_t mon_epochs_max = (size_t)(batch_epochs + monitor_every - 1) / monitor_every + 1;
+    const size_t mon_bytes = mon_epochs_max * sc.n_slots * (kMonNear + kMonFar) * sizeof(long long);
+    if (monitor_fp)
+        for (int i = 0; i < 2; ++i)
+            if (hipMalloc((void **)&mon[i].dev, mon_bytes) != hipSuccess ||
+                hipHostMalloc((void **)&mon[i].host, mon_bytes, hipHostMallocDefault) != hipSuccess) {
+                fprintf(stderr, "ERROR: buffer allocation failed\n");
+                exit(1);
+            }
     stage("device + pinned buffers");
     // (a stream for the engine, made here: left to the engine it would be made inside the first gal_synth_plan -- 7-17 ms
     // of the run instead of the start-up)
@@ -868,6 +1004,42 @@ int main(int argc, char *argv[])
             cv.wait(lk, [&] { return !slot[cur].full; });
         }
         const double tb_slot = ms_since(tb0);
+        // --monitor: the requests of this batch's monitored epochs, made while the rows are still ours
+        std::vector<gal_corr_req_t> mon_reqs;
+        std::vector<int> mon_epoch;  // per pair of requests: the epoch's position in the batch
+        std::vector<int> mon_skip;   // ... and the samples skipped at its start (ibit: so that the address is 16-byte aligned)
+        if (monitor_fp) {
+            if (mon[cur].pending) {  // (cannot happen: flushed behind the finish of the batch after it)
+                fprintf(stderr, "\nERROR: monitor buffer still in use\n");
+                rc = 1;
+                break;
+            }
+            for (int e = 0; e < n; ++e) {
+                if ((emitted + e) % monitor_every) continue;
+                const size_t ob = gal_synth_iq_bytes(iq_format, (size_t)e * cfg.samples_per_epoch);
+                const int skip = iq_format == GAL_IQ_IBIT ? (int)((16 - ob % 16) % 16) * 4 : 0;
+                for (int s = 0; s < sc.n_slots; ++s) {
+                    const gal_chan_epoch_t &rec = rows_ptr[(size_t)e * sc.n_slots + s];
+                    if (rec.prn <= 0) continue;
+                    gal_corr_req_t q = mon_shape;
+                    if (gal_corr_from_epoch(&rec, kSampleRate, skip, &q) != GAL_OK) continue;  // (a record the monitor cannot follow)
+                    MonEntry me;
+                    me.t = (emitted + e) * 0.1;
+                    me.f_carr = rec.f_carr;
+                    me.prn = rec.prn;
+                    me.off = mon[cur].entries.size() * (kMonNear + kMonFar);
+                    mon[cur].entries.push_back(me);
+                    q.delay0 = -1;
+                    q.n_delay = 3;
+                    mon_reqs.push_back(q);
+                    q.delay0 = kMonFarDelay;
+                    q.n_delay = 1;
+                    mon_reqs.push_back(q);
+                    mon_epoch.push_back(e);
+                    mon_skip.push_back(skip);
+                }
+            }
+        }
         if (gal_synth_plan(eng, rows_ptr, n, have_state ? state.data() : nullptr) != GAL_OK ||
             gal_synth_execute(eng, d_iq[cur]) != GAL_OK) {
             fprintf(stderr, "\nERROR: %s\n", gal_synth_last_error());
@@ -888,6 +1060,8 @@ int main(int argc, char *argv[])
             rc = 1;
             break;
         }
+        // (the stream has drained up to this batch's synthesis: the sums of the batch before it are on the host)
+        if (monitor_fp && mon[cur ^ 1].pending) monitor_flush(mon[cur ^ 1], monitor_fp, kSampleRate, mon_shape, mon_sum);
         const double tb_synth = ms_since(tb0);
         if (batch_timing)
             fprintf(stderr, "[timing] batch at %7.2f ms: %3d epochs, waited %.2f ms for rows, %.2f for a free slot, plan + execute + finish %.2f\n",
@@ -912,6 +1086,26 @@ int main(int argc, char *argv[])
                 rc = 1;
                 break;
             }
+        }
+        if (monitor_fp && !mon_reqs.empty()) {
+            // behind the conversion, on the same stream, in the buffer the copies read: one call per monitored epoch
+            bool mon_ok = true;
+            size_t i = 0;
+            while (i < mon_epoch.size() && mon_ok) {
+                size_t j = i;
+                while (j < mon_epoch.size() && mon_epoch[j] == mon_epoch[i]) ++j;
+                const size_t ob = gal_synth_iq_bytes(iq_format, (size_t)mon_epoch[i] * cfg.samples_per_epoch) + (size_t)mon_skip[i] / 4;
+                mon_ok = gal_synth_correlate(eng, (const char *)d_out[cur] + ob, iq_format, (size_t)cfg.samples_per_epoch - mon_skip[i],
+                                             &mon_reqs[2 * i], (int32_t)(2 * (j - i)), (int64_t *)(mon[cur].dev + mon[cur].entries[i].off)) == GAL_OK;
+                i = j;
+            }
+            if (!mon_ok || hipMemcpyAsync(mon[cur].host, mon[cur].dev, mon[cur].entries.size() * (kMonNear + kMonFar) * sizeof(long long),
+                                          hipMemcpyDeviceToHost, stream) != hipSuccess) {
+                fprintf(stderr, "\nERROR: monitor: %s\n", mon_ok ? "copy of the sums failed" : gal_synth_last_error());
+                rc = 1;
+                break;
+            }
+            mon[cur].pending = true;
         }
         {
             // split at an epoch boundary: epoch_bytes is whole bytes in every format (see above)
@@ -965,6 +1159,29 @@ int main(int argc, char *argv[])
     const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
     fprintf(stderr, "\nDone!\nProcess time = %.2f [sec]  (%.1f Msamples/s, %.0fx real time)\n", el,
             emitted * 0.26 / el, emitted * 0.1 / el);
+    if (monitor_fp) {
+        if (hipStreamSynchronize(stream) != hipSuccess) rc = 1;
+        for (int i = 0; i < 2 && rc == 0; ++i)
+            if (mon[i].pending) monitor_flush(mon[i], monitor_fp, kSampleRate, mon_shape, mon_sum);
+        if (fclose(monitor_fp) != 0) {
+            fprintf(stderr, "ERROR: writing the monitor file %s failed\n", monitor_arg);
+            rc = 1;
+        }
+        fprintf(stderr, "Monitor (%s, every %d epochs, %d code periods each): C/N0 of the composite E1B + E1C signal\n", monitor_arg, monitor_every,
+                kMonPeriods);
+        for (int prn = 1; prn <= GAL_NUM_PRN; ++prn) {
+            const MonSummary &s = mon_sum[prn];
+            if (!s.n) continue;
+            if (s.n > s.no_peak)
+                fprintf(stderr, "  PRN %2d: %4d epochs, C/N0 mean %.2f dB-Hz (min %.2f, max %.2f), peak off the plan in %d, no peak in %d\n", prn, s.n,
+                        s.sum / (s.n - s.no_peak), s.lo, s.hi, s.off_peak, s.no_peak);
+            else fprintf(stderr, "  PRN %2d: %4d epochs, no peak in any\n", prn, s.n);
+        }
+        for (int i = 0; i < 2; ++i) {
+            hipFree(mon[i].dev);
+            hipHostFree(mon[i].host);
+        }
+    }
     if (gal_scen_eph_gaps(scen) > 0)
         fprintf(stderr, "NOTE: %d (satellite, refresh) pairs ran on a stale ephemeris record (see the warning above)\n",
                 gal_scen_eph_gaps(scen));

@@ -93,6 +93,9 @@ int galk_launch_synth(const DevPlan *P, const DevPlan *Pd, int nch, int accumula
 hipError_t galk_launch_iq(int format, const int16_t *in, uint64_t n_val, int shift, void *out, unsigned long long *sat, hipStream_t st);
 hipError_t galk_launch_iq_noise(int format, const int16_t *in, uint64_t n_val, uint64_t first_sample, uint64_t seed, uint32_t stream,
                                 uint32_t gain_q16, uint32_t sigma_q4, int shift, void *out, unsigned long long *sat, hipStream_t st);
+hipError_t galk_launch_corr(int format, const void *buf, uint64_t n_eff, uint64_t code_ph0, uint64_t code_dph, uint32_t carr_ph0,
+                            uint32_t carr_step0, uint32_t dopp_step, int delay0, int delay_step, int n_delay, int n_dopp, int max_periods,
+                            const uint32_t *lut_dev, const uint32_t *code_dev, long long *out, hipStream_t st);
 }
 
 namespace {
@@ -318,6 +321,7 @@ struct gal_synth {
     double prev_wait_us = 0.0;  // how long the last gal_synth_finish waited for its batch (paces the next one's naps)
     int g_holdoff = 0;  // batches for which k_synth_g is not used although it could be: its last batch listed too many groups
     unsigned long long *d_iq_sat = nullptr;  // gal_synth_iq_convert: saturated ibyte values (device; made at the first conversion)
+    uint32_t *d_corr_tab = nullptr;  // gal_synth_correlate: [512] carrier table + [50][512] replica bits (device; made at the first call)
 };
 
 // The stream the handle works on: the caller's (gal_synth_set_stream), or one of its own, made at first need.
@@ -545,6 +549,7 @@ int gal_synth_destroy(gal_synth_t *h)
     if (h->own_iq) hipFree(h->own_iq);
     if (h->own_pin) hipHostFree(h->own_pin);
     if (h->d_iq_sat) hipFree(h->d_iq_sat);
+    if (h->d_corr_tab) hipFree(h->d_corr_tab);
     if (h->d_lut) hipFree(h->d_lut);
     if (h->d_str) hipFree(h->d_str);
     if (h->h_up) hipHostFree(h->h_up);
@@ -1835,6 +1840,161 @@ int gal_synth_iq_saturated(gal_synth_t *h, uint64_t *n_saturated, int32_t reset)
     if (reset) HIP_TRY(hipMemsetAsync(h->d_iq_sat, 0, sizeof(v), st));
     HIP_TRY(hipStreamSynchronize(st));
     *n_saturated = (uint64_t)v;
+    return GAL_OK;
+}
+
+
+// ---- correlator bank and C/N0 monitor (iq_corr.hip) --------------------------------------------------------------------------
+static constexpr uint64_t kCorrL = (uint64_t)(2 * GAL_CODE_LEN) << 32;  // one code period: 8184 half chips x 2^32
+
+// nullptr: the request is fine; otherwise what is wrong with it
+static const char *corr_req_fault(const gal_corr_req_t *q)
+{
+    if (q->prn < 1 || q->prn > GAL_NUM_PRN) return "prn outside 1..50";
+    if (q->max_periods < 1 || q->max_periods > 1024) return "max_periods outside 1..1024";
+    if (q->code_ph0 >= kCorrL) return "code_ph0 outside [0, 8184 x 2^32)";
+    if (q->code_dph > ((uint64_t)1 << 32)) return "code_dph above 2^32 (one half chip per sample)";
+    if (q->delay_step < 1) return "delay_step below 1";
+    if (q->n_delay < 1 || q->n_delay > 2 * GAL_CODE_LEN) return "n_delay outside 1..8184";
+    if (q->n_dopp < 1 || q->n_dopp > 64) return "n_dopp outside 1..64";
+    return nullptr;
+}
+
+size_t gal_synth_corr_out_bytes(const gal_corr_req_t *req)
+{
+    if (!req || req->max_periods < 1 || req->max_periods > 1024 || req->n_delay < 1 || req->n_delay > 2 * GAL_CODE_LEN || req->n_dopp < 1 ||
+        req->n_dopp > 64)
+        return 0;
+    return (size_t)req->max_periods * (size_t)req->n_dopp * (size_t)req->n_delay * 4 * sizeof(int64_t);
+}
+
+int gal_synth_correlate(gal_synth_t *h, const void *buf_dev, int32_t format, size_t n_samples, const gal_corr_req_t *reqs, int32_t n_req,
+                        int64_t *out_dev)
+{
+    if (!h) return fail(GAL_E_INVAL, "null handle");
+    if (format != GAL_IQ_ISHORT && format != GAL_IQ_IBYTE && format != GAL_IQ_IBIT)
+        return fail(GAL_E_INVAL, "gal_synth_correlate: unknown format %d (GAL_IQ_ISHORT 0, GAL_IQ_IBYTE 1, GAL_IQ_IBIT 2)", format);
+    if (!buf_dev || !out_dev || !reqs || ((uintptr_t)buf_dev & 15) || ((uintptr_t)out_dev & 15))
+        return fail(GAL_E_INVAL, "gal_synth_correlate: pointers must be non-null, the device pointers 16-byte aligned");
+    if (n_req < 1 || n_req > GAL_CORR_MAX_REQ) return fail(GAL_E_INVAL, "gal_synth_correlate: %d requests (1..%d)", n_req, GAL_CORR_MAX_REQ);
+    if (n_samples == 0 || n_samples > ((size_t)1 << 32)) return fail(GAL_E_INVAL, "gal_synth_correlate: n_samples %zu (1..2^32)", n_samples);
+    size_t total = 0;
+    for (int r = 0; r < n_req; ++r) {
+        const char *what = corr_req_fault(&reqs[r]);
+        if (what) return fail(GAL_E_INVAL, "gal_synth_correlate: request %d: %s", r, what);
+        // P(n) = code_ph0 + n code_dph must stay below 2^64 for every n < n_samples
+        if (reqs[r].code_dph && (uint64_t)(n_samples - 1) > (UINT64_MAX - reqs[r].code_ph0) / reqs[r].code_dph)
+            return fail(GAL_E_INVAL, "gal_synth_correlate: request %d: the code phase overflows 64 bits within %zu samples", r, n_samples);
+        total += gal_synth_corr_out_bytes(&reqs[r]);
+        if (total > GAL_CORR_MAX_OUT_BYTES)
+            return fail(GAL_E_INVAL, "gal_synth_correlate: the requests take more than %zu bytes of output", (size_t)GAL_CORR_MAX_OUT_BYTES);
+    }
+    {
+        const char *x = (const char *)buf_dev, *y = x + gal_synth_iq_bytes(format, n_samples);
+        const char *o = (const char *)out_dev, *e = o + total;
+        if (x < e && o < y) return fail(GAL_E_INVAL, "gal_synth_correlate: buffer and output overlap");
+        if (h->in_flight && h->last_iq) {  // the batch in flight may still be synthesised again by gal_synth_finish
+            const char *a = (const char *)h->last_iq, *b = a + (size_t)h->range_ne * (size_t)h->P.N * 4;
+            if ((x < b && a < y) || (o < b && a < e))
+                return fail(GAL_E_STATE, "gal_synth_correlate: buffer of the batch in flight (call gal_synth_finish first)");
+        }
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = handle_stream(h);
+    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
+    if (!h->d_corr_tab) {
+        // [512] cos | sin << 16, then per PRN 8184 half chips x 2 bits: bit 2 (h & 15) of word h >> 4 = (b[h] < 0), the next one (c[h] < 0);
+        // b[h] = (E1B chip: set bit -1) x (sboc: even half chip -1), as the synthesis kernels take them out of the same tables
+        init_tables();
+        std::vector<uint32_t> tab(512 + 50 * 512, 0u);
+        for (int k = 0; k < 512; ++k) tab[k] = (uint32_t)(uint16_t)g_cos[k] | ((uint32_t)(uint16_t)g_sin[k] << 16);
+        for (int prn = 0; prn < 50; ++prn)
+            for (int hc = 0; hc < 2 * GAL_CODE_LEN; ++hc) {
+                const int chip = hc >> 1;
+                const uint32_t b = (kE1B[prn][chip >> 5] >> (chip & 31)) & 1u, c = (kE1C[prn][chip >> 5] >> (chip & 31)) & 1u;
+                const uint32_t even = (uint32_t)(~hc & 1);
+                tab[512 + prn * 512 + (hc >> 4)] |= ((b ^ even) | ((c ^ even) << 1)) << (2 * (hc & 15));
+            }
+        uint32_t *d = nullptr;
+        HIP_TRY(hipMalloc((void **)&d, tab.size() * sizeof(uint32_t)));
+        const hipError_t err = hipMemcpy(d, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (err != hipSuccess) {
+            hipFree(d);
+            return fail(GAL_E_DEVICE, "gal_synth_correlate: table upload failed: %s", hipGetErrorString(err));
+        }
+        h->d_corr_tab = d;
+    }
+    HIP_TRY(hipMemsetAsync(out_dev, 0, total, st));
+    size_t off = 0;
+    for (int r = 0; r < n_req; ++r) {  // the request travels as kernel arguments: copied when this returns
+        const gal_corr_req_t &q = reqs[r];
+        // the first sample of period max_periods: nothing from there on is wanted
+        uint64_t n_eff = n_samples;
+        if (q.code_dph) {
+            const uint64_t span = (uint64_t)q.max_periods * kCorrL - q.code_ph0;  // > 0
+            const uint64_t first = (span + q.code_dph - 1) / q.code_dph;
+            if (first < n_eff) n_eff = first;
+        }
+        HIP_TRY(galk_launch_corr(format, buf_dev, n_eff, q.code_ph0, q.code_dph, q.carr_ph0, (uint32_t)q.carr_dph + (uint32_t)q.dopp0,
+                                 (uint32_t)q.dopp_step, q.delay0, q.delay_step, q.n_delay, q.n_dopp, q.max_periods, h->d_corr_tab,
+                                 h->d_corr_tab + 512 + (size_t)(q.prn - 1) * 512, (long long *)((char *)out_dev + off), st));
+        off += gal_synth_corr_out_bytes(&q);
+    }
+    return GAL_OK;
+}
+
+int gal_corr_from_epoch(const gal_chan_epoch_t *rec, double sample_rate, int64_t sample_offset, gal_corr_req_t *out)
+{
+    if (!rec || !out) return fail(GAL_E_INVAL, "gal_corr_from_epoch: null argument");
+    if (rec->prn < 1 || rec->prn > GAL_NUM_PRN) return fail(GAL_E_INVAL, "gal_corr_from_epoch: prn %d (1..50)", rec->prn);
+    if (sample_offset < 0 || sample_offset > ((int64_t)1 << 32)) return fail(GAL_E_INVAL, "gal_corr_from_epoch: sample_offset outside 0..2^32");
+    if (!std::isfinite(sample_rate) || sample_rate <= 0.0 || !std::isfinite(rec->f_code) || !std::isfinite(rec->f_carr) ||
+        !std::isfinite(rec->code_phase0) || !std::isfinite(rec->carr_phase0))
+        return fail(GAL_E_INVAL, "gal_corr_from_epoch: a rate or phase is not finite, or sample_rate <= 0");
+    const double two32 = 4294967296.0;
+    const double dph = 2.0 * rec->f_code / sample_rate * two32, cdph = rec->f_carr / sample_rate * two32;
+    if (!(dph >= 0.0 && dph <= two32)) return fail(GAL_E_INVAL, "gal_corr_from_epoch: f_code %g outside [0, sample_rate / 2]", rec->f_code);
+    if (!(std::fabs(cdph) < 2147483647.5)) return fail(GAL_E_INVAL, "gal_corr_from_epoch: |f_carr| %g is not below sample_rate / 2", rec->f_carr);
+    if (!(rec->code_phase0 >= 0.0 && rec->code_phase0 < 3.0 * GAL_CODE_LEN))
+        return fail(GAL_E_INVAL, "gal_corr_from_epoch: code_phase0 %g outside [0, 3 x 4092)", rec->code_phase0);
+    out->prn = rec->prn;
+    out->code_dph = (uint64_t)llround(dph);
+    const unsigned __int128 p = (unsigned __int128)(uint64_t)llround(2.0 * rec->code_phase0 * two32) +
+                                (unsigned __int128)(uint64_t)sample_offset * out->code_dph;
+    out->code_ph0 = (uint64_t)(p % kCorrL);
+    out->carr_dph = (int32_t)llround(cdph);
+    out->carr_ph0 = 0;
+    if (rec->flags & GAL_CH_RESTART) {
+        const double fr = rec->carr_phase0 - std::floor(rec->carr_phase0);
+        out->carr_ph0 = (uint32_t)((uint64_t)llround(fr * two32) + (uint64_t)sample_offset * (uint64_t)(int64_t)out->carr_dph);
+    }
+    return GAL_OK;
+}
+
+int gal_corr_cn0(const int64_t *out_host, const gal_corr_req_t *req, int32_t k_prompt, int32_t k_noise, int32_t d, double sample_rate,
+                 double *cn0_dbhz, double *peak_ratio)
+{
+    if (!out_host || !req || !cn0_dbhz || !peak_ratio) return fail(GAL_E_INVAL, "gal_corr_cn0: null argument");
+    if (gal_synth_corr_out_bytes(req) == 0 || req->max_periods < 3 || req->code_dph == 0 || k_prompt < 0 || k_prompt >= req->n_delay ||
+        k_noise < 0 || k_noise >= req->n_delay || d < 0 || d >= req->n_dopp || !std::isfinite(sample_rate) || sample_rate <= 0.0)
+        return fail(GAL_E_INVAL, "gal_corr_cn0: a grid outside the caps, fewer than 3 periods, code_dph 0, an index outside the grid or a bad sample rate");
+    double pp = 0.0, pn = 0.0;
+    for (int m = 1; m < req->max_periods - 1; ++m) {
+        const int64_t *a = out_host + (((size_t)m * req->n_dopp + d) * req->n_delay + k_prompt) * 4;
+        const int64_t *b = out_host + (((size_t)m * req->n_dopp + d) * req->n_delay + k_noise) * 4;
+        for (int r = 0; r < 4; ++r) {
+            pp += (double)a[r] * (double)a[r];
+            pn += (double)b[r] * (double)b[r];
+        }
+    }
+    const int M = req->max_periods - 2;
+    pp /= M;
+    pn /= M;
+    *cn0_dbhz = 0.0;
+    *peak_ratio = pn > 0.0 ? pp / pn : 0.0;
+    if (!(pp > pn) || !(pn > 0.0)) return fail(GAL_E_INVAL, "gal_corr_cn0: no peak (Pp %g <= Pn %g)", pp, pn);
+    const double T = (double)kCorrL / (double)req->code_dph / sample_rate;
+    *cn0_dbhz = 10.0 * log10((pp - pn) / (pn * T / 2.0));
     return GAL_OK;
 }
 

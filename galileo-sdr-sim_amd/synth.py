@@ -99,6 +99,28 @@ class _Noise(ctypes.Structure):  # gal_iq_noise_t
     ]
 
 
+class _CorrReq(ctypes.Structure):  # gal_corr_req_t (56 bytes)
+    _fields_ = [
+        ("prn", ctypes.c_int32),
+        ("max_periods", ctypes.c_int32),
+        ("code_ph0", ctypes.c_uint64),
+        ("code_dph", ctypes.c_uint64),
+        ("carr_ph0", ctypes.c_uint32),
+        ("carr_dph", ctypes.c_int32),
+        ("delay0", ctypes.c_int32),
+        ("delay_step", ctypes.c_int32),
+        ("n_delay", ctypes.c_int32),
+        ("dopp0", ctypes.c_int32),
+        ("dopp_step", ctypes.c_int32),
+        ("n_dopp", ctypes.c_int32),
+    ]
+
+
+assert ctypes.sizeof(_CorrReq) == 56
+CORR_REQ_FIELDS = tuple(name for name, _ in _CorrReq._fields_)
+GAL_CORR_MAX_REQ = 64
+
+
 class GalSynthError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("galsynth error %d: %s" % (code, msg))
@@ -129,6 +151,8 @@ EXPORTED_SYMBOLS = (
     "gal_synth_iq_saturated",
     "gal_synth_iq_convert_noise",
     "gal_synth_noise_from_cn0",
+    "gal_synth_corr_out_bytes",
+    "gal_synth_correlate",
     "gal_tables_e1b",
     "gal_tables_e1c",
     "gal_tables_cos512",
@@ -189,6 +213,15 @@ def load_library(hooks=False):
     lib.gal_synth_iq_convert_noise.restype = ctypes.c_int
     lib.gal_synth_noise_from_cn0.argtypes = [ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(_Noise)]
     lib.gal_synth_noise_from_cn0.restype = ctypes.c_int
+    lib.gal_synth_corr_out_bytes.argtypes = [ctypes.POINTER(_CorrReq)]
+    lib.gal_synth_corr_out_bytes.restype = ctypes.c_size_t
+    lib.gal_synth_correlate.argtypes = [vp, vp, i32, ctypes.c_size_t, ctypes.POINTER(_CorrReq), i32, vp]
+    lib.gal_synth_correlate.restype = ctypes.c_int
+    lib.gal_corr_from_epoch.argtypes = [vp, ctypes.c_double, ctypes.c_int64, ctypes.POINTER(_CorrReq)]
+    lib.gal_corr_from_epoch.restype = ctypes.c_int
+    lib.gal_corr_cn0.argtypes = [vp, ctypes.POINTER(_CorrReq), i32, i32, i32, ctypes.c_double, ctypes.POINTER(ctypes.c_double),
+                                 ctypes.POINTER(ctypes.c_double)]
+    lib.gal_corr_cn0.restype = ctypes.c_int
     for name in ("gal_tables_e1b", "gal_tables_e1c", "gal_tables_cos512", "gal_tables_sin512", "gal_tables_gauss"):
         getattr(lib, name).restype = vp
     lib.gal_tables_cs25.restype = ctypes.c_uint32
@@ -234,6 +267,53 @@ def _noise_struct(noise):
         noise = (noise.get("seed", 0), noise.get("stream", 0), noise["gain_q16"], noise["sigma_q4"])
     seed, stream, gain_q16, sigma_q4 = (int(v) for v in noise)
     return _Noise(seed, stream, gain_q16, sigma_q4, 0)
+
+
+def _corr_struct(req):
+    """dict with the fields of gal_corr_req_t (grids default to one prompt cell, max_periods to 1), or a _CorrReq."""
+    if isinstance(req, _CorrReq):
+        return req
+    unknown = set(req) - set(CORR_REQ_FIELDS)
+    if unknown:
+        raise ValueError("correlator request: unknown keys %s" % sorted(unknown))
+    d = {"max_periods": 1, "carr_ph0": 0, "carr_dph": 0, "delay0": 0, "delay_step": 1, "n_delay": 1, "dopp0": 0, "dopp_step": 0, "n_dopp": 1}
+    d.update(req)
+    return _CorrReq(**{k: int(d[k]) for k in CORR_REQ_FIELDS})
+
+
+def corr_out_bytes(req):
+    """gal_synth_corr_out_bytes (no GPU needed): bytes of sums one request takes, 0 for a grid outside the caps."""
+    return int(load_library().gal_synth_corr_out_bytes(ctypes.byref(_corr_struct(req))))
+
+
+def corr_from_epoch(rec, sample_rate, sample_offset=0, **grid):
+    """gal_corr_from_epoch (no GPU needed): the replica of one planned record (a CHAN_EPOCH_DTYPE element) as a request dict --
+    prn, code_ph0, code_dph, carr_ph0, carr_dph -- with `grid` (delay0, n_delay, dopp_step, max_periods, ...) merged in."""
+    lib = load_library()
+    r = np.ascontiguousarray(rec, dtype=CHAN_EPOCH_DTYPE).reshape(1)
+    q = _CorrReq()
+    rc = lib.gal_corr_from_epoch(r.ctypes.data, float(sample_rate), int(sample_offset), ctypes.byref(q))
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+    out = {k: int(getattr(q, k)) for k in ("prn", "code_ph0", "code_dph", "carr_ph0", "carr_dph")}
+    out.update({k: int(v) for k, v in grid.items()})
+    return out
+
+
+def corr_cn0(sums, req, k_prompt, k_noise, d, sample_rate):
+    """gal_corr_cn0 (no GPU needed): (C/N0 in dB-Hz of the composite E1B + E1C signal, Pp / Pn) from the [m, d, k, 4] sums of one
+    request, over the whole periods m = 1 .. max_periods - 2.  Raises GalSynthError(GAL_E_INVAL) where there is no peak."""
+    lib = load_library()
+    q = _corr_struct(req)
+    a = np.ascontiguousarray(sums, dtype=np.int64)
+    if a.size * 8 != int(lib.gal_synth_corr_out_bytes(ctypes.byref(q))):
+        raise ValueError("corr_cn0: sums of %d values do not belong to this request" % a.size)
+    cn0, ratio = ctypes.c_double(0.0), ctypes.c_double(0.0)
+    rc = lib.gal_corr_cn0(a.ctypes.data, ctypes.byref(q), int(k_prompt), int(k_noise), int(d), float(sample_rate), ctypes.byref(cn0),
+                          ctypes.byref(ratio))
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+    return float(cn0.value), float(ratio.value)
 
 
 def tables():
@@ -397,3 +477,31 @@ class SynthEngine:
         n = ctypes.c_uint64(0)
         self._check(self._lib.gal_synth_iq_saturated(self._h, ctypes.byref(n), 1 if reset else 0))
         return int(n.value)
+
+    def correlate(self, buf_ptr, fmt, n_samples, reqs, out_ptr=None):
+        """gal_synth_correlate: despread the n_samples complex samples in format `fmt` at device address buf_ptr (16-byte aligned, final
+        output) with each request (dicts as corr_from_epoch makes them, or one dict).  Returns the sums as int64 numpy arrays of shape
+        [max_periods, n_dopp, n_delay, 4] (Re S_B, Im S_B, Re S_C, Im S_C), one per request (a single array for a single dict); waits
+        for them.  out_ptr: a device address for the sums (16-byte aligned, the sum of corr_out_bytes) -- then nothing is copied or
+        waited for and None is returned; iq_saturated() is the fence."""
+        single = isinstance(reqs, (dict, _CorrReq))
+        qs = [_corr_struct(r) for r in ([reqs] if single else reqs)]
+        arr = (_CorrReq * max(1, len(qs)))(*qs)
+        sizes = [int(self._lib.gal_synth_corr_out_bytes(ctypes.byref(q))) for q in qs]
+        if out_ptr is not None:
+            self._check(self._lib.gal_synth_correlate(self._h, ctypes.c_void_p(int(buf_ptr)), iq_format_code(fmt), int(n_samples), arr,
+                                                      len(qs), ctypes.c_void_p(int(out_ptr))))
+            return None
+        import torch
+
+        out = torch.empty(max(2, sum(sizes) // 8), dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()  # (the block may come from torch's cache with work of torch's stream still behind it)
+        self._check(self._lib.gal_synth_correlate(self._h, ctypes.c_void_p(int(buf_ptr)), iq_format_code(fmt), int(n_samples), arr, len(qs),
+                                                  ctypes.c_void_p(out.data_ptr())))
+        self.iq_saturated()
+        host = out.cpu().numpy()
+        res, off = [], 0
+        for q, nb in zip(qs, sizes):
+            res.append(host[off:off + nb // 8].reshape(q.max_periods, q.n_dopp, q.n_delay, 4).copy())
+            off += nb // 8
+        return res[0] if single else res

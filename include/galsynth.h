@@ -320,6 +320,80 @@ int gal_synth_iq_convert_noise(gal_synth_t *h, const int16_t *iq_dev, size_t n_s
  * GAL_E_INVAL for a null `out`, a non-finite argument, sample_rate <= 0, gain outside [0, 16], or a sigma_q4 above 2^20. */
 int gal_synth_noise_from_cn0(double cn0_dbhz, double sample_rate, double gain, gal_iq_noise_t *out);
 
+/*
+ * Correlator bank and C/N0 monitor (not in the reference): despread a device buffer of output IQ with the engine's own replica of one
+ * satellite and get, per code period, delay and Doppler bin, the complex correlation sums of the E1B and the E1C component.  Read-only
+ * on the buffer, in any of the three formats.  Like the formats and the noise floor it is a FIXED INTEGER FUNCTION of its inputs: the
+ * same int64 sums on any machine (tests/corr_model.py states it in numpy).
+ *
+ * v[j] = the interleaved I/Q values of the buffer: GAL_IQ_ISHORT the int16, GAL_IQ_IBYTE the int8, GAL_IQ_IBIT +1 for a set bit and
+ * -1 for a clear one (MSB first, as the format defines).  Sample n is (I, Q) = (v[2n], v[2n+1]).  With L = 8184 * 2^32:
+ *   P(n)   = code_ph0 + n code_dph (64-bit, exact: the call refuses an n_samples for which it could overflow)
+ *   m      = P(n) div L, the code period of sample n;  h(n) = (P(n) mod L) >> 32, the prompt half chip
+ *   h_k(n) = (h(n) - (delay0 + k delay_step)) mod 8184 in [0, 8184) for delay index k (m is the prompt's, whatever k)
+ *   b[h], c[h]  the E1B / E1C primary code chip of `prn` (gal_tables_e1b / gal_tables_e1c: bit (h >> 1) & 31 of word h >> 6; a set
+ *          bit is -1, a clear one +1) times the BOC(1,1) sub-carrier in the sboc convention quoted at GAL_CFG_CBOC (+1 on an odd half
+ *          chip, -1 on an even one); no data symbol, no secondary code, no minus sign on C
+ *   phi_d(n) = (carr_ph0 + n (carr_dph + dopp0 + d dopp_step)) mod 2^32 for Doppler index d; i = phi_d(n) >> 23;
+ *          w = gal_tables_cos512()[i] + i gal_tables_sin512()[i]
+ *   S_B(m, d, k) = sum over the samples n of period m of (I + iQ)(n) conj(w) b[h_k(n)];  S_C the same with c
+ * out[((m n_dopp + d) n_delay + k) 4 + (0, 1, 2, 3)] = Re S_B, Im S_B, Re S_C, Im S_C for m < max_periods; samples of later periods are
+ * not looked at, periods the buffer does not reach stay 0.
+ */
+typedef struct gal_corr_req {
+    int32_t  prn;         /* 1..50                                                                                            */
+    int32_t  max_periods; /* 1..1024: code periods (4 ms at the nominal rate), counted from the one sample 0 lies in          */
+    uint64_t code_ph0;    /* replica code phase at sample 0: half chips x 2^32, in [0, L)                                     */
+    uint64_t code_dph;    /* half chips per sample x 2^32, <= 2^32 (one half chip per sample: the engine's f_code <= fs / 2)   */
+    uint32_t carr_ph0;    /* carrier phase at sample 0, 2^-32 cycles                                                         */
+    int32_t  carr_dph;    /* carrier phase step per sample, 2^-32 cycles (wraps modulo 2^32 with the Doppler grid added)      */
+    int32_t  delay0;      /* first delay, half chips (may be negative); a positive delay = the replica LATER than planned      */
+    int32_t  delay_step;  /* >= 1                                                                                             */
+    int32_t  n_delay;     /* 1..8184                                                                                          */
+    int32_t  dopp0;       /* first Doppler offset, units of carr_dph                                                          */
+    int32_t  dopp_step;
+    int32_t  n_dopp;      /* 1..64                                                                                            */
+} gal_corr_req_t;         /* 56 bytes */
+#define GAL_CORR_MAX_REQ 64
+#define GAL_CORR_MAX_OUT_BYTES ((size_t)1 << 30) /* of one call, all requests together */
+/* Bytes of `out` one request takes: max_periods n_dopp n_delay 4 int64; 0 for a null request or a grid outside the caps above.
+ * Needs no GPU. */
+size_t gal_synth_corr_out_bytes(const gal_corr_req_t *req);
+/* Enqueue on the handle's stream: correlate the n_samples complex samples at buf_dev (DEVICE memory in `format`, 16-byte aligned,
+ * gal_synth_iq_bytes(format, n_samples) bytes, only read) with every request; request r writes its sums at out_dev (DEVICE memory,
+ * 16-byte aligned) + the sum of gal_synth_corr_out_bytes of the requests in front of it.  out_dev is zeroed by the call.  `reqs` is
+ * copied before the call returns.  The rules of gal_synth_iq_convert hold: GAL_E_STATE for the int16 buffer of a batch in flight,
+ * gal_synth_iq_saturated is the fence behind which out_dev may be copied.  GAL_E_INVAL for a null handle or pointer, a misaligned
+ * pointer, an unknown format, n_req outside 1..GAL_CORR_MAX_REQ, a request outside the ranges stated at gal_corr_req_t, more than
+ * GAL_CORR_MAX_OUT_BYTES of output, n_samples = 0 or so large that P(n) could pass 2^64, out_dev overlapping buf_dev. */
+int gal_synth_correlate(gal_synth_t *h, const void *buf_dev, int32_t format, size_t n_samples, const gal_corr_req_t *reqs,
+                        int32_t n_req, int64_t *out_dev);
+/* The replica of a planned record, host only (no GPU): fills prn, code_ph0, code_dph, carr_ph0, carr_dph of *out and leaves the
+ * grids and max_periods as they are.  sample_offset >= 0 = the position of the buffer's sample 0 inside the record's epoch.  All
+ * rounding is to nearest (ties away from zero, llround):
+ *   code_dph = llround(2 f_code / sample_rate x 2^32)
+ *   code_ph0 = (llround(2 code_phase0 x 2^32) + sample_offset code_dph) mod L
+ *   carr_dph = llround(f_carr / sample_rate x 2^32)   (GAL_E_INVAL where it does not fit an int32: |f_carr| >= sample_rate / 2)
+ *   carr_ph0 = (llround(frac(carr_phase0) x 2^32) + sample_offset carr_dph) mod 2^32 with GAL_CH_RESTART, 0 otherwise (the phase a
+ *              continuing channel carries is the engine's state, not the record's; |S| does not depend on it)
+ * The engine advances its code phase by the double f_code / sample_rate per sample; the replica by code_dph 2^-32, which differs
+ * from twice that by at most 2^-33 half chips: over the 260 000 samples of an epoch the replica drifts by at most 260 000 x 2^-33
+ * = 3.1e-5 half chips (plus 2^-33 of code_ph0 and the rounding of the engine's own recurrence, ~1e-9 chips), i.e. the half chip
+ * index differs on about 3e-5 of the samples at worst.  GAL_E_INVAL also for a null pointer, prn outside 1..50, a negative offset,
+ * rates that are not finite or a code step above one half chip per sample. */
+int gal_corr_from_epoch(const gal_chan_epoch_t *rec, double sample_rate, int64_t sample_offset, gal_corr_req_t *out);
+/* C/N0 from the sums of ONE request copied to the host (`out_host`: gal_synth_corr_out_bytes(req) bytes), host only.  Over the WHOLE
+ * periods m = 1 .. max_periods - 2 (m = 0 and the last one are cut by the buffer's ends; the caller keeps max_periods within what
+ * the buffer holds; GAL_E_INVAL below 3 periods), at Doppler index d:
+ *   Pp = mean of |S_B|^2 + |S_C|^2 at delay index k_prompt,  Pn = the same at k_noise (a delay far from the peak)
+ *   T  = the mean period length in seconds = 8184 x 2^32 / (code_dph sample_rate)
+ *   *cn0_dbhz = 10 log10((Pp - Pn) / (Pn T / 2)),  *peak_ratio = Pp / Pn
+ * the C/N0 of the satellite's COMPOSITE E1B + E1C signal, the figure of gal_synth_noise_from_cn0.  Pp and Pn both sum TWO
+ * components, each of which carries half of C against the whole of N0: (Pp - Pn) / Pn = (C / 2) T / N0, hence the factor 2
+ * (DESIGN.md section 12 derives it from section 11's powers).  GAL_E_INVAL when Pp <= Pn, or for an index outside the request. */
+int gal_corr_cn0(const int64_t *out_host, const gal_corr_req_t *req, int32_t k_prompt, int32_t k_noise, int32_t d, double sample_rate,
+                 double *cn0_dbhz, double *peak_ratio);
+
 /* Signal tables as the engine uses them (for tests and for the oracle to share DATA, not code). */
 const uint32_t *gal_tables_e1b(void);   /* [50][128] */
 const uint32_t *gal_tables_e1c(void);   /* [50][128] */
