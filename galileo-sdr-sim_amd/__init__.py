@@ -25,6 +25,7 @@ from .synth import (  # noqa: F401
     corr_from_epoch,
     corr_out_bytes,
     device_count,
+    interf_make,
     iq_bytes,
     load_library,
     noise_from_cn0,

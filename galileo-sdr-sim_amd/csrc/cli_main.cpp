@@ -13,6 +13,8 @@
 // or 1-bit packed IQ, converted on the GPU behind each batch (gal_synth_iq_convert); half / a sixteenth of the bytes to move.
 // --cn0 <dBHz> (not in the reference either): a seeded white Gaussian noise floor under the signals, in every format, mixed in on the
 // GPU in the same pass (gal_synth_iq_convert_noise); the file is a fixed function of the command line, whatever the batch length.
+// --jam js_db,f_hz[,f_hi_hz,sweep_us[,period_us,on_us]] (not in the reference), up to four times: CW, chirp or pulsed interference at
+// a stated J/S, with or without --cn0, in that same pass (gal_synth_iq_convert_interf); again a fixed function of the command line.
 //
 // --monitor <file> (not in the reference): the built-in receiver check -- every --monitor-every'th epoch (default 10) the first 25 code
 // periods of every active channel are despread, in the buffer as it is written (behind noise and format), with the planned replica
@@ -95,8 +97,11 @@ void usage(const char *prog)
            "                   3 dB lower); every format; the same bytes for the same options on any machine (default: no noise)\n"
            "  --noise-seed <n> with --cn0: seed of the noise, 0 .. 2^64 - 1 (default 1)\n"
            "  --noise-stream <n> with --cn0: independent noise under the same seed, 0 .. 2^32 - 1 (default 0; --sites: the site's index)\n"
-           "  --signal-gain <g> with --cn0: gain on the signals, 0 < g <= 16 (default: the largest power of two <= 1 that keeps\n"
-           "                   5 sigma of noise + the largest signal sum inside int16)\n"
+           "  --signal-gain <g> with --cn0 or --jam: gain on the signals, 0 < g <= 16 (default: the largest power of two <= 1 that keeps\n"
+           "                   5 sigma of noise + the largest signal sum + the --jam amplitudes inside int16)\n"
+           "  --jam <spec>     Add an interference source, up to 4 times: js_db,f_hz[,f_hi_hz,sweep_us[,period_us,on_us]] -- J/S in dB against\n"
+           "                   one satellite's composite signal, a CW tone at f_hz from the centre, or a chirp from f_hz to f_hi_hz that\n"
+           "                   restarts every sweep_us microseconds, on for on_us of every period_us; with or without --cn0\n"
            "  --monitor <file> Despread the output with the planned replicas and write one CSV line per monitored epoch and PRN:\n"
            "                   time, PRN, planned Doppler, measured C/N0 (composite E1B + E1C), peak ratio, strongest of the delays\n"
            "                   -1 / 0 / +1 half chip and of the Doppler offsets -1 / 0 / +1 bin of 250 Hz; a summary per PRN on stderr\n"
@@ -276,6 +281,37 @@ private:
     size_t job_bytes_ = 0, job_next_ = 0;
     int job_left_ = 0;
 };
+
+// ---- --jam js_db,f_hz[,f_hi_hz,sweep_us[,period_us,on_us]] ---------------------------------------------------------------------
+struct JamSpec {
+    double js_db, f_lo, f_hi, sweep_s, period_s, on_s;
+};
+
+// two, four or six numbers with commas between them and nothing else
+bool parse_jam(const char *arg, JamSpec *j)
+{
+    double v[6] = {0, 0, 0, 0, 0, 0};
+    int n = 0;
+    const char *p = arg;
+    for (;;) {
+        char *end = nullptr;
+        if (n == 6 || !*p || *p == ',') return false;
+        v[n++] = strtod(p, &end);
+        if (end == p) return false;
+        if (!*end) break;
+        if (*end != ',') return false;
+        p = end + 1;
+    }
+    if (n != 2 && n != 4 && n != 6) return false;
+    if (n >= 4 && !(v[3] > 0.0)) return false;  // a chirp needs a sweep time
+    j->js_db = v[0];
+    j->f_lo = v[1];
+    j->f_hi = v[2];
+    j->sweep_s = v[3] * 1e-6;
+    j->period_s = v[4] * 1e-6;
+    j->on_s = v[5] * 1e-6;
+    return true;
+}
 
 // ---- --sites: one child process per receiver site ---------------------------------------------------------------
 struct Site {
@@ -516,11 +552,12 @@ int main(int argc, char *argv[])
     const char *iq_format_arg = "ishort", *iq_shift_arg = nullptr;
     const char *monitor_arg = nullptr, *monitor_every_arg = nullptr;
     const char *cn0_arg = nullptr, *noise_seed_arg = nullptr, *noise_stream_arg = nullptr, *signal_gain_arg = nullptr;
+    std::vector<const char *> jam_args;
     sc.udp_port = GAL_SCEN_UDP_PORT;  // the reference always listens for position updates (src/galileo-sdr.cpp:185)
     sc.udp_loopback = 1;              // ... on every interface; the default listener here takes local datagrams only
 
     enum { OPT_STRICT = 1000, OPT_SITES, OPT_WRITERS, OPT_GPUS, OPT_PER_GPU, OPT_EXACT, OPT_SHIFT_TOE, OPT_REF_T, OPT_IQ_FORMAT, OPT_IQ_SHIFT, OPT_CN0, OPT_NOISE_SEED,
-           OPT_NOISE_STREAM, OPT_SIGNAL_GAIN, OPT_MONITOR, OPT_MONITOR_EVERY };
+           OPT_NOISE_STREAM, OPT_SIGNAL_GAIN, OPT_MONITOR, OPT_MONITOR_EVERY, OPT_JAM };
     static const struct option long_opts[] = {{"strict", no_argument, nullptr, OPT_STRICT},
                                               {"exact-replay", no_argument, nullptr, OPT_EXACT},
                                               {"shift-toe", no_argument, nullptr, OPT_SHIFT_TOE},
@@ -537,6 +574,7 @@ int main(int argc, char *argv[])
                                               {"signal-gain", required_argument, nullptr, OPT_SIGNAL_GAIN},
                                               {"monitor", required_argument, nullptr, OPT_MONITOR},
                                               {"monitor-every", required_argument, nullptr, OPT_MONITOR_EVERY},
+                                              {"jam", required_argument, nullptr, OPT_JAM},
                                               {nullptr, 0, nullptr, 0}};
     std::vector<std::string> child_args;  // --sites: everything but -l / -o / --sites / --gpus / --per-gpu / --noise-stream goes to the children
     int opt;
@@ -545,7 +583,7 @@ int main(int argc, char *argv[])
             if (opt >= 1000) {
                 child_args.push_back(opt == OPT_STRICT ? "--strict" : opt == OPT_EXACT ? "--exact-replay" : opt == OPT_SHIFT_TOE ? "--shift-toe" : opt == OPT_REF_T ? "--ref-T"
                                      : opt == OPT_IQ_FORMAT ? "--iq-format" : opt == OPT_IQ_SHIFT ? "--iq-shift" : opt == OPT_CN0 ? "--cn0"
-                                     : opt == OPT_NOISE_SEED ? "--noise-seed" : opt == OPT_SIGNAL_GAIN ? "--signal-gain" : opt == OPT_MONITOR_EVERY ? "--monitor-every" : "--writers");
+                                     : opt == OPT_NOISE_SEED ? "--noise-seed" : opt == OPT_SIGNAL_GAIN ? "--signal-gain" : opt == OPT_MONITOR_EVERY ? "--monitor-every" : opt == OPT_JAM ? "--jam" : "--writers");
             } else {
                 char name[3] = {'-', (char)opt, 0};
                 child_args.push_back(name);
@@ -605,6 +643,7 @@ int main(int argc, char *argv[])
         case OPT_SIGNAL_GAIN: signal_gain_arg = optarg; break;
         case OPT_MONITOR: monitor_arg = optarg; break;
         case OPT_MONITOR_EVERY: monitor_every_arg = optarg; break;
+        case OPT_JAM: jam_args.push_back(optarg); break;
         case 'n': case 'g': case 'G': case 'a': case 'p': case 'i': case 'U': case 'b': break;
         case ':':
         case '?':
@@ -657,10 +696,41 @@ int main(int argc, char *argv[])
     bool noise_on = false;
     gal_iq_noise_t noise;
     memset(&noise, 0, sizeof(noise));
-    if (!cn0_arg && (noise_seed_arg || noise_stream_arg || signal_gain_arg)) {
+    if (!cn0_arg && (noise_seed_arg || noise_stream_arg || (signal_gain_arg && jam_args.empty()))) {
         fprintf(stderr, "ERROR: --noise-seed, --noise-stream and --signal-gain need --cn0 <dBHz>.\n");
         exit(1);
     }
+    // interference: the strings are checked here, the sources are made below, once the signal gain is known.  Without --jam nothing
+    // below differs from a build without it.
+    JamSpec jam[GAL_INTERF_MAX];
+    const int n_jam = (int)jam_args.size();
+    double jam_unit = 0.0;  // the sum of the amplitudes at signal gain 1, int16 LSB
+    if (n_jam > GAL_INTERF_MAX) {
+        fprintf(stderr, "ERROR: --jam may be given %d times at most.\n", GAL_INTERF_MAX);
+        exit(1);
+    }
+    for (int k = 0; k < n_jam; ++k) {
+        gal_iq_interf_t probe;
+        if (!parse_jam(jam_args[k], &jam[k])) {
+            fprintf(stderr, "ERROR: --jam '%s' is not js_db,f_hz[,f_hi_hz,sweep_us[,period_us,on_us]].\n", jam_args[k]);
+            exit(1);
+        }
+        if (gal_synth_interf_make(jam[k].js_db, 0.0, kSampleRate, jam[k].f_lo, jam[k].f_hi, jam[k].sweep_s, jam[k].period_s, jam[k].on_s,
+                                  &probe) != GAL_OK) {  // (gain 0: everything but the amplitude)
+            fprintf(stderr, "ERROR: --jam %s: %s\n", jam_args[k], gal_synth_last_error());
+            exit(1);
+        }
+        jam_unit += 250.0 * sqrt(2.0) * pow(10.0, jam[k].js_db / 20.0);
+    }
+    double gain = 1.0;
+    const auto given_gain = [&]() {
+        char *end = nullptr;
+        gain = strtod(signal_gain_arg, &end);
+        if (!*signal_gain_arg || *end || !(gain > 0.0 && gain <= 16.0)) {
+            fprintf(stderr, "ERROR: --signal-gain '%s' out of range (0 < g <= 16).\n", signal_gain_arg);
+            exit(1);
+        }
+    };
     if (cn0_arg) {
         char *end = nullptr;
         const double cn0 = strtod(cn0_arg, &end);
@@ -668,23 +738,18 @@ int main(int argc, char *argv[])
             fprintf(stderr, "ERROR: --cn0 '%s' is not a number (dB-Hz).\n", cn0_arg);
             exit(1);
         }
-        double gain = 0.0;
         if (signal_gain_arg) {
-            gain = strtod(signal_gain_arg, &end);
-            if (!*signal_gain_arg || *end || !(gain > 0.0 && gain <= 16.0)) {
-                fprintf(stderr, "ERROR: --signal-gain '%s' out of range (0 < g <= 16).\n", signal_gain_arg);
-                exit(1);
-            }
+            given_gain();
         } else {
-            // the largest power of two <= 1 with 5 sigma + 4100 g <= 32767 (4100: the largest |x| of the reference's scenarios,
-            // DESIGN.md section 10); sigma is proportional to g
+            // the largest power of two <= 1 with 5 sigma + 4100 g + the --jam amplitudes <= 32767 (4100: the largest |x| of the
+            // reference's scenarios); sigma and the amplitudes are proportional to g
             gal_iq_noise_t unit;
             if (gal_synth_noise_from_cn0(cn0, kSampleRate, 1.0, &unit) != GAL_OK) {
                 fprintf(stderr, "ERROR: --cn0 %s: %s\n", cn0_arg, gal_synth_last_error());
                 exit(1);
             }
             gain = 1.0;
-            while (gain > 1.0 / 65536.0 && (5.0 * (unit.sigma_q4 / 16.0) + 4100.0) * gain > 32767.0) gain *= 0.5;
+            while (gain > 1.0 / 65536.0 && (5.0 * (unit.sigma_q4 / 16.0) + 4100.0 + jam_unit) * gain > 32767.0) gain *= 0.5;
         }
         if (gal_synth_noise_from_cn0(cn0, kSampleRate, gain, &noise) != GAL_OK) {
             fprintf(stderr, "ERROR: --cn0 %s: %s\n", cn0_arg, gal_synth_last_error());
@@ -710,9 +775,9 @@ int main(int argc, char *argv[])
         }
         noise_on = true;
         const double sigma = noise.sigma_q4 / 16.0;
-        if (iq_format == GAL_IQ_IBYTE && !iq_shift_arg) {  // the smallest shift with 127 x 2^s >= 4 sigma
+        if (iq_format == GAL_IQ_IBYTE && !iq_shift_arg) {  // the smallest shift with 127 x 2^s >= 4 sigma + the --jam amplitudes
             iq_shift = 0;
-            while (iq_shift < 15 && 127.0 * (double)(1 << iq_shift) < 4.0 * sigma) ++iq_shift;
+            while (iq_shift < 15 && 127.0 * (double)(1 << iq_shift) < 4.0 * sigma + jam_unit * gain) ++iq_shift;
         }
         if (!sitesfile[0]) {  // (--sites: every child prints its own)
             fprintf(stderr, "Noise floor: C/N0 %g dB-Hz -> sigma %.1f LSB, signal gain %g%s, seed %llu, stream %u", cn0, sigma, gain,
@@ -721,6 +786,41 @@ int main(int argc, char *argv[])
             fprintf(stderr, "\n");
         }
     }
+    gal_iq_interf_t interf[GAL_INTERF_MAX];
+    memset(interf, 0, sizeof(interf));
+    if (n_jam > 0) {
+        if (!cn0_arg) {  // the sources alone on top of the scaled signals
+            if (signal_gain_arg) given_gain();
+            else
+                while (gain > 1.0 / 65536.0 && (4100.0 + jam_unit) * gain > 32767.0) gain *= 0.5;
+            noise.gain_q16 = (uint32_t)llround(gain * 65536.0);  // (sigma_q4 0: nothing random is computed)
+            if (iq_format == GAL_IQ_IBYTE && !iq_shift_arg) {  // the smallest shift with 127 x 2^s >= 4100 g + the amplitudes
+                iq_shift = 0;
+                while (iq_shift < 15 && 127.0 * (double)(1 << iq_shift) < (4100.0 + jam_unit) * gain) ++iq_shift;
+            }
+        }
+        for (int k = 0; k < n_jam; ++k)
+            if (gal_synth_interf_make(jam[k].js_db, gain, kSampleRate, jam[k].f_lo, jam[k].f_hi, jam[k].sweep_s, jam[k].period_s, jam[k].on_s,
+                                      &interf[k]) != GAL_OK) {
+                fprintf(stderr, "ERROR: --jam %s: %s\n", jam_args[k], gal_synth_last_error());
+                exit(1);
+            }
+        if (!sitesfile[0]) {  // (--sites: every child prints its own)
+            if (!cn0_arg) {
+                fprintf(stderr, "Interference without a noise floor: signal gain %g%s", gain, signal_gain_arg ? "" : " (chosen)");
+                if (iq_format == GAL_IQ_IBYTE) fprintf(stderr, ", --iq-shift %d%s", iq_shift, iq_shift_arg ? "" : " (chosen)");
+                fprintf(stderr, "\n");
+            }
+            for (int k = 0; k < n_jam; ++k) {
+                const gal_iq_interf_t &c = interf[k];
+                const double f_lo = c.f0 / 4294967296.0 * kSampleRate;
+                fprintf(stderr, "Interference %d: J/S %g dB -> A %.1f LSB, %.1f Hz .. %.1f Hz, sweep %u samples, pulse %u of %u samples\n", k + 1,
+                        jam[k].js_db, c.amp_q4 / 16.0, f_lo, f_lo + (double)c.df * c.sweep_len / 4294967296.0 * kSampleRate, c.sweep_len,
+                        c.pulse_on, c.pulse_period);
+            }
+        }
+    }
+    const bool mix_on = noise_on || n_jam > 0;  // a pass over the final int16 batch in front of the format
     // monitor: checked here too, before any device work.  Without --monitor nothing below differs from a build without it.
     int monitor_every = 10;
     FILE *monitor_fp = nullptr;
@@ -860,7 +960,7 @@ int main(int argc, char *argv[])
             fprintf(stderr, "ERROR: buffer allocation failed\n");
             exit(1);
         }
-        if ((iq_format != GAL_IQ_ISHORT || noise_on) && hipEventCreateWithFlags(&converted[i], hipEventDisableTiming) != hipSuccess) {
+        if ((iq_format != GAL_IQ_ISHORT || mix_on) && hipEventCreateWithFlags(&converted[i], hipEventDisableTiming) != hipSuccess) {
             fprintf(stderr, "ERROR: buffer allocation failed\n");
             exit(1);
         }
@@ -1067,12 +1167,14 @@ int main(int argc, char *argv[])
             fprintf(stderr, "[timing] batch at %7.2f ms: %3d epochs, waited %.2f ms for rows, %.2f for a free slot, plan + execute + finish %.2f\n",
                     std::chrono::duration<double, std::milli>(tb0 - t_start).count(), n, tb_rows, tb_slot - tb_rows, tb_synth - tb_slot);
         slot[cur].bytes = epoch_bytes * n;
-        if (iq_format != GAL_IQ_ISHORT || noise_on) {
+        if (iq_format != GAL_IQ_ISHORT || mix_on) {
             // the conversion of the final int16 batch, on the engine's stream; both copy streams wait for it.  With --cn0 the noise
             // goes in in the same pass (ishort: in place in d_iq[cur]); first_sample is the running sample count, so the file does
             // not depend on the batch length
             const size_t n_samples = (size_t)n * cfg.samples_per_epoch;
-            const int crc = noise_on ? gal_synth_iq_convert_noise(eng, d_iq[cur], n_samples, (uint64_t)emitted * (uint64_t)cfg.samples_per_epoch,
+            const int crc = n_jam > 0 ? gal_synth_iq_convert_interf(eng, d_iq[cur], n_samples, (uint64_t)emitted * (uint64_t)cfg.samples_per_epoch,
+                                                                    &noise, interf, n_jam, iq_format, iq_shift, d_out[cur])
+                            : noise_on ? gal_synth_iq_convert_noise(eng, d_iq[cur], n_samples, (uint64_t)emitted * (uint64_t)cfg.samples_per_epoch,
                                                                   &noise, iq_format, iq_shift, d_out[cur])
                                      : gal_synth_iq_convert(eng, d_iq[cur], n_samples, iq_format, iq_shift, d_out[cur]);
             if (crc != GAL_OK) {
@@ -1185,7 +1287,7 @@ int main(int argc, char *argv[])
     if (gal_scen_eph_gaps(scen) > 0)
         fprintf(stderr, "NOTE: %d (satellite, refresh) pairs ran on a stale ephemeris record (see the warning above)\n",
                 gal_scen_eph_gaps(scen));
-    if (iq_format == GAL_IQ_IBYTE || noise_on) {
+    if (iq_format == GAL_IQ_IBYTE || mix_on) {
         // (stderr: with -o - the data go to stdout)
         uint64_t n_sat = 0;
         const double n_val = (double)emitted * cfg.samples_per_epoch * 2;

@@ -93,6 +93,8 @@ int galk_launch_synth(const DevPlan *P, const DevPlan *Pd, int nch, int accumula
 hipError_t galk_launch_iq(int format, const int16_t *in, uint64_t n_val, int shift, void *out, unsigned long long *sat, hipStream_t st);
 hipError_t galk_launch_iq_noise(int format, const int16_t *in, uint64_t n_val, uint64_t first_sample, uint64_t seed, uint32_t stream,
                                 uint32_t gain_q16, uint32_t sigma_q4, int shift, void *out, unsigned long long *sat, hipStream_t st);
+hipError_t galk_launch_iq_interf(int format, const int16_t *in, uint64_t n_val, uint64_t first_sample, const gal_iq_noise_t *noise,
+                                 const gal_iq_interf_t *src, int n_src, int shift, void *out, unsigned long long *sat, hipStream_t st);
 hipError_t galk_launch_corr(int format, const void *buf, uint64_t n_eff, uint64_t code_ph0, uint64_t code_dph, uint32_t carr_ph0,
                             uint32_t carr_step0, uint32_t dopp_step, int delay0, int delay_step, int n_delay, int n_dopp, int max_periods,
                             const uint32_t *lut_dev, const uint32_t *code_dev, long long *out, hipStream_t st);
@@ -1821,6 +1823,103 @@ int gal_synth_noise_from_cn0(double cn0_dbhz, double sample_rate, double gain, g
     memset(out, 0, sizeof(*out));
     out->gain_q16 = (uint32_t)llround(gain * 65536.0);
     out->sigma_q4 = (uint32_t)llround(sigma_q4);
+    return GAL_OK;
+}
+
+// ---- interference sources (iq_interf.hip) -------------------------------------------------------------------------------------
+int gal_synth_iq_convert_interf(gal_synth_t *h, const int16_t *iq_dev, size_t n_samples, uint64_t first_sample, const gal_iq_noise_t *noise,
+                                const gal_iq_interf_t *interf, int32_t n_interf, int32_t format, int32_t shift, void *out_dev)
+{
+    if (n_interf < 0 || n_interf > GAL_INTERF_MAX)
+        return fail(GAL_E_INVAL, "gal_synth_iq_convert_interf: n_interf %d (0..%d)", n_interf, GAL_INTERF_MAX);
+    if (n_interf == 0) return gal_synth_iq_convert_noise(h, iq_dev, n_samples, first_sample, noise, format, shift, out_dev);
+    if (!h) return fail(GAL_E_INVAL, "null handle");
+    if (!interf) return fail(GAL_E_INVAL, "gal_synth_iq_convert_interf: null interf with n_interf %d", n_interf);
+    gal_iq_interf_t src[GAL_INTERF_MAX];  // the caller's array is not looked at again
+    memcpy(src, interf, (size_t)n_interf * sizeof(gal_iq_interf_t));
+    for (int k = 0; k < n_interf; ++k) {
+        const gal_iq_interf_t &c = src[k];
+        if (c.amp_q4 > (1u << 20) || (c.sweep_len == 0 && c.df != 0) || c.pulse_on > c.pulse_period || c.reserved != 0)
+            return fail(GAL_E_INVAL, "gal_synth_iq_convert_interf: source %d: amp_q4 %u (0..2^20), df %d with sweep_len %u (0 without a sweep), "
+                        "pulse_on %u of pulse_period %u, reserved %u (0)", k, c.amp_q4, c.df, c.sweep_len, c.pulse_on, c.pulse_period, c.reserved);
+    }
+    if (format != GAL_IQ_ISHORT && format != GAL_IQ_IBYTE && format != GAL_IQ_IBIT)
+        return fail(GAL_E_INVAL, "gal_synth_iq_convert_interf: unknown format %d (GAL_IQ_ISHORT 0, GAL_IQ_IBYTE 1, GAL_IQ_IBIT 2)", format);
+    if (format == GAL_IQ_IBYTE ? (shift < 0 || shift > 15) : shift != 0)
+        return fail(GAL_E_INVAL, "gal_synth_iq_convert_interf: shift %d (0..15 for GAL_IQ_IBYTE, 0 otherwise)", shift);
+    if (noise && (noise->gain_q16 > (1u << 20) || noise->sigma_q4 > (1u << 20) || noise->reserved != 0))
+        return fail(GAL_E_INVAL, "gal_synth_iq_convert_interf: gain_q16 %u, sigma_q4 %u (both 0..2^20), reserved %u (0)", noise->gain_q16,
+                    noise->sigma_q4, noise->reserved);
+    if (first_sample >> 62) return fail(GAL_E_INVAL, "gal_synth_iq_convert_interf: first_sample must be below 2^62");
+    if (!iq_dev || !out_dev || ((uintptr_t)iq_dev & 15) || ((uintptr_t)out_dev & 15))
+        return fail(GAL_E_INVAL, "gal_synth_iq_convert_interf: device pointers must be non-null and 16-byte aligned");
+    if (n_samples == 0) return GAL_OK;
+    if (!(format == GAL_IQ_ISHORT && (const void *)iq_dev == out_dev)) {  // exactly in place: every lane rewrites the vector it has read
+        const char *x = (const char *)iq_dev, *y = x + 4 * n_samples;
+        const char *o = (const char *)out_dev, *e = o + gal_synth_iq_bytes(format, n_samples);
+        if (x < e && o < y) return fail(GAL_E_INVAL, "gal_synth_iq_convert_interf: input and output overlap (only ishort exactly in place may)");
+    }
+    if (h->in_flight && h->last_iq) {  // the batch in flight may still be synthesised again by gal_synth_finish
+        const char *a = (const char *)h->last_iq, *b = a + (size_t)h->range_ne * (size_t)h->P.N * 4;
+        const char *x = (const char *)iq_dev, *y = x + 4 * n_samples;
+        if (x < b && a < y) return fail(GAL_E_STATE, "gal_synth_iq_convert_interf: input of the batch in flight (call gal_synth_finish first)");
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = handle_stream(h);
+    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
+    if (!h->d_iq_sat) {
+        unsigned long long *c = nullptr;
+        HIP_TRY(hipMalloc((void **)&c, sizeof(unsigned long long)));
+        const hipError_t err = hipMemsetAsync(c, 0, sizeof(unsigned long long), st);
+        if (err != hipSuccess) {  // (never keep a counter that was not zeroed)
+            hipFree(c);
+            return fail(GAL_E_DEVICE, "gal_synth_iq_convert_interf: hipMemsetAsync of the counter failed: %s", hipGetErrorString(err));
+        }
+        h->d_iq_sat = c;
+    }
+    HIP_TRY(galk_launch_iq_interf(format, iq_dev, 2 * (uint64_t)n_samples, first_sample, noise, src, n_interf, shift, out_dev, h->d_iq_sat, st));
+    return GAL_OK;
+}
+
+int gal_synth_interf_make(double js_db, double gain, double sample_rate, double f_lo_hz, double f_hi_hz, double sweep_s, double pulse_period_s,
+                          double pulse_on_s, gal_iq_interf_t *out)
+{
+    if (!out) return fail(GAL_E_INVAL, "gal_synth_interf_make: null argument");
+    if (!std::isfinite(js_db) || !std::isfinite(gain) || !std::isfinite(sample_rate) || !std::isfinite(f_lo_hz) || !std::isfinite(sweep_s) ||
+        !std::isfinite(pulse_period_s) || !std::isfinite(pulse_on_s) || (sweep_s != 0.0 && !std::isfinite(f_hi_hz)))
+        return fail(GAL_E_INVAL, "gal_synth_interf_make: an argument is not finite");
+    if (sample_rate <= 0.0 || gain < 0.0 || sweep_s < 0.0 || pulse_period_s < 0.0 || pulse_on_s < 0.0)
+        return fail(GAL_E_INVAL, "gal_synth_interf_make: sample rate %g Hz (> 0), gain %g, sweep %g s, pulse %g of %g s (all >= 0)", sample_rate, gain,
+                    sweep_s, pulse_on_s, pulse_period_s);
+    // a tone A e^(j theta) has the power A^2, the composite signal of one satellite 2 (250 gain)^2 (include/galsynth.h)
+    const double amp_q4 = 16.0 * 250.0 * sqrt(2.0) * gain * pow(10.0, js_db / 20.0);
+    if (!(amp_q4 <= 1048576.0))
+        return fail(GAL_E_INVAL, "gal_synth_interf_make: amplitude %g LSB at J/S %g dB is beyond the 65536 LSB amp_q4 holds", amp_q4 / 16.0, js_db);
+    const double half = sample_rate / 2.0;
+    if (!(fabs(f_lo_hz) < half) || (sweep_s != 0.0 && !(fabs(f_hi_hz) < half)))
+        return fail(GAL_E_INVAL, "gal_synth_interf_make: frequencies %g, %g Hz must lie inside +-%g Hz", f_lo_hz, f_hi_hz, half);
+    const double len = sweep_s * sample_rate, period = pulse_period_s * sample_rate, on = pulse_on_s * sample_rate;
+    if (!(len < 4294967295.5) || !(period < 4294967295.5) || !(on < 4294967295.5))
+        return fail(GAL_E_INVAL, "gal_synth_interf_make: sweep %g, pulse period %g, pulse on %g samples do not fit 32 bits", len, period, on);
+    gal_iq_interf_t c;
+    memset(&c, 0, sizeof(c));
+    c.amp_q4 = (uint32_t)llround(amp_q4);
+    const long long f0 = llround(f_lo_hz / sample_rate * 4294967296.0);
+    long long df = 0;
+    if (sweep_s != 0.0) {
+        c.sweep_len = (uint32_t)llround(len);
+        if (c.sweep_len < 1) return fail(GAL_E_INVAL, "gal_synth_interf_make: a sweep of %g s is less than one sample", sweep_s);
+        df = llround((f_hi_hz - f_lo_hz) / sample_rate * 4294967296.0 / (double)c.sweep_len);
+    }
+    if (f0 < INT32_MIN || f0 > INT32_MAX || df < INT32_MIN || df > INT32_MAX)  // (a frequency that rounds to sample_rate / 2 itself)
+        return fail(GAL_E_INVAL, "gal_synth_interf_make: phase step %lld, increment %lld per sample do not fit 32 bits", f0, df);
+    c.f0 = (int32_t)f0;
+    c.df = (int32_t)df;
+    c.pulse_period = (uint32_t)llround(period);
+    c.pulse_on = (uint32_t)llround(on);
+    if (c.pulse_on > c.pulse_period)
+        return fail(GAL_E_INVAL, "gal_synth_interf_make: pulse on %u of a period of %u samples", c.pulse_on, c.pulse_period);
+    *out = c;
     return GAL_OK;
 }
 

@@ -99,6 +99,24 @@ class _Noise(ctypes.Structure):  # gal_iq_noise_t
     ]
 
 
+class _Interf(ctypes.Structure):  # gal_iq_interf_t (32 bytes)
+    _fields_ = [
+        ("amp_q4", ctypes.c_uint32),
+        ("ph0", ctypes.c_uint32),
+        ("f0", ctypes.c_int32),
+        ("df", ctypes.c_int32),
+        ("sweep_len", ctypes.c_uint32),
+        ("pulse_period", ctypes.c_uint32),
+        ("pulse_on", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+assert ctypes.sizeof(_Interf) == 32
+INTERF_FIELDS = tuple(name for name, _ in _Interf._fields_ if name != "reserved")
+GAL_INTERF_MAX = 4
+
+
 class _CorrReq(ctypes.Structure):  # gal_corr_req_t (56 bytes)
     _fields_ = [
         ("prn", ctypes.c_int32),
@@ -151,6 +169,8 @@ EXPORTED_SYMBOLS = (
     "gal_synth_iq_saturated",
     "gal_synth_iq_convert_noise",
     "gal_synth_noise_from_cn0",
+    "gal_synth_iq_convert_interf",
+    "gal_synth_interf_make",
     "gal_synth_corr_out_bytes",
     "gal_synth_correlate",
     "gal_tables_e1b",
@@ -159,6 +179,7 @@ EXPORTED_SYMBOLS = (
     "gal_tables_sin512",
     "gal_tables_cs25",
     "gal_tables_gauss",
+    "gal_tables_cos1024",
 )
 
 _libs = {}
@@ -213,6 +234,11 @@ def load_library(hooks=False):
     lib.gal_synth_iq_convert_noise.restype = ctypes.c_int
     lib.gal_synth_noise_from_cn0.argtypes = [ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(_Noise)]
     lib.gal_synth_noise_from_cn0.restype = ctypes.c_int
+    lib.gal_synth_iq_convert_interf.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_uint64, ctypes.POINTER(_Noise), ctypes.POINTER(_Interf), i32,
+                                                i32, i32, vp]
+    lib.gal_synth_iq_convert_interf.restype = ctypes.c_int
+    lib.gal_synth_interf_make.argtypes = [ctypes.c_double] * 8 + [ctypes.POINTER(_Interf)]
+    lib.gal_synth_interf_make.restype = ctypes.c_int
     lib.gal_synth_corr_out_bytes.argtypes = [ctypes.POINTER(_CorrReq)]
     lib.gal_synth_corr_out_bytes.restype = ctypes.c_size_t
     lib.gal_synth_correlate.argtypes = [vp, vp, i32, ctypes.c_size_t, ctypes.POINTER(_CorrReq), i32, vp]
@@ -222,7 +248,7 @@ def load_library(hooks=False):
     lib.gal_corr_cn0.argtypes = [vp, ctypes.POINTER(_CorrReq), i32, i32, i32, ctypes.c_double, ctypes.POINTER(ctypes.c_double),
                                  ctypes.POINTER(ctypes.c_double)]
     lib.gal_corr_cn0.restype = ctypes.c_int
-    for name in ("gal_tables_e1b", "gal_tables_e1c", "gal_tables_cos512", "gal_tables_sin512", "gal_tables_gauss"):
+    for name in ("gal_tables_e1b", "gal_tables_e1c", "gal_tables_cos512", "gal_tables_sin512", "gal_tables_gauss", "gal_tables_cos1024"):
         getattr(lib, name).restype = vp
     lib.gal_tables_cs25.restype = ctypes.c_uint32
     _libs[hooks] = lib
@@ -267,6 +293,33 @@ def _noise_struct(noise):
         noise = (noise.get("seed", 0), noise.get("stream", 0), noise["gain_q16"], noise["sigma_q4"])
     seed, stream, gain_q16, sigma_q4 = (int(v) for v in noise)
     return _Noise(seed, stream, gain_q16, sigma_q4, 0)
+
+
+def interf_make(js_db, gain, sample_rate, f_lo_hz, f_hi_hz=0.0, sweep_s=0.0, pulse_period_s=0.0, pulse_on_s=0.0):
+    """gal_synth_interf_make (no GPU needed): one source of the `interf` list of SynthEngine.iq_convert for a jammer-to-signal ratio
+    in dB against one satellite's composite E1B + E1C signal at `gain` -- a CW tone at f_lo_hz (sweep_s = 0) or a chirp from f_lo_hz
+    to f_hi_hz that restarts every sweep_s seconds, on for pulse_on_s of every pulse_period_s seconds (0: always)."""
+    lib = load_library()
+    c = _Interf()
+    rc = lib.gal_synth_interf_make(float(js_db), float(gain), float(sample_rate), float(f_lo_hz), float(f_hi_hz), float(sweep_s),
+                                   float(pulse_period_s), float(pulse_on_s), ctypes.byref(c))
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+    return {k: int(getattr(c, k)) for k in INTERF_FIELDS}
+
+
+def _interf_struct(src):
+    """dict with the fields of gal_iq_interf_t but `reserved` (amp_q4 is required, the others default to 0), or an _Interf."""
+    if isinstance(src, _Interf):
+        return src
+    unknown = set(src) - set(INTERF_FIELDS)
+    if unknown:
+        raise ValueError("interference source: unknown keys %s" % sorted(unknown))
+    d = dict.fromkeys(INTERF_FIELDS, 0)
+    d.update(src)
+    if "amp_q4" not in src:
+        raise ValueError("interference source: amp_q4 is required")
+    return _Interf(**{k: int(d[k]) for k in INTERF_FIELDS})
 
 
 def _corr_struct(req):
@@ -331,6 +384,7 @@ def tables():
         "sin512": arr(lib.gal_tables_sin512(), ctypes.c_int16, 512, (512,)),
         "cs25": int(lib.gal_tables_cs25()),
         "gauss": arr(lib.gal_tables_gauss(), ctypes.c_int32, 32 * 32 * 2, (32, 32, 2)),
+        "cos1024": arr(lib.gal_tables_cos1024(), ctypes.c_int16, 1024, (1024,)),
     }
 
 
@@ -452,17 +506,27 @@ class SynthEngine:
         self.n_epochs = p.shape[0]
         return iq, st, {k: getattr(stats, k) for k, _ in _Stats._fields_}
 
-    def iq_convert(self, iq_ptr, n_samples, fmt, shift=None, out_ptr=None, noise=None, first_sample=0):
+    def iq_convert(self, iq_ptr, n_samples, fmt, shift=None, out_ptr=None, noise=None, first_sample=0, interf=None):
         """Enqueue on the handle's stream: n_samples complex int16 samples at device address iq_ptr (final output: behind finish())
         -> `fmt` ("ishort" | "ibyte" | "ibit") at device address out_ptr (iq_bytes(fmt, n_samples) bytes, not overlapping the input).
         Both 16-byte aligned; shift 0..15 for "ibyte" (None: IQ_SHIFT_DEFAULT), 0 (or None) otherwise.  iq_saturated() is the fence.
         noise: a dict (seed, stream, gain_q16, sigma_q4; noise_from_cn0 makes one) or a tuple in that order -- the seeded noise floor
         of gal_synth_iq_convert_noise in front of the format; first_sample is then the index of the call's first complex sample in
-        the whole output stream, and "ishort" may run in place (out_ptr == iq_ptr)."""
+        the whole output stream, and "ishort" may run in place (out_ptr == iq_ptr).
+        interf: a list of up to GAL_INTERF_MAX sources (dicts with the fields of gal_iq_interf_t; interf_make makes one) -- CW, chirp
+        and pulsed interference of gal_synth_iq_convert_interf, added in the same pass, with or without `noise`."""
         if out_ptr is None:
             raise ValueError("iq_convert: out_ptr is required")
         if shift is None:
             shift = IQ_SHIFT_DEFAULT if iq_format_code(fmt) == GAL_IQ_IBYTE else 0
+        if interf is not None:
+            src = [_interf_struct(c) for c in interf]
+            arr = (_Interf * max(1, len(src)))(*src)
+            nz = _noise_struct(noise) if noise is not None else None
+            self._check(self._lib.gal_synth_iq_convert_interf(self._h, ctypes.c_void_p(int(iq_ptr)), int(n_samples), int(first_sample),
+                                                              ctypes.byref(nz) if nz is not None else None, arr, len(src),
+                                                              iq_format_code(fmt), int(shift), ctypes.c_void_p(int(out_ptr))))
+            return
         if noise is None:
             self._check(self._lib.gal_synth_iq_convert(self._h, ctypes.c_void_p(int(iq_ptr)), int(n_samples), iq_format_code(fmt),
                                                        int(shift), ctypes.c_void_p(int(out_ptr))))

@@ -321,6 +321,58 @@ int gal_synth_iq_convert_noise(gal_synth_t *h, const int16_t *iq_dev, size_t n_s
 int gal_synth_noise_from_cn0(double cn0_dbhz, double sample_rate, double gain, gal_iq_noise_t *out);
 
 /*
+ * Interference (not in the reference): up to GAL_INTERF_MAX sources -- a CW tone, a linear chirp that restarts every sweep_len samples
+ * (a sawtooth in frequency, phase-continuous), either of them pulsed -- added behind the signal gain and in front of the ONE clamp to
+ * int16, in the same pass as the noise floor.  Like the noise it is a FIXED INTEGER FUNCTION of (parameters, index of the value in the
+ * whole output stream, int16 input): the same bits on any machine and for any cut into batches and calls (tests/interf_model.py states
+ * it in numpy).
+ *
+ * N = first_sample + j / 2, 64-bit: the global index of the complex sample that value j belongs to.  All phase arithmetic is modulo 2^32.
+ *   (s, m) = (0, N) for sweep_len = 0, otherwise (N div sweep_len, N mod sweep_len)
+ *   W      = sweep_len f0 + df sweep_len (sweep_len - 1) / 2, the phase advance of one whole sweep
+ *   phi(N) = ph0 + s W + m f0 + df (m (m - 1) / 2)            (sweep_len = 0: ph0 + N f0)
+ *            = the recurrence phi(0) = ph0, phi(N + 1) = phi(N) + f0 + (N mod sweep_len) df.  m (m - 1) is even and below 2^64, hence
+ *            exact in uint64; of s only the low 32 bits matter
+ *   i      = phi >> 22;  C = gal_tables_cos1024(): C[k] = round(4096 cos(2 pi k / 1024)), int16 in Q12
+ *   gate   = 1 if pulse_period = 0 or (N mod pulse_period) < pulse_on, else 0
+ *   t[j]   = gate A C[i] for the I value (j even), gate A C[(i - 256) & 1023] for the Q value (the sine: a positive f0 is a positive
+ *            frequency offset), A = amp_q4
+ *   y[j]   = clamp((int64(x[j]) G + int64(z) S + sum over the sources of t[j] + 32768) >> 16, -32768, 32767)
+ * with x, G, S, z exactly as the noise floor defines them (no noise: G = 65536, S = 0).  y then takes the three formats unchanged.  A
+ * value counts ONCE as saturated if either clamp changed it.  With no sources this is gal_synth_iq_convert_noise bit for bit.
+ */
+#define GAL_INTERF_MAX 4
+typedef struct gal_iq_interf {
+    uint32_t amp_q4;        /* A = amplitude in int16 LSB x 16, 0 .. 2^20                                                     */
+    uint32_t ph0;           /* phase at sample 0 of the whole output stream, 2^-32 cycles                                     */
+    int32_t  f0;            /* phase step per sample at the start of a sweep, 2^-32 cycles (signed: +- sample_rate / 2)        */
+    int32_t  df;            /* increment of the step per sample inside a sweep; must be 0 when sweep_len = 0                   */
+    uint32_t sweep_len;     /* samples per sweep; 0 = never restarts (CW)                                                     */
+    uint32_t pulse_period;  /* samples; 0 = always on                                                                         */
+    uint32_t pulse_on;      /* <= pulse_period: on while (N mod pulse_period) < pulse_on                                      */
+    uint32_t reserved;      /* 0                                                                                              */
+} gal_iq_interf_t;          /* 32 bytes */
+/* gal_synth_iq_convert_noise with n_interf sources added: every rule of that call holds (enqueued on the handle's stream, 16-byte
+ * alignment, GAL_IQ_ISHORT may run exactly in place and any other overlap is refused, GAL_E_STATE for the buffer of the batch in flight,
+ * gal_synth_iq_saturated as fence and counter, first_sample < 2^62).  noise may be NULL: G = 65536, S = 0, nothing random.  n_interf = 0
+ * IS gal_synth_iq_convert_noise.  `interf` is copied before the call returns.  GAL_E_INVAL also for n_interf outside
+ * 0..GAL_INTERF_MAX, a null `interf` with n_interf > 0, amp_q4 above 2^20, df != 0 with sweep_len = 0, pulse_on > pulse_period,
+ * reserved != 0. */
+int gal_synth_iq_convert_interf(gal_synth_t *h, const int16_t *iq_dev, size_t n_samples, uint64_t first_sample,
+                                const gal_iq_noise_t *noise, const gal_iq_interf_t *interf, int32_t n_interf, int32_t format,
+                                int32_t shift, void *out_dev);
+/* A source for a jammer-to-signal ratio; needs no GPU.  J/S is stated against the same C as gal_synth_noise_from_cn0: the composite
+ * E1B + E1C signal of ONE satellite has the total (both rails) power C = 2 (250 gain)^2 and a tone A e^(j theta) the total power A^2,
+ * so   amp_q4 = round(16 x 250 sqrt(2) gain 10^(js_db / 20)).
+ * f0 = llround(f_lo_hz / sample_rate x 2^32).  sweep_s = 0: CW (f_hi_hz is not looked at, sweep_len = 0, df = 0); otherwise
+ * sweep_len = llround(sweep_s sample_rate) >= 1 and df = llround((f_hi_hz - f_lo_hz) / sample_rate x 2^32 / sweep_len).
+ * pulse_period, pulse_on = llround(seconds x sample_rate); ph0 and reserved are set to 0.
+ * GAL_E_INVAL for a null `out`, a non-finite argument, sample_rate <= 0, a negative gain, time or duration, |f| >= sample_rate / 2,
+ * an amplitude beyond the 2^20 of amp_q4, a sweep that rounds to 0 samples, lengths beyond 32 bits, pulse_on > pulse_period. */
+int gal_synth_interf_make(double js_db, double gain, double sample_rate, double f_lo_hz, double f_hi_hz, double sweep_s,
+                          double pulse_period_s, double pulse_on_s, gal_iq_interf_t *out);
+
+/*
  * Correlator bank and C/N0 monitor (not in the reference): despread a device buffer of output IQ with the engine's own replica of one
  * satellite and get, per code period, delay and Doppler bin, the complex correlation sums of the E1B and the E1C component.  Read-only
  * on the buffer, in any of the three formats.  Like the formats and the noise floor it is a FIXED INTEGER FUNCTION of its inputs: the
@@ -401,6 +453,7 @@ const int16_t  *gal_tables_cos512(void);/* [512]     */
 const int16_t  *gal_tables_sin512(void);/* [512]     */
 uint32_t        gal_tables_cs25(void);
 const int32_t  *gal_tables_gauss(void); /* [32][32][2] = T of the noise floor (above); needs no GPU */
+const int16_t  *gal_tables_cos1024(void);/* [1024] = C of the interference sources (above); needs no GPU */
 
 #ifdef __cplusplus
 }
