@@ -1172,11 +1172,9 @@ int main(int argc, char *argv[])
             // goes in in the same pass (ishort: in place in d_iq[cur]); first_sample is the running sample count, so the file does
             // not depend on the batch length
             const size_t n_samples = (size_t)n * cfg.samples_per_epoch;
-            const int crc = n_jam > 0 ? gal_synth_iq_convert_interf(eng, d_iq[cur], n_samples, (uint64_t)emitted * (uint64_t)cfg.samples_per_epoch,
-                                                                    &noise, interf, n_jam, iq_format, iq_shift, d_out[cur])
-                            : noise_on ? gal_synth_iq_convert_noise(eng, d_iq[cur], n_samples, (uint64_t)emitted * (uint64_t)cfg.samples_per_epoch,
-                                                                  &noise, iq_format, iq_shift, d_out[cur])
-                                     : gal_synth_iq_convert(eng, d_iq[cur], n_samples, iq_format, iq_shift, d_out[cur]);
+            // (without --cn0, `noise` still carries the signal gain of the --jam sources; with neither the library converts plainly)
+            const int crc = gal_synth_iq_convert_interf(eng, d_iq[cur], n_samples, (uint64_t)emitted * (uint64_t)cfg.samples_per_epoch,
+                                                        mix_on ? &noise : NULL, interf, n_jam, iq_format, iq_shift, d_out[cur]);
             if (crc != GAL_OK) {
                 fprintf(stderr, "\nERROR: %s\n", gal_synth_last_error());
                 rc = 1;

@@ -90,11 +90,8 @@ int galk_scanm_blocks(int legs);
 size_t galk_scanm_bytes(int S, int legs);
 int galk_launch_synth(const DevPlan *P, const DevPlan *Pd, int nch, int accumulate, const uint8_t *act,
                       const int *nact, uint32_t *iq, int e0, int ne, hipStream_t st);
-hipError_t galk_launch_iq(int format, const int16_t *in, uint64_t n_val, int shift, void *out, unsigned long long *sat, hipStream_t st);
-hipError_t galk_launch_iq_noise(int format, const int16_t *in, uint64_t n_val, uint64_t first_sample, uint64_t seed, uint32_t stream,
-                                uint32_t gain_q16, uint32_t sigma_q4, int shift, void *out, unsigned long long *sat, hipStream_t st);
-hipError_t galk_launch_iq_interf(int format, const int16_t *in, uint64_t n_val, uint64_t first_sample, const gal_iq_noise_t *noise,
-                                 const gal_iq_interf_t *src, int n_src, int shift, void *out, unsigned long long *sat, hipStream_t st);
+hipError_t galk_launch_iq_pass(int format, const int16_t *in, uint64_t n_val, uint64_t first_sample, const gal_iq_noise_t *noise,
+                               const gal_iq_interf_t *src, int n_src, int shift, void *out, unsigned long long *sat, hipStream_t st);
 hipError_t galk_launch_corr(int format, const void *buf, uint64_t n_eff, uint64_t code_ph0, uint64_t code_dph, uint32_t carr_ph0,
                             uint32_t carr_step0, uint32_t dopp_step, int delay0, int delay_step, int n_delay, int n_dopp, int max_periods,
                             const uint32_t *lut_dev, const uint32_t *code_dev, long long *out, hipStream_t st);
@@ -1714,7 +1711,7 @@ int gal_synth_run_host_n(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t
     return GAL_OK;
 }
 
-// ---- output formats (iq_format.hip) ------------------------------------------------------------------------------------------
+// ---- output formats, noise floor, interference sources (iq_pass.hip) ---------------------------------------------------------------
 size_t gal_synth_iq_bytes(int32_t format, size_t n_samples)
 {
     switch (format) {
@@ -1725,90 +1722,84 @@ size_t gal_synth_iq_bytes(int32_t format, size_t n_samples)
     }
 }
 
-int gal_synth_iq_convert(gal_synth_t *h, const int16_t *iq_dev, size_t n_samples, int32_t format, int32_t shift, void *out_dev)
+// the handle's saturation counter, made (and zeroed on `st`) at the first pass that may count
+static int ensure_sat_counter(gal_synth *h, hipStream_t st)
+{
+    if (h->d_iq_sat) return GAL_OK;
+    unsigned long long *c = nullptr;
+    HIP_TRY(hipMalloc((void **)&c, sizeof(unsigned long long)));
+    const hipError_t err = hipMemsetAsync(c, 0, sizeof(unsigned long long), st);
+    if (err != hipSuccess) {  // (never keep a counter that was not zeroed)
+        hipFree(c);
+        return fail(GAL_E_DEVICE, "hipMemsetAsync of the saturation counter failed: %s", hipGetErrorString(err));
+    }
+    h->d_iq_sat = c;
+    return GAL_OK;
+}
+
+// The one check path of the three conversions below, `who` in the messages.  in_place: ishort may run with out_dev == iq_dev (every
+// lane rewrites the vector it has read); otherwise any overlap would race (ibyte: lane i writes where lane i / 2 reads), and the
+// kernels take both as __restrict__.
+static int iq_pass(const char *who, bool in_place, gal_synth_t *h, const int16_t *iq_dev, size_t n_samples, uint64_t first_sample,
+                   const gal_iq_noise_t *noise, const gal_iq_interf_t *interf, int32_t n_interf, int32_t format, int32_t shift, void *out_dev)
 {
     if (!h) return fail(GAL_E_INVAL, "null handle");
+    gal_iq_interf_t src[GAL_INTERF_MAX];  // the caller's array is not looked at again
+    if (n_interf > 0) {
+        if (!interf) return fail(GAL_E_INVAL, "%s: null interf with n_interf %d", who, n_interf);
+        memcpy(src, interf, (size_t)n_interf * sizeof(gal_iq_interf_t));
+    }
+    for (int k = 0; k < n_interf; ++k) {
+        const gal_iq_interf_t &c = src[k];
+        if (c.amp_q4 > (1u << 20) || (c.sweep_len == 0 && c.df != 0) || c.pulse_on > c.pulse_period || c.reserved != 0)
+            return fail(GAL_E_INVAL, "%s: source %d: amp_q4 %u (0..2^20), df %d with sweep_len %u (0 without a sweep), "
+                        "pulse_on %u of pulse_period %u, reserved %u (0)", who, k, c.amp_q4, c.df, c.sweep_len, c.pulse_on, c.pulse_period, c.reserved);
+    }
     if (format != GAL_IQ_ISHORT && format != GAL_IQ_IBYTE && format != GAL_IQ_IBIT)
-        return fail(GAL_E_INVAL, "gal_synth_iq_convert: unknown format %d (GAL_IQ_ISHORT 0, GAL_IQ_IBYTE 1, GAL_IQ_IBIT 2)", format);
+        return fail(GAL_E_INVAL, "%s: unknown format %d (GAL_IQ_ISHORT 0, GAL_IQ_IBYTE 1, GAL_IQ_IBIT 2)", who, format);
     if (format == GAL_IQ_IBYTE ? (shift < 0 || shift > 15) : shift != 0)
-        return fail(GAL_E_INVAL, "gal_synth_iq_convert: shift %d (0..15 for GAL_IQ_IBYTE, 0 otherwise)", shift);
+        return fail(GAL_E_INVAL, "%s: shift %d (0..15 for GAL_IQ_IBYTE, 0 otherwise)", who, shift);
+    if (noise && (noise->gain_q16 > (1u << 20) || noise->sigma_q4 > (1u << 20) || noise->reserved != 0))
+        return fail(GAL_E_INVAL, "%s: gain_q16 %u, sigma_q4 %u (both 0..2^20), reserved %u (0)", who, noise->gain_q16, noise->sigma_q4,
+                    noise->reserved);
+    if (first_sample >> 62) return fail(GAL_E_INVAL, "%s: first_sample must be below 2^62", who);
     if (!iq_dev || !out_dev || ((uintptr_t)iq_dev & 15) || ((uintptr_t)out_dev & 15))
-        return fail(GAL_E_INVAL, "gal_synth_iq_convert: device pointers must be non-null and 16-byte aligned");
+        return fail(GAL_E_INVAL, "%s: device pointers must be non-null and 16-byte aligned", who);
     if (n_samples == 0) return GAL_OK;
-    {  // in place would race (ibyte: lane i writes where lane i / 2 reads), and the kernels take both as __restrict__
-        const char *x = (const char *)iq_dev, *y = x + 4 * n_samples;
+    const char *x = (const char *)iq_dev, *y = x + 4 * n_samples;
+    if (!(in_place && format == GAL_IQ_ISHORT && (const void *)iq_dev == out_dev)) {
         const char *o = (const char *)out_dev, *e = o + gal_synth_iq_bytes(format, n_samples);
-        if (x < e && o < y) return fail(GAL_E_INVAL, "gal_synth_iq_convert: input and output overlap");
+        if (x < e && o < y)
+            return fail(GAL_E_INVAL, "%s: input and output overlap%s", who, in_place ? " (only ishort exactly in place may)" : "");
     }
     if (h->in_flight && h->last_iq) {  // the batch in flight may still be synthesised again by gal_synth_finish
         const char *a = (const char *)h->last_iq, *b = a + (size_t)h->range_ne * (size_t)h->P.N * 4;
-        const char *x = (const char *)iq_dev, *y = x + 4 * n_samples;
-        if (x < b && a < y) return fail(GAL_E_STATE, "gal_synth_iq_convert: input of the batch in flight (call gal_synth_finish first)");
+        if (x < b && a < y) return fail(GAL_E_STATE, "%s: input of the batch in flight (call gal_synth_finish first)", who);
     }
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = handle_stream(h);
     if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
-    if (format == GAL_IQ_ISHORT) {
+    if (format == GAL_IQ_ISHORT && !noise && n_interf == 0) {  // nothing to mix: a copy
         HIP_TRY(hipMemcpyAsync(out_dev, iq_dev, 4 * n_samples, hipMemcpyDeviceToDevice, st));
         return GAL_OK;
     }
-    if (!h->d_iq_sat) {
-        unsigned long long *c = nullptr;
-        HIP_TRY(hipMalloc((void **)&c, sizeof(unsigned long long)));
-        const hipError_t err = hipMemsetAsync(c, 0, sizeof(unsigned long long), st);
-        if (err != hipSuccess) {  // (never keep a counter that was not zeroed)
-            hipFree(c);
-            return fail(GAL_E_DEVICE, "gal_synth_iq_convert: hipMemsetAsync of the counter failed: %s", hipGetErrorString(err));
-        }
-        h->d_iq_sat = c;
-    }
-    HIP_TRY(galk_launch_iq(format, iq_dev, 2 * (uint64_t)n_samples, shift, out_dev, h->d_iq_sat, st));
+    const int rc = ensure_sat_counter(h, st);
+    if (rc) return rc;
+    HIP_TRY(galk_launch_iq_pass(format, iq_dev, 2 * (uint64_t)n_samples, first_sample, noise, src, n_interf, shift, out_dev, h->d_iq_sat, st));
     return GAL_OK;
 }
 
-// ---- noise floor (iq_noise.hip) ----------------------------------------------------------------------------------------------
+int gal_synth_iq_convert(gal_synth_t *h, const int16_t *iq_dev, size_t n_samples, int32_t format, int32_t shift, void *out_dev)
+{
+    return iq_pass("gal_synth_iq_convert", false, h, iq_dev, n_samples, 0, nullptr, nullptr, 0, format, shift, out_dev);
+}
+
+// ---- noise floor ---------------------------------------------------------------------------------------------------------------
 int gal_synth_iq_convert_noise(gal_synth_t *h, const int16_t *iq_dev, size_t n_samples, uint64_t first_sample, const gal_iq_noise_t *noise,
                                int32_t format, int32_t shift, void *out_dev)
 {
     if (!noise) return gal_synth_iq_convert(h, iq_dev, n_samples, format, shift, out_dev);
-    if (!h) return fail(GAL_E_INVAL, "null handle");
-    if (format != GAL_IQ_ISHORT && format != GAL_IQ_IBYTE && format != GAL_IQ_IBIT)
-        return fail(GAL_E_INVAL, "gal_synth_iq_convert_noise: unknown format %d (GAL_IQ_ISHORT 0, GAL_IQ_IBYTE 1, GAL_IQ_IBIT 2)", format);
-    if (format == GAL_IQ_IBYTE ? (shift < 0 || shift > 15) : shift != 0)
-        return fail(GAL_E_INVAL, "gal_synth_iq_convert_noise: shift %d (0..15 for GAL_IQ_IBYTE, 0 otherwise)", shift);
-    if (noise->gain_q16 > (1u << 20) || noise->sigma_q4 > (1u << 20) || noise->reserved != 0)
-        return fail(GAL_E_INVAL, "gal_synth_iq_convert_noise: gain_q16 %u, sigma_q4 %u (both 0..2^20), reserved %u (0)", noise->gain_q16,
-                    noise->sigma_q4, noise->reserved);
-    if (first_sample >> 62) return fail(GAL_E_INVAL, "gal_synth_iq_convert_noise: first_sample must be below 2^62");
-    if (!iq_dev || !out_dev || ((uintptr_t)iq_dev & 15) || ((uintptr_t)out_dev & 15))
-        return fail(GAL_E_INVAL, "gal_synth_iq_convert_noise: device pointers must be non-null and 16-byte aligned");
-    if (n_samples == 0) return GAL_OK;
-    if (!(format == GAL_IQ_ISHORT && (const void *)iq_dev == out_dev)) {  // exactly in place: every lane rewrites the vector it has read
-        const char *x = (const char *)iq_dev, *y = x + 4 * n_samples;
-        const char *o = (const char *)out_dev, *e = o + gal_synth_iq_bytes(format, n_samples);
-        if (x < e && o < y) return fail(GAL_E_INVAL, "gal_synth_iq_convert_noise: input and output overlap (only ishort exactly in place may)");
-    }
-    if (h->in_flight && h->last_iq) {  // the batch in flight may still be synthesised again by gal_synth_finish
-        const char *a = (const char *)h->last_iq, *b = a + (size_t)h->range_ne * (size_t)h->P.N * 4;
-        const char *x = (const char *)iq_dev, *y = x + 4 * n_samples;
-        if (x < b && a < y) return fail(GAL_E_STATE, "gal_synth_iq_convert_noise: input of the batch in flight (call gal_synth_finish first)");
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = handle_stream(h);
-    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
-    if (!h->d_iq_sat) {
-        unsigned long long *c = nullptr;
-        HIP_TRY(hipMalloc((void **)&c, sizeof(unsigned long long)));
-        const hipError_t err = hipMemsetAsync(c, 0, sizeof(unsigned long long), st);
-        if (err != hipSuccess) {  // (never keep a counter that was not zeroed)
-            hipFree(c);
-            return fail(GAL_E_DEVICE, "gal_synth_iq_convert_noise: hipMemsetAsync of the counter failed: %s", hipGetErrorString(err));
-        }
-        h->d_iq_sat = c;
-    }
-    HIP_TRY(galk_launch_iq_noise(format, iq_dev, 2 * (uint64_t)n_samples, first_sample, noise->seed, noise->stream, noise->gain_q16,
-                                 noise->sigma_q4, shift, out_dev, h->d_iq_sat, st));
-    return GAL_OK;
+    return iq_pass("gal_synth_iq_convert_noise", true, h, iq_dev, n_samples, first_sample, noise, nullptr, 0, format, shift, out_dev);
 }
 
 int gal_synth_noise_from_cn0(double cn0_dbhz, double sample_rate, double gain, gal_iq_noise_t *out)
@@ -1826,59 +1817,14 @@ int gal_synth_noise_from_cn0(double cn0_dbhz, double sample_rate, double gain, g
     return GAL_OK;
 }
 
-// ---- interference sources (iq_interf.hip) -------------------------------------------------------------------------------------
+// ---- interference sources ------------------------------------------------------------------------------------------------------
 int gal_synth_iq_convert_interf(gal_synth_t *h, const int16_t *iq_dev, size_t n_samples, uint64_t first_sample, const gal_iq_noise_t *noise,
                                 const gal_iq_interf_t *interf, int32_t n_interf, int32_t format, int32_t shift, void *out_dev)
 {
     if (n_interf < 0 || n_interf > GAL_INTERF_MAX)
         return fail(GAL_E_INVAL, "gal_synth_iq_convert_interf: n_interf %d (0..%d)", n_interf, GAL_INTERF_MAX);
     if (n_interf == 0) return gal_synth_iq_convert_noise(h, iq_dev, n_samples, first_sample, noise, format, shift, out_dev);
-    if (!h) return fail(GAL_E_INVAL, "null handle");
-    if (!interf) return fail(GAL_E_INVAL, "gal_synth_iq_convert_interf: null interf with n_interf %d", n_interf);
-    gal_iq_interf_t src[GAL_INTERF_MAX];  // the caller's array is not looked at again
-    memcpy(src, interf, (size_t)n_interf * sizeof(gal_iq_interf_t));
-    for (int k = 0; k < n_interf; ++k) {
-        const gal_iq_interf_t &c = src[k];
-        if (c.amp_q4 > (1u << 20) || (c.sweep_len == 0 && c.df != 0) || c.pulse_on > c.pulse_period || c.reserved != 0)
-            return fail(GAL_E_INVAL, "gal_synth_iq_convert_interf: source %d: amp_q4 %u (0..2^20), df %d with sweep_len %u (0 without a sweep), "
-                        "pulse_on %u of pulse_period %u, reserved %u (0)", k, c.amp_q4, c.df, c.sweep_len, c.pulse_on, c.pulse_period, c.reserved);
-    }
-    if (format != GAL_IQ_ISHORT && format != GAL_IQ_IBYTE && format != GAL_IQ_IBIT)
-        return fail(GAL_E_INVAL, "gal_synth_iq_convert_interf: unknown format %d (GAL_IQ_ISHORT 0, GAL_IQ_IBYTE 1, GAL_IQ_IBIT 2)", format);
-    if (format == GAL_IQ_IBYTE ? (shift < 0 || shift > 15) : shift != 0)
-        return fail(GAL_E_INVAL, "gal_synth_iq_convert_interf: shift %d (0..15 for GAL_IQ_IBYTE, 0 otherwise)", shift);
-    if (noise && (noise->gain_q16 > (1u << 20) || noise->sigma_q4 > (1u << 20) || noise->reserved != 0))
-        return fail(GAL_E_INVAL, "gal_synth_iq_convert_interf: gain_q16 %u, sigma_q4 %u (both 0..2^20), reserved %u (0)", noise->gain_q16,
-                    noise->sigma_q4, noise->reserved);
-    if (first_sample >> 62) return fail(GAL_E_INVAL, "gal_synth_iq_convert_interf: first_sample must be below 2^62");
-    if (!iq_dev || !out_dev || ((uintptr_t)iq_dev & 15) || ((uintptr_t)out_dev & 15))
-        return fail(GAL_E_INVAL, "gal_synth_iq_convert_interf: device pointers must be non-null and 16-byte aligned");
-    if (n_samples == 0) return GAL_OK;
-    if (!(format == GAL_IQ_ISHORT && (const void *)iq_dev == out_dev)) {  // exactly in place: every lane rewrites the vector it has read
-        const char *x = (const char *)iq_dev, *y = x + 4 * n_samples;
-        const char *o = (const char *)out_dev, *e = o + gal_synth_iq_bytes(format, n_samples);
-        if (x < e && o < y) return fail(GAL_E_INVAL, "gal_synth_iq_convert_interf: input and output overlap (only ishort exactly in place may)");
-    }
-    if (h->in_flight && h->last_iq) {  // the batch in flight may still be synthesised again by gal_synth_finish
-        const char *a = (const char *)h->last_iq, *b = a + (size_t)h->range_ne * (size_t)h->P.N * 4;
-        const char *x = (const char *)iq_dev, *y = x + 4 * n_samples;
-        if (x < b && a < y) return fail(GAL_E_STATE, "gal_synth_iq_convert_interf: input of the batch in flight (call gal_synth_finish first)");
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = handle_stream(h);
-    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
-    if (!h->d_iq_sat) {
-        unsigned long long *c = nullptr;
-        HIP_TRY(hipMalloc((void **)&c, sizeof(unsigned long long)));
-        const hipError_t err = hipMemsetAsync(c, 0, sizeof(unsigned long long), st);
-        if (err != hipSuccess) {  // (never keep a counter that was not zeroed)
-            hipFree(c);
-            return fail(GAL_E_DEVICE, "gal_synth_iq_convert_interf: hipMemsetAsync of the counter failed: %s", hipGetErrorString(err));
-        }
-        h->d_iq_sat = c;
-    }
-    HIP_TRY(galk_launch_iq_interf(format, iq_dev, 2 * (uint64_t)n_samples, first_sample, noise, src, n_interf, shift, out_dev, h->d_iq_sat, st));
-    return GAL_OK;
+    return iq_pass("gal_synth_iq_convert_interf", true, h, iq_dev, n_samples, first_sample, noise, interf, n_interf, format, shift, out_dev);
 }
 
 int gal_synth_interf_make(double js_db, double gain, double sample_rate, double f_lo_hz, double f_hi_hz, double sweep_s, double pulse_period_s,

@@ -519,22 +519,11 @@ class SynthEngine:
             raise ValueError("iq_convert: out_ptr is required")
         if shift is None:
             shift = IQ_SHIFT_DEFAULT if iq_format_code(fmt) == GAL_IQ_IBYTE else 0
-        if interf is not None:
-            src = [_interf_struct(c) for c in interf]
-            arr = (_Interf * max(1, len(src)))(*src)
-            nz = _noise_struct(noise) if noise is not None else None
-            self._check(self._lib.gal_synth_iq_convert_interf(self._h, ctypes.c_void_p(int(iq_ptr)), int(n_samples), int(first_sample),
-                                                              ctypes.byref(nz) if nz is not None else None, arr, len(src),
-                                                              iq_format_code(fmt), int(shift), ctypes.c_void_p(int(out_ptr))))
-            return
-        if noise is None:
-            self._check(self._lib.gal_synth_iq_convert(self._h, ctypes.c_void_p(int(iq_ptr)), int(n_samples), iq_format_code(fmt),
-                                                       int(shift), ctypes.c_void_p(int(out_ptr))))
-            return
-        nz = _noise_struct(noise)
-        self._check(self._lib.gal_synth_iq_convert_noise(self._h, ctypes.c_void_p(int(iq_ptr)), int(n_samples), int(first_sample),
-                                                         ctypes.byref(nz), iq_format_code(fmt), int(shift),
-                                                         ctypes.c_void_p(int(out_ptr))))
+        src = [_interf_struct(c) for c in interf or ()]  # (the library itself goes on to the noise / plain call where one is absent)
+        nz = _noise_struct(noise) if noise is not None else None
+        self._check(self._lib.gal_synth_iq_convert_interf(self._h, ctypes.c_void_p(int(iq_ptr)), int(n_samples), int(first_sample),
+                                                          ctypes.byref(nz) if nz is not None else None, (_Interf * max(1, len(src)))(*src),
+                                                          len(src), iq_format_code(fmt), int(shift), ctypes.c_void_p(int(out_ptr))))
 
     def iq_saturated(self, reset=False):
         """Waits for the conversions enqueued so far; int16 values saturated by "ibyte" conversions since create (or the last reset)."""

@@ -95,11 +95,14 @@ def test_formats_sizes_and_first_sample(eng, data, first_sample, with_noise):
     ("ishort", 0, 2_200_003, True, ((FOUR, (1 << 33) + 2), (LONG, 999_999))),
     ("ibyte", 6, 4_300_005, False, ((FOUR, (1 << 33) + 3), (LONG, 999_998))),
     ("ibit", 0, 16_900_007, False, (([FOUR[1], LONG[1], FOUR[3]], (1 << 33) + 999_999),)),
+    ("ishort", 0, 2_200_003, True, (([], (1 << 33) + 4), ([], (1 << 33) + 7))),  # noise only, even and odd
+    ("ishort", 0, 2_200_003, False, ((FOUR, (1 << 33) + 6),)),  # sources without noise
 ])
 def test_beyond_one_trip_of_the_grid(eng, fmt, s, n, with_noise, cases):
     """More vectors than the 2048 x 256 lanes of the grid (4, 8, 32 complex samples per vector): the lanes of the first blocks take a
     second trip, and (s, m) and the pulse position jump by the constant stride -- with sweeps and periods shorter than a vector
-    (FOUR) and longer than the jump (LONG)."""
+    (FOUR) and longer than the jump (LONG).  The instances without sources and the one without noise share that loop and its tail:
+    an empty source list is the noise floor alone (interf_model.convert is then noise_model.convert)."""
     import torch
 
     x = _input(n, 41)

@@ -5,8 +5,9 @@
         One conversion of BASELINE config 1's batch (1199 epochs x 260 000 = 311.74 M complex samples) into ibyte and ibit, and the
         CLI's per-batch conversion (128 epochs), timed with device events on the handle's stream.  Bytes moved: int16 in + format
         out; the share is of 6.29 TB/s, the measured float4-copy rate of the chip's HBM.  Run it under `rocprofv3 --kernel-trace --stats` for the
-        kernel times of the profiler (k_iq_ibyte, k_iq_ibit).  Then the same with the noise floor at 45 dB-Hz mixed in (ishort in
-        place, ibyte at shift 7, ibit; k_iqn_ishort, k_iqn_ibyte, k_iqn_ibit), beside the plain legs in the same process.
+        kernel times of the profiler (k_iq_pass<FmtByte, 0, false>, k_iq_pass<FmtBit, 0, false> of csrc/iq_pass.hip).  Then the same with
+        the noise floor at 45 dB-Hz mixed in (ishort in place, ibyte at shift 7, ibit; k_iq_pass<Fmt, 1, false>), beside the plain legs in
+        the same process.
     python tools/iq_format_e2e.py cli [--reps R] [--dir D]
         The CLI on config 1 (-l -6,51,100 -t 2022/02/20,12:00:00 -d 120) in each format, into /dev/null and into a file under D
         (default /dev/shm, a tmpfs), alternating formats; the rate is the CLI's own "Process time" figure (samples / s).

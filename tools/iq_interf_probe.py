@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Probe of the interference pass (gal_synth_iq_convert_interf) on the MI355X: at the CLI's batch -- 128 epochs = 33.28 M complex
-samples -- and in each output format, the time of one call with the noise floor alone (n_interf = 0: the kernels of iq_noise.hip),
+samples -- and in each output format, the time of one call with the noise floor alone (n_interf = 0: the instances k_iq_pass<Fmt, 1, false> of csrc/iq_pass.hip),
 with 1 and with 4 sources on top of it, and with 1 source and no noise.  The variants alternate inside every repetition, each call
 between two events on the engine's stream; the noise-only call is timed twice per repetition, so that the difference of its two
 series is the run-to-run scatter against which the others are read.  Kernel times proper:
