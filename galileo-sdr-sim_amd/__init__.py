@@ -15,6 +15,8 @@ from .synth import (  # noqa: F401
     CHAN_EPOCH_DTYPE,
     CHAN_STATE_DTYPE,
     GAL_CH_RESTART,
+    GAL_GAIN_MAX,
+    GAL_GAIN_UNITY,
     GAL_IQ_IBIT,
     GAL_IQ_IBYTE,
     GAL_IQ_ISHORT,
@@ -25,6 +27,7 @@ from .synth import (  # noqa: F401
     corr_from_epoch,
     corr_out_bytes,
     device_count,
+    gain_q7,
     interf_make,
     iq_bytes,
     load_library,

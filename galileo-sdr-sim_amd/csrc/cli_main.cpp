@@ -16,6 +16,11 @@
 // --jam js_db,f_hz[,f_hi_hz,sweep_us[,period_us,on_us]] (not in the reference), up to four times: CW, chirp or pulsed interference at
 // a stated J/S, with or without --cn0, in that same pass (gal_synth_iq_convert_interf); again a fixed function of the command line.
 //
+// --power-model, --antenna <file>, --prn-power prn:dB[,...] (the reference computes such a gain per channel and epoch and leaves it
+// commented out in its loop, src/galileo-sdr.cpp:469-477, 520-521): per-satellite signal power -- path loss, a receiver antenna pattern,
+// per-PRN offsets -- as Q7 gains from the front-end (gal_scen_next_gains), applied by gal_synth_run_gains in front of noise,
+// interference and the format.  Without the three options every byte is the reference's.
+//
 // --monitor <file> (not in the reference): the built-in receiver check -- every --monitor-every'th epoch (default 10) the first 25 code
 // periods of every active channel are despread, in the buffer as it is written (behind noise and format), with the planned replica
 // (gal_synth_correlate); one CSV line per (epoch, PRN) with the measured C/N0 and where the peak lies.  Read-only: the IQ is the same.
@@ -102,6 +107,10 @@ void usage(const char *prog)
            "  --jam <spec>     Add an interference source, up to 4 times: js_db,f_hz[,f_hi_hz,sweep_us[,period_us,on_us]] -- J/S in dB against\n"
            "                   one satellite's composite signal, a CW tone at f_hz from the centre, or a chirp from f_hz to f_hi_hz that\n"
            "                   restarts every sweep_us microseconds, on for on_us of every period_us; with or without --cn0\n"
+           "  --power-model    Per-satellite signal power from the path loss: gain = 23 222 km / distance (a satellite at the zenith is\n"
+           "                   about unity); --cn0 and --jam then hold for a satellite at unity gain\n"
+           "  --antenna <file> Receiver antenna pattern: 37 attenuations in dB, one per 5 degrees off the zenith (default: isotropic)\n"
+           "  --prn-power <l>  Per-PRN power offsets prn:dB[,prn:dB...], e.g. 5:-6,12:3 (PRN 1..50, -60..60 dB)\n"
            "  --monitor <file> Despread the output with the planned replicas and write one CSV line per monitored epoch and PRN:\n"
            "                   time, PRN, planned Doppler, measured C/N0 (composite E1B + E1C), peak ratio, strongest of the delays\n"
            "                   -1 / 0 / +1 half chip and of the Doppler offsets -1 / 0 / +1 bin of 250 Hz; a summary per PRN on stderr\n"
@@ -310,6 +319,74 @@ bool parse_jam(const char *arg, JamSpec *j)
     j->sweep_s = v[3] * 1e-6;
     j->period_s = v[4] * 1e-6;
     j->on_s = v[5] * 1e-6;
+    return true;
+}
+
+// ---- --prn-power prn:dB[,prn:dB...] and --antenna <file> ----------------------------------------------------------------------------
+constexpr double kPowerDbMax = 60.0;  // |offset| and |attenuation| accepted, dB
+
+// a number that ends at `stop` (or at the end of the string), finite and within +-kPowerDbMax
+bool parse_db(const char *p, char **end, double *v)
+{
+    if (!*p || *p == ' ' || *p == '\t' || *p == '\n') return false;
+    *v = strtod(p, end);
+    return *end != p && std::isfinite(*v) && fabs(*v) <= kPowerDbMax;
+}
+
+bool parse_prn_power(const char *arg, double (&off)[GAL_NUM_PRN])
+{
+    const char *p = arg;
+    for (;;) {
+        char *end = nullptr;
+        if (*p < '0' || *p > '9') return false;
+        const long prn = strtol(p, &end, 10);
+        if (prn < 1 || prn > GAL_NUM_PRN || *end != ':') return false;
+        double db;
+        p = end + 1;
+        if (!parse_db(p, &end, &db)) return false;
+        off[prn - 1] = db;
+        if (!*end) return true;
+        if (*end != ',') return false;
+        p = end + 1;
+    }
+}
+
+// GAL_GAIN_PATTERN_LEN numbers separated by white space or commas, nothing else (# starts a comment that runs to the end of the line)
+bool load_antenna(const char *path, double (&pat)[GAL_GAIN_PATTERN_LEN], std::string *why)
+{
+    FILE *fp = fopen(path, "r");
+    if (!fp) {
+        *why = "cannot read it";
+        return false;
+    }
+    std::string text;
+    char buf[4096];
+    size_t n;
+    while ((n = fread(buf, 1, sizeof(buf), fp)) > 0 && text.size() < (1u << 20)) text.append(buf, n);
+    fclose(fp);
+    int count = 0;
+    const char *p = text.c_str();
+    for (;;) {
+        while (*p == ' ' || *p == '\t' || *p == '\n' || *p == '\r' || *p == ',') ++p;
+        if (*p == '#') {
+            while (*p && *p != '\n') ++p;
+            continue;
+        }
+        if (!*p) break;
+        char *end = nullptr;
+        double v;
+        if (!parse_db(p, &end, &v)) {
+            *why = "value " + std::to_string(count + 1) + " is not a number of dB within +-60";
+            return false;
+        }
+        if (count < GAL_GAIN_PATTERN_LEN) pat[count] = v;
+        ++count;
+        p = end;
+    }
+    if (count != GAL_GAIN_PATTERN_LEN) {
+        *why = "it holds " + std::to_string(count) + " values, not " + std::to_string(GAL_GAIN_PATTERN_LEN);
+        return false;
+    }
     return true;
 }
 
@@ -551,13 +628,16 @@ int main(int argc, char *argv[])
     int batch_epochs = 128, n_writers = -1, sites_gpus = 0, sites_per_gpu = 1;
     const char *iq_format_arg = "ishort", *iq_shift_arg = nullptr;
     const char *monitor_arg = nullptr, *monitor_every_arg = nullptr;
+    bool power_model = false;
+    const char *antenna_arg = nullptr;
+    std::vector<const char *> prn_power_args;
     const char *cn0_arg = nullptr, *noise_seed_arg = nullptr, *noise_stream_arg = nullptr, *signal_gain_arg = nullptr;
     std::vector<const char *> jam_args;
     sc.udp_port = GAL_SCEN_UDP_PORT;  // the reference always listens for position updates (src/galileo-sdr.cpp:185)
     sc.udp_loopback = 1;              // ... on every interface; the default listener here takes local datagrams only
 
     enum { OPT_STRICT = 1000, OPT_SITES, OPT_WRITERS, OPT_GPUS, OPT_PER_GPU, OPT_EXACT, OPT_SHIFT_TOE, OPT_REF_T, OPT_IQ_FORMAT, OPT_IQ_SHIFT, OPT_CN0, OPT_NOISE_SEED,
-           OPT_NOISE_STREAM, OPT_SIGNAL_GAIN, OPT_MONITOR, OPT_MONITOR_EVERY, OPT_JAM };
+           OPT_NOISE_STREAM, OPT_SIGNAL_GAIN, OPT_MONITOR, OPT_MONITOR_EVERY, OPT_JAM, OPT_POWER_MODEL, OPT_ANTENNA, OPT_PRN_POWER };
     static const struct option long_opts[] = {{"strict", no_argument, nullptr, OPT_STRICT},
                                               {"exact-replay", no_argument, nullptr, OPT_EXACT},
                                               {"shift-toe", no_argument, nullptr, OPT_SHIFT_TOE},
@@ -575,6 +655,9 @@ int main(int argc, char *argv[])
                                               {"monitor", required_argument, nullptr, OPT_MONITOR},
                                               {"monitor-every", required_argument, nullptr, OPT_MONITOR_EVERY},
                                               {"jam", required_argument, nullptr, OPT_JAM},
+                                              {"power-model", no_argument, nullptr, OPT_POWER_MODEL},
+                                              {"antenna", required_argument, nullptr, OPT_ANTENNA},
+                                              {"prn-power", required_argument, nullptr, OPT_PRN_POWER},
                                               {nullptr, 0, nullptr, 0}};
     std::vector<std::string> child_args;  // --sites: everything but -l / -o / --sites / --gpus / --per-gpu / --noise-stream goes to the children
     int opt;
@@ -583,7 +666,8 @@ int main(int argc, char *argv[])
             if (opt >= 1000) {
                 child_args.push_back(opt == OPT_STRICT ? "--strict" : opt == OPT_EXACT ? "--exact-replay" : opt == OPT_SHIFT_TOE ? "--shift-toe" : opt == OPT_REF_T ? "--ref-T"
                                      : opt == OPT_IQ_FORMAT ? "--iq-format" : opt == OPT_IQ_SHIFT ? "--iq-shift" : opt == OPT_CN0 ? "--cn0"
-                                     : opt == OPT_NOISE_SEED ? "--noise-seed" : opt == OPT_SIGNAL_GAIN ? "--signal-gain" : opt == OPT_MONITOR_EVERY ? "--monitor-every" : opt == OPT_JAM ? "--jam" : "--writers");
+                                     : opt == OPT_NOISE_SEED ? "--noise-seed" : opt == OPT_SIGNAL_GAIN ? "--signal-gain" : opt == OPT_MONITOR_EVERY ? "--monitor-every" : opt == OPT_JAM ? "--jam" : opt == OPT_POWER_MODEL ? "--power-model"
+                                     : opt == OPT_ANTENNA ? "--antenna" : opt == OPT_PRN_POWER ? "--prn-power" : "--writers");
             } else {
                 char name[3] = {'-', (char)opt, 0};
                 child_args.push_back(name);
@@ -644,6 +728,9 @@ int main(int argc, char *argv[])
         case OPT_MONITOR: monitor_arg = optarg; break;
         case OPT_MONITOR_EVERY: monitor_every_arg = optarg; break;
         case OPT_JAM: jam_args.push_back(optarg); break;
+        case OPT_POWER_MODEL: power_model = true; break;
+        case OPT_ANTENNA: antenna_arg = optarg; break;
+        case OPT_PRN_POWER: prn_power_args.push_back(optarg); break;
         case 'n': case 'g': case 'G': case 'a': case 'p': case 'i': case 'U': case 'b': break;
         case ':':
         case '?':
@@ -691,6 +778,38 @@ int main(int argc, char *argv[])
     } else if (iq_format == GAL_IQ_IBYTE) {
         iq_shift = 5;  // sigma of 9-12 channels ~ 750-870 LSB: 23-27 LSB after the shift, the clamp at ~5 sigma
     }
+    // per-satellite signal power: checked here too.  Without the three options nothing below differs from a build without them.
+    const bool power_on = power_model || antenna_arg || !prn_power_args.empty();
+    double ant_db[GAL_GAIN_PATTERN_LEN], prn_db[GAL_NUM_PRN];
+    memset(ant_db, 0, sizeof(ant_db));
+    memset(prn_db, 0, sizeof(prn_db));
+    for (const char *a : prn_power_args)
+        if (!parse_prn_power(a, prn_db)) {
+            fprintf(stderr, "ERROR: --prn-power '%s' is not prn:dB[,prn:dB...] (PRN 1..%d, -60..60 dB).\n", a, GAL_NUM_PRN);
+            exit(1);
+        }
+    if (antenna_arg) {
+        std::string why;
+        if (!load_antenna(antenna_arg, ant_db, &why)) {
+            fprintf(stderr, "ERROR: --antenna %s: %s.\n", antenna_arg, why.c_str());
+            exit(1);
+        }
+    }
+    // the largest gain the options can produce, as a factor: the path loss of a satellite at the zenith of a low orbit point (the
+    // nominal altitude against 22 900 km: 1.4 %), the least attenuation of the pattern, the largest offset (PRNs without one: 0 dB).
+    // It scales the 4100 LSB of the headroom rules below
+    double power_peak = 1.0;
+    if (power_on) {
+        double att = ant_db[0], off = 0.0;
+        for (double v : ant_db) att = v < att ? v : att;
+        for (double v : prn_db) off = v > off ? v : off;
+        power_peak = (power_model ? 23222000.0 / 22900000.0 : 1.0) * pow(10.0, -att / 20.0) * pow(10.0, off / 20.0);
+        if (!sitesfile[0])
+            fprintf(stderr, "Signal power: path loss %s, antenna %s, %zu PRN offset list%s; largest gain %.3f (%.2f dB)\n", power_model ? "on" : "off",
+                    antenna_arg ? antenna_arg : "isotropic", prn_power_args.size(), prn_power_args.size() == 1 ? "" : "s", power_peak,
+                    20.0 * log10(power_peak));
+    }
+    const double sig_peak = 4100.0 * power_peak;  // the largest |x| of the signal sum: 4100 in the reference's scenarios
     // noise floor: checked here too.  Without --cn0 nothing below differs from a build without it.
     const double kSampleRate = 2.6e6;
     bool noise_on = false;
@@ -749,7 +868,7 @@ int main(int argc, char *argv[])
                 exit(1);
             }
             gain = 1.0;
-            while (gain > 1.0 / 65536.0 && (5.0 * (unit.sigma_q4 / 16.0) + 4100.0 + jam_unit) * gain > 32767.0) gain *= 0.5;
+            while (gain > 1.0 / 65536.0 && (5.0 * (unit.sigma_q4 / 16.0) + sig_peak + jam_unit) * gain > 32767.0) gain *= 0.5;
         }
         if (gal_synth_noise_from_cn0(cn0, kSampleRate, gain, &noise) != GAL_OK) {
             fprintf(stderr, "ERROR: --cn0 %s: %s\n", cn0_arg, gal_synth_last_error());
@@ -792,11 +911,11 @@ int main(int argc, char *argv[])
         if (!cn0_arg) {  // the sources alone on top of the scaled signals
             if (signal_gain_arg) given_gain();
             else
-                while (gain > 1.0 / 65536.0 && (4100.0 + jam_unit) * gain > 32767.0) gain *= 0.5;
+                while (gain > 1.0 / 65536.0 && (sig_peak + jam_unit) * gain > 32767.0) gain *= 0.5;
             noise.gain_q16 = (uint32_t)llround(gain * 65536.0);  // (sigma_q4 0: nothing random is computed)
             if (iq_format == GAL_IQ_IBYTE && !iq_shift_arg) {  // the smallest shift with 127 x 2^s >= 4100 g + the amplitudes
                 iq_shift = 0;
-                while (iq_shift < 15 && 127.0 * (double)(1 << iq_shift) < (4100.0 + jam_unit) * gain) ++iq_shift;
+                while (iq_shift < 15 && 127.0 * (double)(1 << iq_shift) < (sig_peak + jam_unit) * gain) ++iq_shift;
             }
         }
         for (int k = 0; k < n_jam; ++k)
@@ -894,6 +1013,11 @@ int main(int argc, char *argv[])
         }
         exit(1);
     }
+    if (power_on && (gal_scen_set_power(scen, antenna_arg ? ant_db : nullptr, prn_db) != GAL_OK ||
+                     gal_scen_set_path_loss(scen, power_model ? 1 : 0) != GAL_OK)) {
+        fprintf(stderr, "ERROR: %s\n", gal_scen_last_error());
+        exit(1);
+    }
     stage("scenario opened (RINEX)");
     const int total = gal_scen_total_epochs(scen);
     int32_t wk;
@@ -960,7 +1084,7 @@ int main(int argc, char *argv[])
             fprintf(stderr, "ERROR: buffer allocation failed\n");
             exit(1);
         }
-        if ((iq_format != GAL_IQ_ISHORT || mix_on) && hipEventCreateWithFlags(&converted[i], hipEventDisableTiming) != hipSuccess) {
+        if ((iq_format != GAL_IQ_ISHORT || mix_on || power_on) && hipEventCreateWithFlags(&converted[i], hipEventDisableTiming) != hipSuccess) {
             fprintf(stderr, "ERROR: buffer allocation failed\n");
             exit(1);
         }
@@ -1040,11 +1164,15 @@ int main(int argc, char *argv[])
     constexpr int kRowBufs = 3;
     struct RowBuf {
         std::vector<gal_chan_epoch_t> rows;
+        std::vector<uint16_t> gains;  // per-satellite signal power: [epochs][slots] Q7
         int n = 0;  // epochs in it; < 0: front-end error, 0 with `last`: end of the scenario
         bool ready = false;
     };
     RowBuf rb[kRowBufs];
-    for (auto &b : rb) b.rows.resize((size_t)batch_epochs * sc.n_slots);
+    for (auto &b : rb) {
+        b.rows.resize((size_t)batch_epochs * sc.n_slots);
+        if (power_on) b.gains.resize((size_t)batch_epochs * sc.n_slots);
+    }
     std::mutex rmu;
     std::condition_variable rcv;
     bool consumer_gone = false;
@@ -1062,7 +1190,9 @@ int main(int argc, char *argv[])
                              // produced no earlier than k * 0.1 s after the start, so that position updates are current
                 std::this_thread::sleep_until(t_start + std::chrono::milliseconds(100) * produced_epochs);
             }
-            const int n = g_stop ? 0 : gal_scen_next(scen, batch_epochs, rb[w].rows.data());
+            const int n = g_stop      ? 0
+                          : power_on ? gal_scen_next_gains(scen, batch_epochs, rb[w].rows.data(), rb[w].gains.data())
+                                     : gal_scen_next(scen, batch_epochs, rb[w].rows.data());
             if (n > 0) produced_epochs += n;
             {
                 std::lock_guard<std::mutex> lk(rmu);
@@ -1079,6 +1209,8 @@ int main(int argc, char *argv[])
     memset(state.data(), 0, sizeof(gal_chan_state_t) * sc.n_slots);
     bool have_state = false;
     int emitted = 0, cur = 0, rc = 0, r = 0;
+    int prn_gain_lo[GAL_NUM_PRN + 1], prn_gain_hi[GAL_NUM_PRN + 1];  // per-satellite signal power: the gains each PRN was given
+    for (int i = 0; i <= GAL_NUM_PRN; ++i) prn_gain_lo[i] = GAL_GAIN_MAX + 1, prn_gain_hi[i] = -1;
     // (SIGINT: the batch in flight is finished and written, batches the producer has queued behind it are dropped)
     const bool batch_timing = getenv("GAL_CLI_TIMING") != nullptr;
     auto ms_since = [&](std::chrono::steady_clock::time_point a) {
@@ -1140,8 +1272,23 @@ int main(int argc, char *argv[])
                 }
             }
         }
-        if (gal_synth_plan(eng, rows_ptr, n, have_state ? state.data() : nullptr) != GAL_OK ||
-            gal_synth_execute(eng, d_iq[cur]) != GAL_OK) {
+        if (power_on) {
+            // one synthesis run per group of slots with equal gains, finished when the call returns, and the weighted sum enqueued
+            // on the engine's stream behind them (include/galsynth.h)
+            const uint16_t *gp = rb[r].gains.data();
+            for (size_t i = 0; i < (size_t)n * sc.n_slots; ++i) {
+                const int prn = rows_ptr[i].prn;
+                if (prn < 1 || prn > GAL_NUM_PRN) continue;
+                prn_gain_lo[prn] = gp[i] < prn_gain_lo[prn] ? gp[i] : prn_gain_lo[prn];
+                prn_gain_hi[prn] = gp[i] > prn_gain_hi[prn] ? gp[i] : prn_gain_hi[prn];
+            }
+            if (gal_synth_run_gains(eng, rows_ptr, n, have_state ? state.data() : nullptr, gp, d_iq[cur], state.data()) != GAL_OK) {
+                fprintf(stderr, "\nERROR: %s\n", gal_synth_last_error());
+                rc = 1;
+                break;
+            }
+        } else if (gal_synth_plan(eng, rows_ptr, n, have_state ? state.data() : nullptr) != GAL_OK ||
+                   gal_synth_execute(eng, d_iq[cur]) != GAL_OK) {
             fprintf(stderr, "\nERROR: %s\n", gal_synth_last_error());
             rc = 1;
             break;
@@ -1155,7 +1302,7 @@ int main(int argc, char *argv[])
         // The IQ in d_iq[cur] is final only once gal_synth_finish() has returned: finish() may find the speculative
         // carrier chain unverified (or the replay check unhappy) and synthesise the batch again.  The copies are
         // therefore enqueued after it; they still run beside the front-end and the synthesis of the next batch.
-        if (gal_synth_finish(eng, state.data(), nullptr) != GAL_OK) {
+        if (!power_on && gal_synth_finish(eng, state.data(), nullptr) != GAL_OK) {
             fprintf(stderr, "\nERROR: %s\n", gal_synth_last_error());
             rc = 1;
             break;
@@ -1164,8 +1311,9 @@ int main(int argc, char *argv[])
         if (monitor_fp && mon[cur ^ 1].pending) monitor_flush(mon[cur ^ 1], monitor_fp, kSampleRate, mon_shape, mon_sum);
         const double tb_synth = ms_since(tb0);
         if (batch_timing)
-            fprintf(stderr, "[timing] batch at %7.2f ms: %3d epochs, waited %.2f ms for rows, %.2f for a free slot, plan + execute + finish %.2f\n",
-                    std::chrono::duration<double, std::milli>(tb0 - t_start).count(), n, tb_rows, tb_slot - tb_rows, tb_synth - tb_slot);
+            fprintf(stderr, "[timing] batch at %7.2f ms: %3d epochs, waited %.2f ms for rows, %.2f for a free slot, %s %.2f\n",
+                    std::chrono::duration<double, std::milli>(tb0 - t_start).count(), n, tb_rows, tb_slot - tb_rows,
+                    power_on ? "run_gains (every group's plan + execute + finish, the sum enqueued)" : "plan + execute + finish", tb_synth - tb_slot);
         slot[cur].bytes = epoch_bytes * n;
         if (iq_format != GAL_IQ_ISHORT || mix_on) {
             // the conversion of the final int16 batch, on the engine's stream; both copy streams wait for it.  With --cn0 the noise
@@ -1180,6 +1328,8 @@ int main(int argc, char *argv[])
                 rc = 1;
                 break;
             }
+        }
+        if (iq_format != GAL_IQ_ISHORT || mix_on || power_on) {  // what the copies read is enqueued on the engine's stream: they wait for it
             if (hipEventRecord(converted[cur], stream) != hipSuccess || hipStreamWaitEvent(copy_stream[0], converted[cur], 0) != hipSuccess ||
                 hipStreamWaitEvent(copy_stream[1], converted[cur], 0) != hipSuccess) {
                 fprintf(stderr, "\nERROR: event after the IQ conversion failed\n");
@@ -1285,7 +1435,14 @@ int main(int argc, char *argv[])
     if (gal_scen_eph_gaps(scen) > 0)
         fprintf(stderr, "NOTE: %d (satellite, refresh) pairs ran on a stale ephemeris record (see the warning above)\n",
                 gal_scen_eph_gaps(scen));
-    if (iq_format == GAL_IQ_IBYTE || mix_on) {
+    if (power_on) {
+        fprintf(stderr, "Signal power per PRN (Q7 gain, 128 = unity; dB against unity):\n");
+        for (int prn = 1; prn <= GAL_NUM_PRN; ++prn)
+            if (prn_gain_hi[prn] >= 0)
+                fprintf(stderr, "  PRN %2d: gain %5d .. %5d  (%+.2f .. %+.2f dB)\n", prn, prn_gain_lo[prn], prn_gain_hi[prn],
+                        prn_gain_lo[prn] > 0 ? 20.0 * log10(prn_gain_lo[prn] / 128.0) : -INFINITY, prn_gain_hi[prn] > 0 ? 20.0 * log10(prn_gain_hi[prn] / 128.0) : -INFINITY);
+    }
+    if (iq_format == GAL_IQ_IBYTE || mix_on || power_on) {
         // (stderr: with -o - the data go to stdout)
         uint64_t n_sat = 0;
         const double n_val = (double)emitted * cfg.samples_per_epoch * 2;

@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "gain_q7.h"
 #include "scen_internal.h"
 
 using namespace galscen;
@@ -75,6 +76,10 @@ struct gal_scen {
     int live_updates = 0, live_rejected = 0;
     bool gap_warned = false;  // ephemeris-gap policy, see gal_scen_next
     int eph_gaps = 0;         // (satellite, refresh) pairs that kept a stale record
+    // per-satellite signal power (gal_scen_set_power / gal_scen_next_gains): isotropic, no offsets, path loss on until told otherwise
+    bool have_pattern = false, path_loss = true;
+    double pattern_db[GAL_GAIN_PATTERN_LEN] = {};
+    double prn_offset_db[GAL_NUM_PRN] = {};
 
     ~gal_scen()
     {
@@ -347,14 +352,37 @@ int gal_scen_start_time(const gal_scen_t *s, int32_t *week, double *sec)
     return GAL_OK;
 }
 
-int32_t gal_scen_next(gal_scen_t *s, int32_t max_epochs, gal_chan_epoch_t *rows)
+int gal_scen_set_power(gal_scen_t *s, const double *pattern_db, const double *prn_offset_db)
 {
-    if (!s || !rows || max_epochs < 0) return scen_fail(GAL_E_INVAL, "gal_scen_next: bad argument");
+    if (!s) return scen_fail(GAL_E_INVAL, "gal_scen_set_power: null handle");
+    for (int i = 0; pattern_db && i < GAL_GAIN_PATTERN_LEN; ++i)
+        if (!std::isfinite(pattern_db[i])) return scen_fail(GAL_E_INVAL, "gal_scen_set_power: pattern value %d is not finite", i);
+    for (int i = 0; prn_offset_db && i < GAL_NUM_PRN; ++i)
+        if (!std::isfinite(prn_offset_db[i])) return scen_fail(GAL_E_INVAL, "gal_scen_set_power: the offset of PRN %d is not finite", i + 1);
+    s->have_pattern = pattern_db != nullptr;
+    if (pattern_db) memcpy(s->pattern_db, pattern_db, sizeof(s->pattern_db));
+    if (prn_offset_db) memcpy(s->prn_offset_db, prn_offset_db, sizeof(s->prn_offset_db));
+    else memset(s->prn_offset_db, 0, sizeof(s->prn_offset_db));
+    return GAL_OK;
+}
+
+int gal_scen_set_path_loss(gal_scen_t *s, int32_t enable)
+{
+    if (!s) return scen_fail(GAL_E_INVAL, "gal_scen_set_path_loss: null handle");
+    s->path_loss = enable != 0;
+    return GAL_OK;
+}
+
+// gal_scen_next and gal_scen_next_gains (gain_q7 == nullptr: the rows alone)
+static int32_t next_rows(gal_scen_t *s, int32_t max_epochs, gal_chan_epoch_t *rows, uint16_t *gain_q7)
+{
     const int S = s->cfg.n_slots;
     int produced = 0;
     while (produced < max_epochs && s->iumd < s->numd) {
         gal_chan_epoch_t *row = rows + (size_t)produced * S;
         memset(row, 0, sizeof(gal_chan_epoch_t) * S);
+        uint16_t *const grow = gain_q7 ? gain_q7 + (size_t)produced * S : nullptr;
+        if (grow) memset(grow, 0, sizeof(uint16_t) * S);  // idle slots: 0
         poll_live_position(s);
         const double *xyz = position(s, s->iumd);
         for (int i = 0; i < S; ++i) {
@@ -368,6 +396,12 @@ int32_t gal_scen_next(gal_scen_t *s, int32_t max_epochs, gal_chan_epoch_t *rows)
             const Ephemeris &eph = s->nav.sv[sv][k];
             Range rho;
             compute_range(&rho, eph, s->nav.iono, s->grx, xyz);
+            // src/galileo-sdr.cpp:469-477, as include/galsynth.h defines it (gal_synth_gain_q7); without the path loss every
+            // satellite stands at the reference distance
+            if (grow)
+                grow[i] = (uint16_t)gal_gain_q7_eval(s->path_loss ? rho.d : GAL_GAIN_REF_DISTANCE_M, rho.azel[1],
+                                                     s->have_pattern ? s->pattern_db : nullptr,
+                                                     c.prn <= GAL_NUM_PRN ? s->prn_offset_db[c.prn - 1] : 0.0);
 
             // computeCodePhase, src/gal-sig.cpp:308-347
             const double rhorate = (rho.range - c.rho0.range) / kEpochDt;
@@ -434,6 +468,18 @@ int32_t gal_scen_next(gal_scen_t *s, int32_t max_epochs, gal_chan_epoch_t *rows)
         produced++;
     }
     return produced;
+}
+
+int32_t gal_scen_next(gal_scen_t *s, int32_t max_epochs, gal_chan_epoch_t *rows)
+{
+    if (!s || !rows || max_epochs < 0) return scen_fail(GAL_E_INVAL, "gal_scen_next: bad argument");
+    return next_rows(s, max_epochs, rows, nullptr);
+}
+
+int32_t gal_scen_next_gains(gal_scen_t *s, int32_t max_epochs, gal_chan_epoch_t *rows, uint16_t *gain_q7)
+{
+    if (!s || !rows || !gain_q7 || max_epochs < 0) return scen_fail(GAL_E_INVAL, "gal_scen_next_gains: bad argument");
+    return next_rows(s, max_epochs, rows, gain_q7);
 }
 
 int gal_scen_inav_page(gal_scen_t *s, int32_t svid, int32_t eph_index, int32_t week, double sec,

@@ -21,6 +21,7 @@
 #include "nco_walk.h"
 #include "synth_dev.h"
 #include "e1_tables.inc"
+#include "gain_q7.h"
 
 // Smallest distance between two of the 15 thresholds T_u = 1 - frac(u s) of the 16-sample hold pattern (k_synth,
 // rw_phase_a): the kernel's bin table (128 bins of the group-start fraction) decides a lane only if its bin holds ONE
@@ -92,6 +93,8 @@ int galk_launch_synth(const DevPlan *P, const DevPlan *Pd, int nch, int accumula
                       const int *nact, uint32_t *iq, int e0, int ne, hipStream_t st);
 hipError_t galk_launch_iq_pass(int format, const int16_t *in, uint64_t n_val, uint64_t first_sample, const gal_iq_noise_t *noise,
                                const gal_iq_interf_t *src, int n_src, int shift, void *out, unsigned long long *sat, hipStream_t st);
+hipError_t galk_launch_iq_wsum(const int16_t *const *parts_dev, const int *gain_dev, int n_parts, int n_epochs, int samples_per_epoch, int wide,
+                               int16_t *out, unsigned long long *sat, hipStream_t st);
 hipError_t galk_launch_corr(int format, const void *buf, uint64_t n_eff, uint64_t code_ph0, uint64_t code_dph, uint32_t carr_ph0,
                             uint32_t carr_step0, uint32_t dopp_step, int delay0, int delay_step, int n_delay, int n_dopp, int max_periods,
                             const uint32_t *lut_dev, const uint32_t *code_dev, long long *out, hipStream_t st);
@@ -321,6 +324,16 @@ struct gal_synth {
     int g_holdoff = 0;  // batches for which k_synth_g is not used although it could be: its last batch listed too many groups
     unsigned long long *d_iq_sat = nullptr;  // gal_synth_iq_convert: saturated ibyte values (device; made at the first conversion)
     uint32_t *d_corr_tab = nullptr;  // gal_synth_correlate: [512] carrier table + [50][512] replica bits (device; made at the first call)
+    // gal_synth_iq_wsum: the part pointers ([GAL_ENGINE_MAX_CHAN]) and the gains ([n_epochs][n_parts] int32) of the last call, pinned
+    // on the host and on the device; ev_gain = that call's kernel is done (both are free again)
+    char *h_gain = nullptr;
+    char *d_gain = nullptr;
+    size_t gain_bytes = 0;
+    hipEvent_t ev_gain = nullptr;
+    bool gain_pending = false;
+    void *own_parts = nullptr;  // gal_synth_run_gains: the streams of the slot groups, one behind the other
+    int gain_runs = 0;          // ... synthesis runs its last call took (gal_synth_gain_runs)
+    size_t own_parts_bytes = 0;
 };
 
 // The stream the handle works on: the caller's (gal_synth_set_stream), or one of its own, made at first need.
@@ -549,6 +562,10 @@ int gal_synth_destroy(gal_synth_t *h)
     if (h->own_pin) hipHostFree(h->own_pin);
     if (h->d_iq_sat) hipFree(h->d_iq_sat);
     if (h->d_corr_tab) hipFree(h->d_corr_tab);
+    if (h->own_parts) hipFree(h->own_parts);
+    if (h->d_gain) hipFree(h->d_gain);
+    if (h->h_gain) hipHostFree(h->h_gain);
+    if (h->ev_gain) hipEventDestroy(h->ev_gain);
     if (h->d_lut) hipFree(h->d_lut);
     if (h->d_str) hipFree(h->d_str);
     if (h->h_up) hipHostFree(h->h_up);
@@ -1888,6 +1905,196 @@ int gal_synth_iq_saturated(gal_synth_t *h, uint64_t *n_saturated, int32_t reset)
     return GAL_OK;
 }
 
+
+// ---- per-satellite signal power (iq_gain.hip) --------------------------------------------------------------------------------------
+int gal_synth_gain_q7(double d_m, double elev_rad, const double *pattern_db, double offset_db, uint16_t *out)
+{
+    if (!out) return fail(GAL_E_INVAL, "gal_synth_gain_q7: null argument");
+    bool ok = std::isfinite(d_m) && d_m > 0.0 && std::isfinite(elev_rad) && std::isfinite(offset_db);
+    for (int i = 0; pattern_db && ok && i < GAL_GAIN_PATTERN_LEN; ++i) ok = std::isfinite(pattern_db[i]);
+    if (!ok)
+        return fail(GAL_E_INVAL, "gal_synth_gain_q7: distance %g m (> 0), elevation %g rad, offset %g dB and the pattern must be finite", d_m,
+                    elev_rad, offset_db);
+    *out = (uint16_t)gal_gain_q7_eval(d_m, elev_rad, pattern_db, offset_db);
+    return GAL_OK;
+}
+
+// [x, x + bytes) against the int16 output of the batch in flight (gal_synth_finish may still synthesise it again)
+static bool hits_batch_in_flight(const gal_synth *h, const void *p, size_t bytes)
+{
+    if (!h->in_flight || !h->last_iq) return false;
+    const char *x = (const char *)p, *y = x + bytes;
+    const char *a = (const char *)h->last_iq, *b = a + (size_t)h->range_ne * (size_t)h->P.N * 4;
+    return x < b && a < y;
+}
+
+int gal_synth_iq_wsum(gal_synth_t *h, const int16_t *const *parts_dev, int32_t n_parts, const uint16_t *gain_q7, int32_t n_epochs,
+                      int16_t *out_dev)
+{
+    const char *who = "gal_synth_iq_wsum";
+    if (!h) return fail(GAL_E_INVAL, "null handle");
+    if (!parts_dev || !gain_q7 || n_parts < 1 || n_parts > GAL_ENGINE_MAX_CHAN || n_epochs < 1)
+        return fail(GAL_E_INVAL, "%s: null argument, n_parts %d (1..%d) or n_epochs %d (>= 1)", who, n_parts, GAL_ENGINE_MAX_CHAN, n_epochs);
+    if (!out_dev || ((uintptr_t)out_dev & 15)) return fail(GAL_E_INVAL, "%s: device pointers must be non-null and 16-byte aligned", who);
+    const size_t bytes = (size_t)n_epochs * (size_t)h->cfg.samples_per_epoch * 4;
+    const char *o = (const char *)out_dev, *oe = o + bytes;
+    for (int k = 0; k < n_parts; ++k) {
+        const char *x = (const char *)parts_dev[k];
+        if (!x || ((uintptr_t)x & 15)) return fail(GAL_E_INVAL, "%s: device pointers must be non-null and 16-byte aligned (part %d)", who, k);
+        if (x < oe && o < x + bytes) return fail(GAL_E_INVAL, "%s: part %d and the output overlap", who, k);
+        if (hits_batch_in_flight(h, x, bytes)) return fail(GAL_E_STATE, "%s: input of the batch in flight (call gal_synth_finish first)", who);
+    }
+    if (hits_batch_in_flight(h, out_dev, bytes)) return fail(GAL_E_STATE, "%s: output of the batch in flight (call gal_synth_finish first)", who);
+    uint64_t row_max = 0;  // the largest sum of one epoch's gains: what w needs (iq_gain.hip)
+    for (int e = 0; e < n_epochs; ++e) {
+        uint64_t row = 0;
+        for (int k = 0; k < n_parts; ++k) {
+            const uint16_t g = gain_q7[(size_t)e * n_parts + k];
+            if (g > GAL_GAIN_MAX) return fail(GAL_E_INVAL, "%s: gain %u of epoch %d, part %d (0..%d)", who, g, e, k, GAL_GAIN_MAX);
+            row += g;
+        }
+        row_max = std::max(row_max, row);
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = handle_stream(h);
+    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
+    const int rc = ensure_sat_counter(h, st);
+    if (rc) return rc;
+    // the table of this call: pointers, then gains.  One of each per handle: a call waits for the kernel of the call before it
+    if (!h->ev_gain) HIP_TRY(hipEventCreateWithFlags(&h->ev_gain, hipEventDisableTiming));
+    if (h->gain_pending) {
+        HIP_TRY(hipEventSynchronize(h->ev_gain));
+        h->gain_pending = false;
+    }
+    const size_t o_gain = sizeof(void *) * GAL_ENGINE_MAX_CHAN, need = o_gain + (size_t)n_epochs * n_parts * sizeof(int);
+    if (need > h->gain_bytes) {
+        if (h->h_gain) hipHostFree(h->h_gain);
+        if (h->d_gain) hipFree(h->d_gain);
+        h->h_gain = h->d_gain = nullptr;
+        h->gain_bytes = 0;
+        const size_t cap = need + need / 4;
+        if (hipHostMalloc((void **)&h->h_gain, cap, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&h->d_gain, cap) != hipSuccess) {
+            if (h->h_gain) hipHostFree(h->h_gain);
+            h->h_gain = nullptr;
+            return fail(GAL_E_NOMEM, "%s: the gain table of %zu bytes could not be allocated", who, cap);
+        }
+        h->gain_bytes = cap;
+    }
+    memset(h->h_gain, 0, o_gain);
+    memcpy(h->h_gain, parts_dev, sizeof(void *) * (size_t)n_parts);
+    int *const hg = (int *)(h->h_gain + o_gain);
+    for (size_t i = 0; i < (size_t)n_epochs * n_parts; ++i) hg[i] = gain_q7[i];
+    HIP_TRY(hipMemcpyAsync(h->d_gain, h->h_gain, need, hipMemcpyHostToDevice, st));
+    HIP_TRY(galk_launch_iq_wsum((const int16_t *const *)h->d_gain, (const int *)(h->d_gain + o_gain), n_parts, n_epochs, h->cfg.samples_per_epoch,
+                                row_max > 65535 ? 1 : 0, out_dev, h->d_iq_sat, st));
+    HIP_TRY(hipEventRecord(h->ev_gain, st));
+    h->gain_pending = true;
+    return GAL_OK;
+}
+
+int gal_synth_run_gains(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_epochs, const gal_chan_state_t *state_in,
+                        const uint16_t *gain_q7, int16_t *iq_dev, gal_chan_state_t *state_out)
+{
+    const char *who = "gal_synth_run_gains";
+    if (!h || !params || !gain_q7 || !iq_dev || n_epochs < 1) return fail(GAL_E_INVAL, "%s: null argument or n_epochs %d (>= 1)", who, n_epochs);
+    if ((uintptr_t)iq_dev & 15) return fail(GAL_E_INVAL, "%s: iq_dev must be 16-byte aligned", who);
+    if (h->in_flight) return fail(GAL_E_STATE, "%s while a batch is in flight: call gal_synth_finish first", who);
+    if (h->staged_pending)  // (gal_synth_plan would replace it silently: here the caller has not asked for a plan)
+        return fail(GAL_E_STATE, "%s with a plan of gal_synth_plan_async waiting for its gal_synth_execute", who);
+    const int E = n_epochs, S = h->cfg.n_slots;
+    for (size_t i = 0; i < (size_t)E * S; ++i)
+        if (gain_q7[i] > GAL_GAIN_MAX)
+            return fail(GAL_E_INVAL, "%s: gain %u of epoch %zu, slot %zu (0..%d)", who, gain_q7[i], i / S, i % S, GAL_GAIN_MAX);
+    // Slot groups: the slots of a group have the same gain in every epoch in which they are active, so one run of the existing path
+    // with only those slots active is the part sum_s x_s of the group, and the group's gain of an epoch is that common value (first
+    // fit; a slot that is never active joins no group).  All slots at one gain -- the unity case -- make one group
+    struct Group {
+        std::vector<int> slots;
+        std::vector<int> g;  // [E]; -1: no slot of the group is active in that epoch
+    };
+    std::vector<Group> groups;
+    std::vector<int> group_of(S, -1);
+    for (int s = 0; s < S; ++s) {
+        bool active = false;
+        for (int e = 0; e < E && !active; ++e) active = params[(size_t)e * S + s].prn > 0;
+        if (!active) continue;
+        size_t k = 0;
+        for (; k < groups.size(); ++k) {
+            bool fits = true;
+            for (int e = 0; e < E && fits; ++e)
+                fits = params[(size_t)e * S + s].prn <= 0 || groups[k].g[e] < 0 || groups[k].g[e] == (int)gain_q7[(size_t)e * S + s];
+            if (fits) break;
+        }
+        if (k == groups.size()) {
+            groups.emplace_back();
+            groups[k].g.assign(E, -1);
+        }
+        groups[k].slots.push_back(s);
+        group_of[s] = (int)k;
+        for (int e = 0; e < E; ++e)
+            if (params[(size_t)e * S + s].prn > 0) groups[k].g[e] = gain_q7[(size_t)e * S + s];
+    }
+    const int n_parts = groups.empty() ? 1 : (int)groups.size();  // (an empty sky: one run of nothing)
+    bool unity = n_parts == 1;  // one part at gain 128 wherever it is not zero: y = x, the run goes straight into iq_dev
+    if (!groups.empty())
+        for (int e = 0; e < E && unity; ++e) unity = groups[0].g[e] < 0 || groups[0].g[e] == GAL_GAIN_UNITY;
+    const size_t bytes = (size_t)E * (size_t)h->cfg.samples_per_epoch * 4;
+    // the weighted sum of the call before may still read the scratch buffers: wait for it here, whatever stream the handle is on now
+    // (on one stream the runs below would order behind it by themselves)
+    if (h->gain_pending) {
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(hipEventSynchronize(h->ev_gain));
+        h->gain_pending = false;
+    }
+    h->gain_runs = 0;
+    if (!unity && bytes * (size_t)n_parts > h->own_parts_bytes) {
+        HIP_TRY(hipSetDevice(h->device));
+        if (h->own_parts) hipFree(h->own_parts);
+        h->own_parts = nullptr;
+        h->own_parts_bytes = 0;
+        if (hipMalloc(&h->own_parts, bytes * (size_t)n_parts) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(GAL_E_NOMEM, "%s: %d slot groups of %zu bytes each: hipMalloc of %zu bytes of scratch failed", who, n_parts, bytes,
+                        bytes * (size_t)n_parts);
+        }
+        h->own_parts_bytes = bytes * (size_t)n_parts;
+    }
+    std::vector<gal_chan_epoch_t> one((size_t)E * S);
+    std::vector<gal_chan_state_t> st_k(S), st_all(S);
+    const int16_t *parts[GAL_ENGINE_MAX_CHAN];
+    for (int k = 0; k < n_parts; ++k) {
+        memcpy(one.data(), params, sizeof(gal_chan_epoch_t) * (size_t)E * S);
+        for (int e = 0; e < E; ++e)
+            for (int s = 0; s < S; ++s)
+                if (group_of[s] != k) one[(size_t)e * S + s].prn = 0;
+        int16_t *dst = unity ? iq_dev : (int16_t *)((char *)h->own_parts + bytes * (size_t)k);
+        parts[k] = dst;
+        int rc = gal_synth_plan(h, one.data(), E, state_in);
+        if (rc == GAL_OK) rc = gal_synth_execute(h, dst);
+        if (rc == GAL_OK) rc = gal_synth_finish_n(h, st_k.data(), nullptr, 0);
+        if (rc != GAL_OK) return rc;
+        h->gain_runs += 1;
+        // the end state of a slot is that of its own run; a slot that is never active is idle in every run (the first one's record)
+        for (int s = 0; s < S; ++s)
+            if (group_of[s] == k || (k == 0 && group_of[s] < 0)) st_all[s] = st_k[s];
+    }
+    if (!unity) {
+        std::vector<uint16_t> gp((size_t)E * n_parts);
+        for (int e = 0; e < E; ++e)
+            for (int k = 0; k < n_parts; ++k) gp[(size_t)e * n_parts + k] = (uint16_t)(groups[k].g[e] < 0 ? 0 : groups[k].g[e]);
+        const int rc = gal_synth_iq_wsum(h, parts, n_parts, gp.data(), E, iq_dev);
+        if (rc != GAL_OK) return rc;
+    }
+    if (state_out) memcpy(state_out, st_all.data(), sizeof(gal_chan_state_t) * S);
+    return GAL_OK;
+}
+
+int gal_synth_gain_runs(const gal_synth_t *h, int32_t *n_runs)
+{
+    if (!h || !n_runs) return fail(GAL_E_INVAL, "gal_synth_gain_runs: null argument");
+    *n_runs = h->gain_runs;
+    return GAL_OK;
+}
 
 // ---- correlator bank and C/N0 monitor (iq_corr.hip) --------------------------------------------------------------------------
 static constexpr uint64_t kCorrL = (uint64_t)(2 * GAL_CODE_LEN) << 32;  // one code period: 8184 half chips x 2^32

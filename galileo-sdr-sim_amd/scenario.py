@@ -6,7 +6,9 @@ import os
 
 import numpy as np
 
-from .synth import CHAN_EPOCH_DTYPE, GAL_PAGE_WORDS
+from .synth import CHAN_EPOCH_DTYPE, GAL_GAIN_PATTERN_LEN, GAL_PAGE_WORDS
+
+GAL_NUM_PRN = 50
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG_DIR, "libgalscen.so")
@@ -17,6 +19,9 @@ EXPORTED_SYMBOLS = (
     "gal_scen_total_epochs",
     "gal_scen_start_time",
     "gal_scen_next",
+    "gal_scen_set_power",
+    "gal_scen_set_path_loss",
+    "gal_scen_next_gains",
     "gal_scen_close",
     "gal_scen_inav_page",
     "gal_scen_inav_raw",
@@ -68,6 +73,9 @@ def load_library():
         lib.gal_scen_total_epochs.argtypes = [vp]
         lib.gal_scen_start_time.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)]
         lib.gal_scen_next.argtypes = [vp, ctypes.c_int32, vp]
+        lib.gal_scen_set_power.argtypes = [vp, vp, vp]
+        lib.gal_scen_set_path_loss.argtypes = [vp, ctypes.c_int32]
+        lib.gal_scen_next_gains.argtypes = [vp, ctypes.c_int32, vp, vp]
         lib.gal_scen_close.argtypes = [vp]
         lib.gal_scen_eph_gaps.argtypes = [vp]
         lib.gal_scen_live_rejected.argtypes = [vp]
@@ -151,6 +159,42 @@ class Scenario:
         if n < 0:
             raise GalScenError(n, self._lib.gal_scen_last_error().decode())
         return rows[:n]
+
+    def set_power(self, pattern_db=None, prn_offset_db=None, path_loss=True):
+        """gal_scen_set_power / gal_scen_set_path_loss: the antenna pattern (37 attenuations in dB, one per 5 degrees off the zenith;
+        None: isotropic), the per-PRN offsets in dB (50 values, or a dict {prn: dB}; None: none) and whether the distance counts, for
+        the gains next_gains() returns from here on."""
+        pat = off = None
+        if pattern_db is not None:
+            pat = np.ascontiguousarray(pattern_db, dtype=np.float64)
+            if pat.shape != (GAL_GAIN_PATTERN_LEN,):
+                raise ValueError("set_power: pattern_db must hold %d values" % GAL_GAIN_PATTERN_LEN)
+        if prn_offset_db is not None:
+            if isinstance(prn_offset_db, dict):
+                off = np.zeros(GAL_NUM_PRN, dtype=np.float64)
+                for prn, db in prn_offset_db.items():
+                    if not 1 <= int(prn) <= GAL_NUM_PRN:
+                        raise ValueError("set_power: PRN %r outside 1..%d" % (prn, GAL_NUM_PRN))
+                    off[int(prn) - 1] = float(db)
+            else:
+                off = np.ascontiguousarray(prn_offset_db, dtype=np.float64)
+                if off.shape != (GAL_NUM_PRN,):
+                    raise ValueError("set_power: prn_offset_db must hold %d values" % GAL_NUM_PRN)
+        rc = self._lib.gal_scen_set_power(self._h, pat.ctypes.data if pat is not None else None, off.ctypes.data if off is not None else None)
+        if rc == 0:
+            rc = self._lib.gal_scen_set_path_loss(self._h, 1 if path_loss else 0)
+        if rc != 0:
+            raise GalScenError(rc, self._lib.gal_scen_last_error().decode())
+
+    def next_gains(self, max_epochs):
+        """gal_scen_next_gains: (rows, gain_q7) -- the rows of next() and, per row and slot, the Q7 gain (uint16, 128 = unity, 0 on idle
+        slots) for SynthEngine.run_gains."""
+        rows = np.zeros((max_epochs, self.n_slots), dtype=CHAN_EPOCH_DTYPE)
+        gains = np.zeros((max_epochs, self.n_slots), dtype=np.uint16)
+        n = self._lib.gal_scen_next_gains(self._h, int(max_epochs), rows.ctypes.data, gains.ctypes.data)
+        if n < 0:
+            raise GalScenError(n, self._lib.gal_scen_last_error().decode())
+        return rows[:n], gains[:n]
 
     def all(self):
         return self.next(self.total_epochs)

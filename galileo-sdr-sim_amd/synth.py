@@ -29,6 +29,11 @@ IQ_FORMATS = {"ishort": GAL_IQ_ISHORT, "ibyte": GAL_IQ_IBYTE, "ibit": GAL_IQ_IBI
 IQ_SHIFT_DEFAULT = 5  # ibyte: the CLI's default --iq-shift
 GAL_PAGE_WORDS = 16
 GAL_N_SYM_PAGE = 500
+# per-satellite signal power (gal_synth_run_gains): Q7 gains in a uint16, 128 = unity
+GAL_GAIN_UNITY = 128
+GAL_GAIN_MAX = 32767
+GAL_GAIN_PATTERN_LEN = 37
+GAL_ENGINE_MAX_CHAN = 64
 
 # gal_chan_epoch_t (176 bytes)
 CHAN_EPOCH_DTYPE = np.dtype(
@@ -171,6 +176,10 @@ EXPORTED_SYMBOLS = (
     "gal_synth_noise_from_cn0",
     "gal_synth_iq_convert_interf",
     "gal_synth_interf_make",
+    "gal_synth_iq_wsum",
+    "gal_synth_run_gains",
+    "gal_synth_gain_runs",
+    "gal_synth_gain_q7",
     "gal_synth_corr_out_bytes",
     "gal_synth_correlate",
     "gal_tables_e1b",
@@ -239,6 +248,14 @@ def load_library(hooks=False):
     lib.gal_synth_iq_convert_interf.restype = ctypes.c_int
     lib.gal_synth_interf_make.argtypes = [ctypes.c_double] * 8 + [ctypes.POINTER(_Interf)]
     lib.gal_synth_interf_make.restype = ctypes.c_int
+    lib.gal_synth_iq_wsum.argtypes = [vp, ctypes.POINTER(vp), i32, vp, i32, vp]
+    lib.gal_synth_iq_wsum.restype = ctypes.c_int
+    lib.gal_synth_run_gains.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    lib.gal_synth_run_gains.restype = ctypes.c_int
+    lib.gal_synth_gain_runs.argtypes = [vp, ctypes.POINTER(i32)]
+    lib.gal_synth_gain_runs.restype = ctypes.c_int
+    lib.gal_synth_gain_q7.argtypes = [ctypes.c_double, ctypes.c_double, vp, ctypes.c_double, ctypes.POINTER(ctypes.c_uint16)]
+    lib.gal_synth_gain_q7.restype = ctypes.c_int
     lib.gal_synth_corr_out_bytes.argtypes = [ctypes.POINTER(_CorrReq)]
     lib.gal_synth_corr_out_bytes.restype = ctypes.c_size_t
     lib.gal_synth_correlate.argtypes = [vp, vp, i32, ctypes.c_size_t, ctypes.POINTER(_CorrReq), i32, vp]
@@ -320,6 +337,23 @@ def _interf_struct(src):
     if "amp_q4" not in src:
         raise ValueError("interference source: amp_q4 is required")
     return _Interf(**{k: int(d[k]) for k in INTERF_FIELDS})
+
+
+def gain_q7(d_m, elev_rad, pattern_db=None, offset_db=0.0):
+    """gal_synth_gain_q7 (no GPU needed): the Q7 gain (128 = unity) of a satellite at the geometric distance d_m [m] and the elevation
+    elev_rad -- path loss against Galileo's nominal altitude, the attenuation pattern_db[(int)((90 - elev) / 5)] (37 values in dB, one
+    per 5 degrees off the zenith; None: isotropic) and an offset in dB; truncated, at most 32767."""
+    lib = load_library()
+    pat = None
+    if pattern_db is not None:
+        pat = np.ascontiguousarray(pattern_db, dtype=np.float64)
+        if pat.shape != (GAL_GAIN_PATTERN_LEN,):
+            raise ValueError("gain_q7: pattern_db must hold %d values" % GAL_GAIN_PATTERN_LEN)
+    g = ctypes.c_uint16(0)
+    rc = lib.gal_synth_gain_q7(float(d_m), float(elev_rad), pat.ctypes.data if pat is not None else None, float(offset_db), ctypes.byref(g))
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+    return int(g.value)
 
 
 def _corr_struct(req):
@@ -529,6 +563,43 @@ class SynthEngine:
         """Waits for the conversions enqueued so far; int16 values saturated by "ibyte" conversions since create (or the last reset)."""
         n = ctypes.c_uint64(0)
         self._check(self._lib.gal_synth_iq_saturated(self._h, ctypes.byref(n), 1 if reset else 0))
+        return int(n.value)
+
+    def iq_wsum(self, part_ptrs, gain_q7, out_ptr):
+        """gal_synth_iq_wsum, enqueued on the handle's stream: out = clamp((sum_k gain_q7[e, k] x part k + 64) >> 7) per epoch e, for the
+        device addresses part_ptrs (n_epochs x samples_per_epoch complex int16 samples each, 16-byte aligned, none overlapping out_ptr)
+        and gain_q7 of shape [n_epochs, n_parts] (0 .. GAL_GAIN_MAX).  iq_saturated() is the fence and counts the clamped values."""
+        g = np.asarray(gain_q7)
+        if g.ndim != 2 or g.shape[1] != len(part_ptrs):
+            raise ValueError("iq_wsum: gain_q7 must have shape [n_epochs, n_parts=%d]" % len(part_ptrs))
+        if g.size and (g.min() < 0 or g.max() > 65535):
+            raise ValueError("iq_wsum: a gain does not fit a uint16")
+        g = np.ascontiguousarray(g, dtype=np.uint16)
+        ptrs = (ctypes.c_void_p * max(1, len(part_ptrs)))(*[int(p) for p in part_ptrs])
+        self._check(self._lib.gal_synth_iq_wsum(self._h, ptrs, len(part_ptrs), g.ctypes.data, g.shape[0], ctypes.c_void_p(int(out_ptr))))
+
+    def run_gains(self, params, gain_q7, iq_dev_ptr, state_in=None):
+        """gal_synth_run_gains: the batch with per-slot, per-epoch Q7 gains gain_q7 [n_epochs, n_slots] (128 = unity) into the device
+        address iq_dev_ptr (16-byte aligned) -- one synthesis run per group of slots with equal gains, then the weighted sum, which is
+        ENQUEUED when this returns (iq_saturated() is the fence).  Returns state_out: per slot the end state of the full run."""
+        p = self._params(params)
+        s = self._state(state_in)
+        g = np.asarray(gain_q7)
+        if g.shape != p.shape:
+            raise ValueError("run_gains: gain_q7 must have shape [n_epochs, n_slots=%d]" % self.n_slots)
+        if g.size and (g.min() < 0 or g.max() > 65535):
+            raise ValueError("run_gains: a gain does not fit a uint16")
+        g = np.ascontiguousarray(g, dtype=np.uint16)
+        st = np.zeros(self.n_slots, dtype=CHAN_STATE_DTYPE)
+        self._check(self._lib.gal_synth_run_gains(self._h, p.ctypes.data, p.shape[0], s.ctypes.data if s is not None else None, g.ctypes.data,
+                                                  ctypes.c_void_p(int(iq_dev_ptr)), st.ctypes.data))
+        self.n_epochs = p.shape[0]
+        return st
+
+    def gain_runs(self):
+        """gal_synth_gain_runs: synthesis runs (slot groups) the last run_gains took; 1 for the unity case."""
+        n = ctypes.c_int32(0)
+        self._check(self._lib.gal_synth_gain_runs(self._h, ctypes.byref(n)))
         return int(n.value)
 
     def correlate(self, buf_ptr, fmt, n_samples, reqs, out_ptr=None):

@@ -66,6 +66,16 @@ int gal_scen_start_time(const gal_scen_t *s, int32_t *week, double *sec);
 /* Produce up to max_epochs further rows of n_slots records into `rows`; returns the number produced
  * (0 at the end) or a negative gal_status_t. */
 int32_t gal_scen_next(gal_scen_t *s, int32_t max_epochs, gal_chan_epoch_t *rows);
+/* Per-satellite signal power (opt-in; include/galsynth.h: gal_synth_run_gains).  gal_scen_set_power, called after open and before the
+ * rows it is to hold for: pattern_db = GAL_GAIN_PATTERN_LEN (37) attenuations in dB, one per 5 degrees off boresight (the zenith), or
+ * NULL: isotropic; prn_offset_db = GAL_NUM_PRN (50) offsets in dB, entry prn - 1, or NULL: none.  Both are copied.
+ * gal_scen_set_path_loss(0) takes the distance out of the gain (every satellite at the reference distance); the default is on.
+ * gal_scen_next_gains is gal_scen_next -- the same rows, the same progress through the scenario -- and fills gain_q7[e * n_slots + s]
+ * with gal_synth_gain_q7 of the geometric distance and the elevation the row's range computation has found (src/galileo-sdr.cpp:
+ * 469-477); idle slots get 0.  GAL_E_INVAL for a null pointer or a value that is not finite. */
+int gal_scen_set_power(gal_scen_t *s, const double *pattern_db, const double *prn_offset_db);
+int gal_scen_set_path_loss(gal_scen_t *s, int32_t enable);
+int32_t gal_scen_next_gains(gal_scen_t *s, int32_t max_epochs, gal_chan_epoch_t *rows, uint16_t *gain_q7);
 int gal_scen_close(gal_scen_t *s);
 /* (satellite, refresh) pairs so far at which a channel kept a stale ephemeris record (strict_eph == 0), and position
  * datagrams dropped because a coordinate was not finite or out of range. */

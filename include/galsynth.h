@@ -373,6 +373,66 @@ int gal_synth_interf_make(double js_db, double gain, double sample_rate, double 
                           double pulse_period_s, double pulse_on_s, gal_iq_interf_t *out);
 
 /*
+ * Per-satellite signal power (opt-in; the reference computes a gain per channel and epoch, src/galileo-sdr.cpp:469-477, and leaves it
+ * commented out in its loop, :520-521: without these calls every satellite leaves the engine at the carrier-table amplitude of 250 and
+ * every byte is the reference's).  Like the formats it is a FIXED INTEGER FUNCTION of its inputs (tests/gain_model.py states it in
+ * numpy).
+ *
+ * x_s[j] = the interleaved int16 stream the engine writes for a batch when only the records of slot s are active (every other slot
+ * with prn = 0; the carrier state of slot s as in the full run).  The engine's plain output is exactly sum_s x_s[j]: the accumulation
+ * is in integers and stays inside int16.  g[e][s] = the gain of slot s in epoch e, Q7 in a uint16, 0 .. GAL_GAIN_MAX, GAL_GAIN_UNITY
+ * = 128 = 1.0 (the reference's "scaled by 2^7"), constant within an epoch like everything else the loop reads.  With
+ * e(j) = (j / 2) / samples_per_epoch:
+ *   w[j] = sum_s int32(g[e(j)][s]) x_s[j]
+ *   y[j] = clamp((w[j] + 64) >> 7, -32768, 32767)          (arithmetic shift: round to nearest, ties up)
+ * A value the clamp changes counts once in the handle's saturation counter (gal_synth_iq_saturated).  All gains 128: y = x, the
+ * reference's bytes.  y then takes noise, interference and the formats unchanged; gal_synth_noise_from_cn0 and gal_synth_interf_make
+ * keep their meaning for a satellite at unity gain, and a satellite at gain g sits 20 log10(g / 128) dB from it.
+ * w fits an int32: one slot contributes |x_s| <= 500 (BOC(1,1): v = E1B d - E1C s is 0 or +-2, times a table entry of at most 250;
+ * CBOC: one of the two terms is 0 and the other +-2 x at most lround(sqrt(10/11) 250) = 238), so for GAL_ENGINE_MAX_CHAN = 64 slots at
+ * GAL_GAIN_MAX |w| + 64 <= 64 x 32767 x 500 + 64 = 1 048 544 064 < 2^31.  (gal_synth_iq_wsum takes ANY int16 streams: where an
+ * epoch's gains sum to more than 65535 it forms w in 64 bits, so the definition holds for them without a wrap.)
+ */
+#define GAL_GAIN_UNITY 128
+#define GAL_GAIN_MAX 32767
+#define GAL_GAIN_PATTERN_LEN 37 /* antenna pattern: one attenuation in dB per 5 degrees off boresight, 0 .. 180 */
+/* Enqueue on the handle's stream: the weighted sum y of the n_parts (1 .. GAL_ENGINE_MAX_CHAN) streams parts_dev[k] -- DEVICE memory,
+ * n_epochs x samples_per_epoch complex int16 samples each -- with the gains gain_q7[e * n_parts + k] (HOST memory, copied before the
+ * call returns, as is the pointer array) into out_dev.  The rules of gal_synth_iq_convert: 16-byte alignment, an out_dev that overlaps
+ * any part is refused (parts may overlap each other), GAL_E_STATE for a buffer of the batch in flight, gal_synth_iq_saturated is the
+ * fence and the counter.  A handle holds one gain table: a call waits (on the host) for the kernel of the call before it.
+ * GAL_E_INVAL for a null handle or pointer, a misaligned pointer, n_parts outside 1..GAL_ENGINE_MAX_CHAN, n_epochs < 1, a gain above
+ * GAL_GAIN_MAX, an overlap; GAL_E_NOMEM if the table cannot be had. */
+int gal_synth_iq_wsum(gal_synth_t *h, const int16_t *const *parts_dev, int32_t n_parts, const uint16_t *gain_q7, int32_t n_epochs,
+                      int16_t *out_dev);
+/* The batch of gal_synth_plan(params, n_epochs, state_in) with the gains gain_q7[e * n_slots + s] (HOST) into iq_dev (DEVICE, 16-byte
+ * aligned, n_epochs x samples_per_epoch x 4 bytes).  Built from what exists: the slots are put into groups of equal gain (the same
+ * gain in every epoch in which they are active); every group is run through gal_synth_plan / _execute / _finish with the other slots
+ * idle, into scratch buffers the handle owns (they grow on demand and are freed by gal_synth_destroy), and gal_synth_iq_wsum is
+ * enqueued behind the last one: the synthesis kernels see nothing of the gains, and the batch costs one synthesis run per distinct
+ * gain column.  One group at unity -- all gains 128 -- is one run straight into iq_dev.  When the call returns the runs are finished
+ * and the sum is ENQUEUED: gal_synth_iq_saturated, or any work on the handle's stream, orders behind it.
+ * state_out (host, n_slots entries, may be NULL): for every slot the end state of its own run -- the state of the full run; a gain of
+ * 0 still advances it.  state_in may be NULL as for gal_synth_plan.
+ * GAL_E_STATE with a batch in flight, or with a plan of gal_synth_plan_async that still waits for its gal_synth_execute (gal_synth_plan
+ * would replace such a plan; this call refuses it); GAL_E_INVAL for a null handle, params, gain_q7 or iq_dev, a misaligned iq_dev, a gain above
+ * GAL_GAIN_MAX, n_epochs < 1 and whatever gal_synth_plan refuses; GAL_E_NOMEM, with the sizes in the text, if the scratch buffers
+ * cannot be had. */
+int gal_synth_run_gains(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_epochs, const gal_chan_state_t *state_in,
+                        const uint16_t *gain_q7, int16_t *iq_dev, gal_chan_state_t *state_out);
+/* Synthesis runs (slot groups) the last gal_synth_run_gains of the handle took: 1 for the unity case or an empty sky, otherwise the
+ * number of parts of its weighted sum; 0 before the first call.  GAL_E_INVAL for a null pointer. */
+int gal_synth_gain_runs(const gal_synth_t *h, int32_t *n_runs);
+/* The gain of one satellite in one epoch; host only, needs no GPU.  d_m = geometric distance in metres, elev_rad = elevation,
+ * pattern_db = GAL_GAIN_PATTERN_LEN attenuations in dB, one per 5 degrees off boresight (boresight = the zenith), or NULL: isotropic.
+ *   ibs  = (int)((90 - elev_rad x 57.2957795131) / 5) clamped to 0 .. 36
+ *   *out = min(32767, (int)(128 x (23222000.0 / d_m) x 10^(-pattern_db[ibs] / 20) x 10^(offset_db / 20)))
+ * evaluated in double from left to right; the truncation is the reference's (src/galileo-sdr.cpp:469-477).  The reference distance
+ * is Galileo's nominal altitude, so a satellite at the zenith is about unity (the reference's 20 200 km is the GPS altitude).
+ * GAL_E_INVAL for a null `out`, an argument or pattern value that is not finite, d_m <= 0. */
+int gal_synth_gain_q7(double d_m, double elev_rad, const double *pattern_db, double offset_db, uint16_t *out);
+
+/*
  * Correlator bank and C/N0 monitor (not in the reference): despread a device buffer of output IQ with the engine's own replica of one
  * satellite and get, per code period, delay and Doppler bin, the complex correlation sums of the E1B and the E1C component.  Read-only
  * on the buffer, in any of the three formats.  Like the formats and the noise floor it is a FIXED INTEGER FUNCTION of its inputs: the
