@@ -21,6 +21,9 @@
 // per-PRN offsets -- as Q7 gains from the front-end (gal_scen_next_gains), applied by gal_synth_run_gains in front of noise,
 // interference and the format.  Without the three options every byte is the reference's.
 //
+// --fir <file> | --fir-lowpass cutoff_hz[,n_taps] (not in the reference): a front-end (IF) FIR filter over the int16 stream, behind noise
+// and interference and in front of the format (gal_synth_iq_fir); the file does not depend on -B.
+//
 // --monitor <file> (not in the reference): the built-in receiver check -- every --monitor-every'th epoch (default 10) the first 25 code
 // periods of every active channel are despread, in the buffer as it is written (behind noise and format), with the planned replica
 // (gal_synth_correlate); one CSV line per (epoch, PRN) with the measured C/N0 and where the peak lies.  Read-only: the IQ is the same.
@@ -111,6 +114,10 @@ void usage(const char *prog)
            "                   about unity); --cn0 and --jam then hold for a satellite at unity gain\n"
            "  --antenna <file> Receiver antenna pattern: 37 attenuations in dB, one per 5 degrees off the zenith (default: isotropic)\n"
            "  --prn-power <l>  Per-PRN power offsets prn:dB[,prn:dB...], e.g. 5:-6,12:3 (PRN 1..50, -60..60 dB)\n"
+           "  --fir <file>     Front-end FIR filter over the stream, behind noise / interference and in front of the format: integer\n"
+           "                   taps in Q14 (16384 = 1.0), one per line, 1..128 of them, sum of |tap| <= 65535\n"
+           "  --fir-lowpass <cutoff_hz>[,n_taps] the same with a Hamming-windowed sinc low-pass (n_taps odd, 3..127, default 63; the taps\n"
+           "                   are printed on stderr); not together with --fir\n"
            "  --monitor <file> Despread the output with the planned replicas and write one CSV line per monitored epoch and PRN:\n"
            "                   time, PRN, planned Doppler, measured C/N0 (composite E1B + E1C), peak ratio, strongest of the delays\n"
            "                   -1 / 0 / +1 half chip and of the Doppler offsets -1 / 0 / +1 bin of 250 Hz; a summary per PRN on stderr\n"
@@ -628,6 +635,7 @@ int main(int argc, char *argv[])
     int batch_epochs = 128, n_writers = -1, sites_gpus = 0, sites_per_gpu = 1;
     const char *iq_format_arg = "ishort", *iq_shift_arg = nullptr;
     const char *monitor_arg = nullptr, *monitor_every_arg = nullptr;
+    const char *fir_arg = nullptr, *fir_lowpass_arg = nullptr;
     bool power_model = false;
     const char *antenna_arg = nullptr;
     std::vector<const char *> prn_power_args;
@@ -637,7 +645,7 @@ int main(int argc, char *argv[])
     sc.udp_loopback = 1;              // ... on every interface; the default listener here takes local datagrams only
 
     enum { OPT_STRICT = 1000, OPT_SITES, OPT_WRITERS, OPT_GPUS, OPT_PER_GPU, OPT_EXACT, OPT_SHIFT_TOE, OPT_REF_T, OPT_IQ_FORMAT, OPT_IQ_SHIFT, OPT_CN0, OPT_NOISE_SEED,
-           OPT_NOISE_STREAM, OPT_SIGNAL_GAIN, OPT_MONITOR, OPT_MONITOR_EVERY, OPT_JAM, OPT_POWER_MODEL, OPT_ANTENNA, OPT_PRN_POWER };
+           OPT_NOISE_STREAM, OPT_SIGNAL_GAIN, OPT_MONITOR, OPT_MONITOR_EVERY, OPT_JAM, OPT_POWER_MODEL, OPT_ANTENNA, OPT_PRN_POWER, OPT_FIR, OPT_FIR_LOWPASS };
     static const struct option long_opts[] = {{"strict", no_argument, nullptr, OPT_STRICT},
                                               {"exact-replay", no_argument, nullptr, OPT_EXACT},
                                               {"shift-toe", no_argument, nullptr, OPT_SHIFT_TOE},
@@ -658,6 +666,8 @@ int main(int argc, char *argv[])
                                               {"power-model", no_argument, nullptr, OPT_POWER_MODEL},
                                               {"antenna", required_argument, nullptr, OPT_ANTENNA},
                                               {"prn-power", required_argument, nullptr, OPT_PRN_POWER},
+                                              {"fir", required_argument, nullptr, OPT_FIR},
+                                              {"fir-lowpass", required_argument, nullptr, OPT_FIR_LOWPASS},
                                               {nullptr, 0, nullptr, 0}};
     std::vector<std::string> child_args;  // --sites: everything but -l / -o / --sites / --gpus / --per-gpu / --noise-stream goes to the children
     int opt;
@@ -667,7 +677,7 @@ int main(int argc, char *argv[])
                 child_args.push_back(opt == OPT_STRICT ? "--strict" : opt == OPT_EXACT ? "--exact-replay" : opt == OPT_SHIFT_TOE ? "--shift-toe" : opt == OPT_REF_T ? "--ref-T"
                                      : opt == OPT_IQ_FORMAT ? "--iq-format" : opt == OPT_IQ_SHIFT ? "--iq-shift" : opt == OPT_CN0 ? "--cn0"
                                      : opt == OPT_NOISE_SEED ? "--noise-seed" : opt == OPT_SIGNAL_GAIN ? "--signal-gain" : opt == OPT_MONITOR_EVERY ? "--monitor-every" : opt == OPT_JAM ? "--jam" : opt == OPT_POWER_MODEL ? "--power-model"
-                                     : opt == OPT_ANTENNA ? "--antenna" : opt == OPT_PRN_POWER ? "--prn-power" : "--writers");
+                                     : opt == OPT_ANTENNA ? "--antenna" : opt == OPT_PRN_POWER ? "--prn-power" : opt == OPT_FIR ? "--fir" : opt == OPT_FIR_LOWPASS ? "--fir-lowpass" : "--writers");
             } else {
                 char name[3] = {'-', (char)opt, 0};
                 child_args.push_back(name);
@@ -731,6 +741,8 @@ int main(int argc, char *argv[])
         case OPT_POWER_MODEL: power_model = true; break;
         case OPT_ANTENNA: antenna_arg = optarg; break;
         case OPT_PRN_POWER: prn_power_args.push_back(optarg); break;
+        case OPT_FIR: fir_arg = optarg; break;
+        case OPT_FIR_LOWPASS: fir_lowpass_arg = optarg; break;
         case 'n': case 'g': case 'G': case 'a': case 'p': case 'i': case 'U': case 'b': break;
         case ':':
         case '?':
@@ -974,6 +986,77 @@ int main(int argc, char *argv[])
             fprintf(monitor_fp, "time_s,prn,doppler_hz,cn0_dbhz,peak_ratio,best_delay_halfchips,best_doppler_bins\n");
         }
     }
+    // front-end filter: checked here too, before any device work.  Without --fir / --fir-lowpass nothing below differs from a build
+    // without them.
+    int16_t fir_taps[GAL_FIR_MAX_TAPS];
+    int n_fir = 0;
+    if (fir_arg && fir_lowpass_arg) {
+        fprintf(stderr, "ERROR: --fir and --fir-lowpass exclude each other.\n");
+        exit(1);
+    }
+    if (fir_arg) {
+        FILE *fp = fopen(fir_arg, "r");
+        if (!fp) {
+            fprintf(stderr, "ERROR: cannot read the tap file %s.\n", fir_arg);
+            exit(1);
+        }
+        char line[256];
+        int lineno = 0;
+        while (fgets(line, sizeof(line), fp)) {
+            ++lineno;
+            char *b = line, *end = nullptr;
+            while (*b == ' ' || *b == '\t') ++b;
+            if (*b == '\n' || *b == '\r' || *b == 0) continue;  // an empty line
+            errno = 0;
+            const long v = strtol(b, &end, 10);
+            while (*end == ' ' || *end == '\t' || *end == '\r' || *end == '\n') ++end;
+            if (end == b || *end || errno || v < -32768 || v > 32767) {
+                fprintf(stderr, "ERROR: --fir %s, line %d: not an integer tap in -32768..32767 (Q14: 16384 = 1.0).\n", fir_arg, lineno);
+                exit(1);
+            }
+            if (n_fir == GAL_FIR_MAX_TAPS) {
+                fprintf(stderr, "ERROR: --fir %s holds more than %d taps.\n", fir_arg, GAL_FIR_MAX_TAPS);
+                exit(1);
+            }
+            fir_taps[n_fir++] = (int16_t)v;
+        }
+        fclose(fp);
+        if (n_fir == 0) {
+            fprintf(stderr, "ERROR: --fir %s holds no tap.\n", fir_arg);
+            exit(1);
+        }
+        if (gal_synth_fir_check(fir_taps, n_fir) != GAL_OK) {
+            fprintf(stderr, "ERROR: --fir %s: %s\n", fir_arg, gal_synth_last_error());
+            exit(1);
+        }
+    }
+    if (fir_lowpass_arg) {
+        char *end = nullptr;
+        const double fc = strtod(fir_lowpass_arg, &end);
+        long nt = 63;
+        bool ok = *fir_lowpass_arg && end != fir_lowpass_arg;
+        if (ok && *end == ',') {
+            const char *b = end + 1;
+            nt = strtol(b, &end, 10);
+            ok = *b && end != b && nt >= 0 && nt <= 1000;
+        }
+        if (!ok || *end) {
+            fprintf(stderr, "ERROR: --fir-lowpass '%s' is not cutoff_hz[,n_taps].\n", fir_lowpass_arg);
+            exit(1);
+        }
+        if (gal_synth_fir_lowpass(fc, kSampleRate, (int32_t)nt, fir_taps) != GAL_OK) {
+            fprintf(stderr, "ERROR: --fir-lowpass %s: %s\n", fir_lowpass_arg, gal_synth_last_error());
+            exit(1);
+        }
+        n_fir = (int)nt;
+        if (!sitesfile[0]) {
+            fprintf(stderr, "Front-end filter: low-pass, cutoff %g Hz, %d taps (Q14):", fc, n_fir);
+            for (int k = 0; k < n_fir; ++k) fprintf(stderr, " %d", fir_taps[k]);
+            fprintf(stderr, "\n");
+        }
+    }
+    const bool fir_on = n_fir > 0;
+    const int fir_delay = fir_on ? (n_fir - 1) / 2 : 0;  // of a symmetric filter, in samples: what --monitor follows
     const double iq_bytes_per_sample = (double)gal_synth_iq_bytes(iq_format, 4) / 4.0;
     if (sitesfile[0]) {
         // several listeners cannot share a port: the sites run without the position listener unless -P names a base port, in
@@ -1065,11 +1148,17 @@ int main(int argc, char *argv[])
         exit(1);
     }
     stage("gal_synth_create");
+    if (fir_on && gal_synth_fir_set(eng, fir_taps, n_fir) != GAL_OK) {
+        fprintf(stderr, "ERROR: %s\n", gal_synth_last_error());
+        exit(1);
+    }
     if (batch_epochs > total) batch_epochs = total > 0 ? total : 1;
     const size_t batch_bytes = epoch_bytes * batch_epochs;  // in the output format
     // d_iq: the engine's int16 output; d_out: what the copies read -- d_iq itself for ishort (with --cn0: after the noise pass has
     // run in place), the converted batch otherwise
+    // --fir: d_fir holds the filtered int16 batch, which then is what the format conversion (ishort: the copies) reads
     int16_t *d_iq[2] = {nullptr, nullptr};
+    int16_t *d_fir[2] = {nullptr, nullptr};
     void *d_out[2] = {nullptr, nullptr};
     hipEvent_t converted[2] = {nullptr, nullptr};
     Slot slot[2];
@@ -1080,11 +1169,18 @@ int main(int argc, char *argv[])
             exit(1);
         }
         d_out[i] = d_iq[i];
+        if (fir_on) {
+            if (hipMalloc((void **)&d_fir[i], (size_t)cfg.samples_per_epoch * 4 * batch_epochs) != hipSuccess) {
+                fprintf(stderr, "ERROR: buffer allocation failed\n");
+                exit(1);
+            }
+            d_out[i] = d_fir[i];
+        }
         if (iq_format != GAL_IQ_ISHORT && hipMalloc(&d_out[i], batch_bytes) != hipSuccess) {
             fprintf(stderr, "ERROR: buffer allocation failed\n");
             exit(1);
         }
-        if ((iq_format != GAL_IQ_ISHORT || mix_on || power_on) && hipEventCreateWithFlags(&converted[i], hipEventDisableTiming) != hipSuccess) {
+        if ((iq_format != GAL_IQ_ISHORT || mix_on || power_on || fir_on) && hipEventCreateWithFlags(&converted[i], hipEventDisableTiming) != hipSuccess) {
             fprintf(stderr, "ERROR: buffer allocation failed\n");
             exit(1);
         }
@@ -1249,12 +1345,16 @@ int main(int argc, char *argv[])
             for (int e = 0; e < n; ++e) {
                 if ((emitted + e) % monitor_every) continue;
                 const size_t ob = gal_synth_iq_bytes(iq_format, (size_t)e * cfg.samples_per_epoch);
-                const int skip = iq_format == GAL_IQ_IBIT ? (int)((16 - ob % 16) % 16) * 4 : 0;
+                int skip = iq_format == GAL_IQ_IBIT ? (int)((16 - ob % 16) % 16) * 4 : 0;
+                if (fir_on && skip < fir_delay) {  // the filtered stream lags by fir_delay: start there or later, on the same 16-byte grid
+                    const int g = iq_format == GAL_IQ_IBIT ? 64 : iq_format == GAL_IQ_IBYTE ? 8 : 4;  // samples per 16 bytes
+                    skip += (fir_delay - skip + g - 1) / g * g;
+                }
                 for (int s = 0; s < sc.n_slots; ++s) {
                     const gal_chan_epoch_t &rec = rows_ptr[(size_t)e * sc.n_slots + s];
                     if (rec.prn <= 0) continue;
                     gal_corr_req_t q = mon_shape;
-                    if (gal_corr_from_epoch(&rec, kSampleRate, skip, &q) != GAL_OK) continue;  // (a record the monitor cannot follow)
+                    if (gal_corr_from_epoch(&rec, kSampleRate, skip - fir_delay, &q) != GAL_OK) continue;  // (a record the monitor cannot follow)
                     MonEntry me;
                     me.t = (emitted + e) * 0.1;
                     me.f_carr = rec.f_carr;
@@ -1315,7 +1415,22 @@ int main(int argc, char *argv[])
                     std::chrono::duration<double, std::milli>(tb0 - t_start).count(), n, tb_rows, tb_slot - tb_rows,
                     power_on ? "run_gains (every group's plan + execute + finish, the sum enqueued)" : "plan + execute + finish", tb_synth - tb_slot);
         slot[cur].bytes = epoch_bytes * n;
-        if (iq_format != GAL_IQ_ISHORT || mix_on) {
+        if (fir_on) {
+            // noise / interference into the int16 batch in place, the filter into d_fir[cur], the plain format conversion from there
+            // (ishort: the copies read d_fir[cur] itself); the filter's history runs on from batch to batch inside the handle
+            const size_t n_samples = (size_t)n * cfg.samples_per_epoch;
+            int crc = GAL_OK;
+            if (mix_on)
+                crc = gal_synth_iq_convert_interf(eng, d_iq[cur], n_samples, (uint64_t)emitted * (uint64_t)cfg.samples_per_epoch, &noise, interf, n_jam,
+                                                  GAL_IQ_ISHORT, 0, d_iq[cur]);
+            if (crc == GAL_OK) crc = gal_synth_iq_fir(eng, d_iq[cur], n_samples, d_fir[cur]);
+            if (crc == GAL_OK && iq_format != GAL_IQ_ISHORT) crc = gal_synth_iq_convert(eng, d_fir[cur], n_samples, iq_format, iq_shift, d_out[cur]);
+            if (crc != GAL_OK) {
+                fprintf(stderr, "\nERROR: %s\n", gal_synth_last_error());
+                rc = 1;
+                break;
+            }
+        } else if (iq_format != GAL_IQ_ISHORT || mix_on) {
             // the conversion of the final int16 batch, on the engine's stream; both copy streams wait for it.  With --cn0 the noise
             // goes in in the same pass (ishort: in place in d_iq[cur]); first_sample is the running sample count, so the file does
             // not depend on the batch length
@@ -1329,7 +1444,7 @@ int main(int argc, char *argv[])
                 break;
             }
         }
-        if (iq_format != GAL_IQ_ISHORT || mix_on || power_on) {  // what the copies read is enqueued on the engine's stream: they wait for it
+        if (iq_format != GAL_IQ_ISHORT || mix_on || power_on || fir_on) {  // what the copies read is enqueued on the engine's stream: they wait for it
             if (hipEventRecord(converted[cur], stream) != hipSuccess || hipStreamWaitEvent(copy_stream[0], converted[cur], 0) != hipSuccess ||
                 hipStreamWaitEvent(copy_stream[1], converted[cur], 0) != hipSuccess) {
                 fprintf(stderr, "\nERROR: event after the IQ conversion failed\n");
@@ -1344,7 +1459,7 @@ int main(int argc, char *argv[])
             while (i < mon_epoch.size() && mon_ok) {
                 size_t j = i;
                 while (j < mon_epoch.size() && mon_epoch[j] == mon_epoch[i]) ++j;
-                const size_t ob = gal_synth_iq_bytes(iq_format, (size_t)mon_epoch[i] * cfg.samples_per_epoch) + (size_t)mon_skip[i] / 4;
+                const size_t ob = gal_synth_iq_bytes(iq_format, (size_t)mon_epoch[i] * cfg.samples_per_epoch) + gal_synth_iq_bytes(iq_format, (size_t)mon_skip[i]);
                 mon_ok = gal_synth_correlate(eng, (const char *)d_out[cur] + ob, iq_format, (size_t)cfg.samples_per_epoch - mon_skip[i],
                                              &mon_reqs[2 * i], (int32_t)(2 * (j - i)), (int64_t *)(mon[cur].dev + mon[cur].entries[i].off)) == GAL_OK;
                 i = j;
@@ -1442,7 +1557,7 @@ int main(int argc, char *argv[])
                 fprintf(stderr, "  PRN %2d: gain %5d .. %5d  (%+.2f .. %+.2f dB)\n", prn, prn_gain_lo[prn], prn_gain_hi[prn],
                         prn_gain_lo[prn] > 0 ? 20.0 * log10(prn_gain_lo[prn] / 128.0) : -INFINITY, prn_gain_hi[prn] > 0 ? 20.0 * log10(prn_gain_hi[prn] / 128.0) : -INFINITY);
     }
-    if (iq_format == GAL_IQ_IBYTE || mix_on || power_on) {
+    if (iq_format == GAL_IQ_IBYTE || mix_on || power_on || fir_on) {
         // (stderr: with -o - the data go to stdout)
         uint64_t n_sat = 0;
         const double n_val = (double)emitted * cfg.samples_per_epoch * 2;

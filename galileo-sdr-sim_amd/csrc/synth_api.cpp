@@ -93,6 +93,9 @@ int galk_launch_synth(const DevPlan *P, const DevPlan *Pd, int nch, int accumula
                       const int *nact, uint32_t *iq, int e0, int ne, hipStream_t st);
 hipError_t galk_launch_iq_pass(int format, const int16_t *in, uint64_t n_val, uint64_t first_sample, const gal_iq_noise_t *noise,
                                const gal_iq_interf_t *src, int n_src, int shift, void *out, unsigned long long *sat, hipStream_t st);
+hipError_t galk_launch_iq_fir(const int16_t *in, int16_t *out, uint64_t n, const uint32_t *table_dev, int n_trips, int hs, const uint32_t *hist_in,
+                              uint32_t *hist_out, unsigned long long *sat, hipStream_t st);
+void galk_fir_table(const int16_t *h, int n_taps, uint32_t *table, int *n_trips, int *hs);
 hipError_t galk_launch_iq_wsum(const int16_t *const *parts_dev, const int *gain_dev, int n_parts, int n_epochs, int samples_per_epoch, int wide,
                                int16_t *out, unsigned long long *sat, hipStream_t st);
 hipError_t galk_launch_corr(int format, const void *buf, uint64_t n_eff, uint64_t code_ph0, uint64_t code_dph, uint32_t carr_ph0,
@@ -334,6 +337,14 @@ struct gal_synth {
     void *own_parts = nullptr;  // gal_synth_run_gains: the streams of the slot groups, one behind the other
     int gain_runs = 0;          // ... synthesis runs its last call took (gal_synth_gain_runs)
     size_t own_parts_bytes = 0;
+    // gal_synth_fir_set / gal_synth_iq_fir (iq_fir.hip): the tap-pair table and the two history buffers of kFirHist complex samples, one
+    // device block; h_fir = the pinned copy of the table the upload reads; ev_fir = the last filter kernel of the handle is done
+    uint32_t *d_fir = nullptr;
+    uint32_t *h_fir = nullptr;
+    int fir_taps = 0, fir_trips = 0, fir_hs = 0;  // fir_taps 0: no filter set
+    int fir_cur = 0;                              // the history buffer the next call reads (it writes the other)
+    hipEvent_t ev_fir = nullptr;
+    bool fir_pending = false;
 };
 
 // The stream the handle works on: the caller's (gal_synth_set_stream), or one of its own, made at first need.
@@ -566,6 +577,9 @@ int gal_synth_destroy(gal_synth_t *h)
     if (h->d_gain) hipFree(h->d_gain);
     if (h->h_gain) hipHostFree(h->h_gain);
     if (h->ev_gain) hipEventDestroy(h->ev_gain);
+    if (h->d_fir) hipFree(h->d_fir);
+    if (h->h_fir) hipHostFree(h->h_fir);
+    if (h->ev_fir) hipEventDestroy(h->ev_fir);
     if (h->d_lut) hipFree(h->d_lut);
     if (h->d_str) hipFree(h->d_str);
     if (h->h_up) hipHostFree(h->h_up);
@@ -1989,6 +2003,134 @@ int gal_synth_iq_wsum(gal_synth_t *h, const int16_t *const *parts_dev, int32_t n
                                 row_max > 65535 ? 1 : 0, out_dev, h->d_iq_sat, st));
     HIP_TRY(hipEventRecord(h->ev_gain, st));
     h->gain_pending = true;
+    return GAL_OK;
+}
+
+// ---- front-end FIR filter (iq_fir.hip) ---------------------------------------------------------------------------------------------
+static constexpr int kFirTableWords = 4 * 33;  // (GE, GO) x 2 pairs per trip, (128 / 2 + 1 + 1) / 2 trips at most
+static constexpr int kFirHist = 128;           // complex samples of history, as iq_fir.hip keeps them
+
+int gal_synth_fir_check(const int16_t *taps_q14, int32_t n_taps)
+{
+    if (!taps_q14) return fail(GAL_E_INVAL, "gal_synth_fir_check: null taps");
+    if (n_taps < 1 || n_taps > GAL_FIR_MAX_TAPS) return fail(GAL_E_INVAL, "gal_synth_fir_check: %d taps (1..%d)", n_taps, GAL_FIR_MAX_TAPS);
+    long sum = 0;
+    for (int k = 0; k < n_taps; ++k) sum += std::abs((long)taps_q14[k]);
+    if (sum > 65535)
+        return fail(GAL_E_INVAL, "gal_synth_fir_check: the taps' absolute values sum to %ld, more than 65535 (16384 = 1.0): the int32 accumulator could wrap", sum);
+    return GAL_OK;
+}
+
+int gal_synth_fir_lowpass(double cutoff_hz, double sample_rate, int32_t n_taps, int16_t *taps_q14)
+{
+    const char *who = "gal_synth_fir_lowpass";
+    if (!taps_q14) return fail(GAL_E_INVAL, "%s: null taps", who);
+    if (n_taps < 3 || n_taps > 127 || !(n_taps & 1)) return fail(GAL_E_INVAL, "%s: %d taps (odd, 3..127)", who, n_taps);
+    if (!std::isfinite(cutoff_hz) || !std::isfinite(sample_rate) || sample_rate <= 0.0 || !(cutoff_hz > 0.0) || !(cutoff_hz < sample_rate / 2))
+        return fail(GAL_E_INVAL, "%s: cutoff %g Hz must lie inside (0, sample_rate / 2 = %g Hz)", who, cutoff_hz, sample_rate / 2);
+    const double pi = 3.14159265358979323846, fc = cutoff_hz / sample_rate;
+    const int M = n_taps - 1;
+    double ws[GAL_FIR_MAX_TAPS], S = 0.0;
+    for (int k = 0; k <= M; ++k) {
+        const double t = (double)(k - M / 2);
+        const double s = k == M / 2 ? 2.0 * fc : sin(2.0 * pi * fc * t) / (pi * t);
+        const double w = 0.54 - 0.46 * cos(2.0 * pi * (double)k / (double)M);
+        ws[k] = w * s;
+        S += ws[k];
+    }
+    if (!std::isfinite(S) || S == 0.0) return fail(GAL_E_INVAL, "%s: the window's sum is %g", who, S);
+    long long q[GAL_FIR_MAX_TAPS], sum = 0;
+    for (int k = 0; k <= M; ++k) {
+        q[k] = llround(16384.0 * ws[k] / S);
+        sum += q[k];
+    }
+    q[M / 2] += 16384 - sum;
+    int16_t out[GAL_FIR_MAX_TAPS];
+    for (int k = 0; k <= M; ++k) {
+        if (q[k] < -32768 || q[k] > 32767) return fail(GAL_E_INVAL, "%s: tap %d = %lld does not fit an int16", who, k, q[k]);
+        out[k] = (int16_t)q[k];
+    }
+    const int rc = gal_synth_fir_check(out, n_taps);
+    if (rc) return rc;
+    memcpy(taps_q14, out, sizeof(int16_t) * (size_t)n_taps);
+    return GAL_OK;
+}
+
+int gal_synth_fir_set(gal_synth_t *h, const int16_t *taps_q14, int32_t n_taps)
+{
+    const char *who = "gal_synth_fir_set";
+    if (!h) return fail(GAL_E_INVAL, "null handle");
+    if (n_taps != 0) {
+        const int rc = gal_synth_fir_check(taps_q14, n_taps);
+        if (rc) return rc;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->fir_pending) {  // the table and the histories belong to the kernel in flight
+        HIP_TRY(hipEventSynchronize(h->ev_fir));
+        h->fir_pending = false;
+    }
+    if (n_taps == 0) {
+        if (h->d_fir) hipFree(h->d_fir);
+        if (h->h_fir) hipHostFree(h->h_fir);
+        h->d_fir = h->h_fir = nullptr;
+        h->fir_taps = 0;
+        return GAL_OK;
+    }
+    hipStream_t st = handle_stream(h);
+    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
+    const size_t table_bytes = sizeof(uint32_t) * kFirTableWords, bytes = table_bytes + 2 * sizeof(uint32_t) * kFirHist;
+    if (!h->ev_fir) HIP_TRY(hipEventCreateWithFlags(&h->ev_fir, hipEventDisableTiming));
+    if (!h->d_fir) {
+        uint32_t *d = nullptr, *p = nullptr;
+        if (hipMalloc((void **)&d, bytes) != hipSuccess || hipHostMalloc((void **)&p, table_bytes, hipHostMallocDefault) != hipSuccess) {
+            if (d) hipFree(d);
+            return fail(GAL_E_NOMEM, "%s: the filter table of %zu bytes could not be allocated", who, bytes);
+        }
+        h->d_fir = d;
+        h->h_fir = p;
+        h->fir_taps = 0;
+    }
+    // from here on the filter in force is gone: a failure leaves the handle without one
+    h->fir_taps = 0;
+    memset(h->h_fir, 0, table_bytes);
+    int trips = 0, hs = 0;
+    galk_fir_table(taps_q14, n_taps, h->h_fir, &trips, &hs);
+    HIP_TRY(hipMemcpyAsync(h->d_fir, h->h_fir, table_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(h->d_fir + kFirTableWords, 0, 2 * sizeof(uint32_t) * kFirHist, st));
+    HIP_TRY(hipEventRecord(h->ev_fir, st));  // (the upload reads h_fir: the next call waits for it as for a kernel)
+    h->fir_pending = true;
+    h->fir_taps = n_taps;
+    h->fir_trips = trips;
+    h->fir_hs = hs;
+    h->fir_cur = 0;
+    return GAL_OK;
+}
+
+int gal_synth_iq_fir(gal_synth_t *h, const int16_t *in_dev, size_t n_samples, int16_t *out_dev)
+{
+    const char *who = "gal_synth_iq_fir";
+    if (!h) return fail(GAL_E_INVAL, "null handle");
+    if (!in_dev || !out_dev || ((uintptr_t)in_dev & 15) || ((uintptr_t)out_dev & 15))
+        return fail(GAL_E_INVAL, "%s: device pointers must be non-null and 16-byte aligned", who);
+    if ((uint64_t)n_samples >> 41) return fail(GAL_E_INVAL, "%s: n_samples must be below 2^41", who);
+    if (!h->fir_taps) return fail(GAL_E_STATE, "%s: no filter set (call gal_synth_fir_set first)", who);
+    if (n_samples == 0) return GAL_OK;
+    const size_t bytes = 4 * n_samples;
+    const char *x = (const char *)in_dev, *o = (const char *)out_dev;
+    if (x < o + bytes && o < x + bytes) return fail(GAL_E_INVAL, "%s: input and output overlap (in place is not possible: tiles read their neighbours' input)", who);
+    if (hits_batch_in_flight(h, in_dev, bytes)) return fail(GAL_E_STATE, "%s: input of the batch in flight (call gal_synth_finish first)", who);
+    if (hits_batch_in_flight(h, out_dev, bytes)) return fail(GAL_E_STATE, "%s: output of the batch in flight (call gal_synth_finish first)", who);
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = handle_stream(h);
+    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
+    const int rc = ensure_sat_counter(h, st);
+    if (rc) return rc;
+    uint32_t *const hist = h->d_fir + kFirTableWords;
+    HIP_TRY(galk_launch_iq_fir(in_dev, out_dev, (uint64_t)n_samples, h->d_fir, h->fir_trips, h->fir_hs, hist + h->fir_cur * kFirHist,
+                               hist + (h->fir_cur ^ 1) * kFirHist, h->d_iq_sat, st));
+    h->fir_cur ^= 1;
+    HIP_TRY(hipEventRecord(h->ev_fir, st));
+    h->fir_pending = true;
     return GAL_OK;
 }
 

@@ -33,6 +33,8 @@ GAL_N_SYM_PAGE = 500
 GAL_GAIN_UNITY = 128
 GAL_GAIN_MAX = 32767
 GAL_GAIN_PATTERN_LEN = 37
+GAL_FIR_MAX_TAPS = 128  # front-end filter (gal_synth_fir_set): taps in Q14
+GAL_FIR_UNITY = 16384
 GAL_ENGINE_MAX_CHAN = 64
 
 # gal_chan_epoch_t (176 bytes)
@@ -180,6 +182,10 @@ EXPORTED_SYMBOLS = (
     "gal_synth_run_gains",
     "gal_synth_gain_runs",
     "gal_synth_gain_q7",
+    "gal_synth_fir_check",
+    "gal_synth_fir_lowpass",
+    "gal_synth_fir_set",
+    "gal_synth_iq_fir",
     "gal_synth_corr_out_bytes",
     "gal_synth_correlate",
     "gal_tables_e1b",
@@ -256,6 +262,14 @@ def load_library(hooks=False):
     lib.gal_synth_gain_runs.restype = ctypes.c_int
     lib.gal_synth_gain_q7.argtypes = [ctypes.c_double, ctypes.c_double, vp, ctypes.c_double, ctypes.POINTER(ctypes.c_uint16)]
     lib.gal_synth_gain_q7.restype = ctypes.c_int
+    lib.gal_synth_fir_check.argtypes = [vp, i32]
+    lib.gal_synth_fir_check.restype = ctypes.c_int
+    lib.gal_synth_fir_lowpass.argtypes = [ctypes.c_double, ctypes.c_double, i32, vp]
+    lib.gal_synth_fir_lowpass.restype = ctypes.c_int
+    lib.gal_synth_fir_set.argtypes = [vp, vp, i32]
+    lib.gal_synth_fir_set.restype = ctypes.c_int
+    lib.gal_synth_iq_fir.argtypes = [vp, vp, ctypes.c_size_t, vp]
+    lib.gal_synth_iq_fir.restype = ctypes.c_int
     lib.gal_synth_corr_out_bytes.argtypes = [ctypes.POINTER(_CorrReq)]
     lib.gal_synth_corr_out_bytes.restype = ctypes.c_size_t
     lib.gal_synth_correlate.argtypes = [vp, vp, i32, ctypes.c_size_t, ctypes.POINTER(_CorrReq), i32, vp]
@@ -354,6 +368,34 @@ def gain_q7(d_m, elev_rad, pattern_db=None, offset_db=0.0):
     if rc != 0:
         raise GalSynthError(rc, lib.gal_synth_last_error().decode())
     return int(g.value)
+
+
+def _fir_taps(taps, who):
+    t = np.asarray(taps)
+    if t.ndim != 1 or (t.size and (not np.issubdtype(t.dtype, np.integer) or t.min() < -32768 or t.max() > 32767)):
+        raise ValueError("%s: taps must be a one-dimensional sequence of integers that fit an int16 (Q14: 16384 = 1.0)" % who)
+    return np.ascontiguousarray(t, dtype=np.int16)
+
+
+def fir_check(taps):
+    """gal_synth_fir_check (no GPU needed): raises GalSynthError unless the Q14 taps are admitted -- 1 .. GAL_FIR_MAX_TAPS of them
+    with sum |h| <= 65535."""
+    lib = load_library()
+    t = _fir_taps(taps, "fir_check")
+    rc = lib.gal_synth_fir_check(t.ctypes.data if t.size else None, int(t.size))
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+
+
+def fir_lowpass(cutoff_hz, sample_rate, n_taps=63):
+    """gal_synth_fir_lowpass (no GPU needed): the int16 Q14 taps of a Hamming-windowed sinc low-pass of n_taps (odd, 3 .. 127) taps
+    with DC gain exactly 1 (the taps sum to 16384)."""
+    lib = load_library()
+    t = np.zeros(GAL_FIR_MAX_TAPS, dtype=np.int16)
+    rc = lib.gal_synth_fir_lowpass(float(cutoff_hz), float(sample_rate), int(n_taps), t.ctypes.data)
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+    return t[: int(n_taps)].copy()
 
 
 def _corr_struct(req):
@@ -577,6 +619,18 @@ class SynthEngine:
         g = np.ascontiguousarray(g, dtype=np.uint16)
         ptrs = (ctypes.c_void_p * max(1, len(part_ptrs)))(*[int(p) for p in part_ptrs])
         self._check(self._lib.gal_synth_iq_wsum(self._h, ptrs, len(part_ptrs), g.ctypes.data, g.shape[0], ctypes.c_void_p(int(out_ptr))))
+
+    def fir_set(self, taps):
+        """gal_synth_fir_set: give the handle the front-end filter `taps` (int16 Q14, 1 .. GAL_FIR_MAX_TAPS, sum |h| <= 65535) and start
+        a stream (the history is zeroed); None or an empty sequence frees the filter."""
+        t = _fir_taps(taps if taps is not None else [], "fir_set")
+        self._check(self._lib.gal_synth_fir_set(self._h, t.ctypes.data if t.size else None, int(t.size)))
+
+    def iq_fir(self, in_ptr, n_samples, out_ptr):
+        """gal_synth_iq_fir, enqueued on the handle's stream: filter the next n_samples complex int16 samples of the stream, device
+        address in_ptr -> out_ptr (both 16-byte aligned, not overlapping).  The handle carries the filter's history from call to call:
+        any cut of a stream into calls gives the same bytes.  iq_saturated() is the fence and counts the clamped values."""
+        self._check(self._lib.gal_synth_iq_fir(self._h, ctypes.c_void_p(int(in_ptr)), int(n_samples), ctypes.c_void_p(int(out_ptr))))
 
     def run_gains(self, params, gain_q7, iq_dev_ptr, state_in=None):
         """gal_synth_run_gains: the batch with per-slot, per-epoch Q7 gains gain_q7 [n_epochs, n_slots] (128 = unity) into the device

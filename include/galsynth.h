@@ -433,6 +433,54 @@ int gal_synth_gain_runs(const gal_synth_t *h, int32_t *n_runs);
 int gal_synth_gain_q7(double d_m, double elev_rad, const double *pattern_db, double offset_db, uint16_t *out);
 
 /*
+ * Front-end (IF) filter (not in the reference, whose files carry the unbounded spectrum of rectangular chips folded into the sample
+ * rate): a real FIR filter over the complex int16 stream, between the noise / interference pass and the format conversion.  Like the
+ * other passes it is a FIXED INTEGER FUNCTION of its inputs (tests/fir_model.py states it in numpy).
+ *
+ * x[n] = (I, Q)[n], the complex int16 samples of the WHOLE output stream, x[n] = 0 for n < 0; h[0 .. T-1] real int16 taps in Q14
+ * (GAL_FIR_UNITY = 16384 = 1.0), 1 <= T <= GAL_FIR_MAX_TAPS.  Per rail, in integers:
+ *   a[n] = sum over k of h[k] x[n - k]
+ *   y[n] = clamp((a[n] + 8192) >> 14, -32768, 32767)          (arithmetic shift: round to nearest, ties up)
+ * A value the clamp changes counts once in the handle's saturation counter (gal_synth_iq_saturated).  Taps are admitted only with
+ * sum |h[k]| <= 65535: then |a| + 8192 <= 65535 x 32768 + 8192 < 2^31 for any int16 input, and a is exact in an int32.
+ * h = {16384} gives y = x; h = 16384 at index D and 0 elsewhere gives y[n] = x[n - D], a pure delay.  A symmetric filter of T taps
+ * delays the stream by (T - 1) / 2 samples.
+ */
+#define GAL_FIR_MAX_TAPS 128
+#define GAL_FIR_UNITY 16384
+/* GAL_OK if the taps are admitted, else GAL_E_INVAL: a null pointer, n_taps outside 1..GAL_FIR_MAX_TAPS, sum |h[k]| > 65535.  Host
+ * only, needs no GPU. */
+int gal_synth_fir_check(const int16_t *taps_q14, int32_t n_taps);
+/* A low-pass: the Hamming-windowed sinc of n_taps taps (odd, 3 .. 127) with the cutoff (-6 dB) frequency cutoff_hz, 0 < cutoff_hz <
+ * sample_rate / 2.  Host only, needs no GPU.  With M = n_taps - 1, fc = cutoff_hz / sample_rate, pi = 3.14159265358979323846, in
+ * double, for k = 0 .. M:
+ *   t    = k - M / 2                                   (an integer: M is even)
+ *   s[k] = 2 fc                 for t = 0,    sin(2 pi fc t) / (pi t)  otherwise
+ *   w[k] = 0.54 - 0.46 cos(2 pi k / M)
+ *   S    = sum over k, in ascending order, of w[k] s[k]
+ *   h[k] = llround(16384 x (w[k] s[k]) / S)            (16384 x (w[k] s[k]) first, then the division)
+ * and then h[M / 2] += 16384 - sum of h, so that the DC gain is exactly 1.  The taps pass gal_synth_fir_check (GAL_E_INVAL if they
+ * would not, or if a tap left the int16 range).  GAL_E_INVAL also for a null pointer, an even n_taps or one outside 3..127, arguments
+ * that are not finite, sample_rate <= 0, a cutoff outside (0, sample_rate / 2). */
+int gal_synth_fir_lowpass(double cutoff_hz, double sample_rate, int32_t n_taps, int16_t *taps_q14);
+/* Give the handle a filter and START A STREAM: the taps (HOST memory, copied before the call returns) go to the device and the
+ * handle's history -- the input samples in front of the next call -- is zeroed.  n_taps = 0 (taps_q14 is then not looked at) frees
+ * the filter.  A handle holds one filter: the call waits (on the host) for a filter kernel of this handle that is still in flight.
+ * GAL_E_INVAL for a null handle and whatever gal_synth_fir_check refuses -- the filter in force, and its history, then stay as they
+ * are; GAL_E_NOMEM if the table cannot be had. */
+int gal_synth_fir_set(gal_synth_t *h, const int16_t *taps_q14, int32_t n_taps);
+/* Enqueue on the handle's stream: filter the NEXT n_samples complex samples of the stream, in_dev -> out_dev (both DEVICE memory,
+ * n_samples x 4 bytes).  The handle keeps the last input samples on the device and the call continues from them: ANY CUT OF A
+ * STREAM INTO CALLS GIVES THE SAME BYTES AS ONE CALL, calls shorter than the filter included.  n_samples may be any number, not only a
+ * multiple of 4 (0: nothing happens).  The rules of gal_synth_iq_convert: 16-byte aligned pointers (of every call: a cut off the vector
+ * grid needs a buffer of its own), GAL_E_STATE for a buffer of the batch in flight and with no filter set, gal_synth_iq_saturated is
+ * the fence and the counter.  out_dev overlapping in_dev is refused, exactly in place included: neighbouring tiles read each other's
+ * input.  GAL_E_INVAL for a null handle, a null or misaligned pointer, an overlap, n_samples >= 2^41.
+ * Sharding: a caller that starts in the middle of a stream (gal_synth_execute_range on one of several GPUs) primes the history after
+ * gal_synth_fir_set by filtering the T - 1 samples in front of its range (fewer at the start of the stream) and discarding that output. */
+int gal_synth_iq_fir(gal_synth_t *h, const int16_t *in_dev, size_t n_samples, int16_t *out_dev);
+
+/*
  * Correlator bank and C/N0 monitor (not in the reference): despread a device buffer of output IQ with the engine's own replica of one
  * satellite and get, per code period, delay and Doppler bin, the complex correlation sums of the E1B and the E1C component.  Read-only
  * on the buffer, in any of the three formats.  Like the formats and the noise floor it is a FIXED INTEGER FUNCTION of its inputs: the

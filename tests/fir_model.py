@@ -1,0 +1,81 @@
+"""The front-end FIR filter as include/galsynth.h defines it (gal_synth_fir_check, gal_synth_fir_lowpass, gal_synth_iq_fir), in numpy --
+TEST INFRASTRUCTURE: the product never imports this."""
+import numpy as np
+
+GAL_FIR_MAX_TAPS = 128
+GAL_FIR_UNITY = 16384
+
+
+def check(taps):
+    """True where gal_synth_fir_check admits the taps."""
+    h = np.asarray(taps, dtype=np.int64)
+    return h.ndim == 1 and 1 <= h.size <= GAL_FIR_MAX_TAPS and int(np.abs(h).sum()) <= 65535
+
+
+def fir(x, taps, history=None):
+    """x: interleaved int16 (I0, Q0, I1, Q1, ...) of the next samples of a stream; taps: int16 Q14; history: the interleaved samples in
+    front of x (None: the start of the stream, zeros; only its last T - 1 samples matter).  Returns (y int16 interleaved, values the
+    clamp changed): per rail a[n] = sum_k h[k] x[n - k], y[n] = clamp16((a[n] + 8192) >> 14)."""
+    x = np.asarray(x, dtype=np.int16)
+    h = np.asarray(taps, dtype=np.int64)
+    assert x.ndim == 1 and x.size % 2 == 0 and check(h)
+    n, T = x.size // 2, h.size
+    past = np.zeros(2 * (T - 1), dtype=np.int64)
+    if history is not None and T > 1:
+        hist = np.asarray(history, dtype=np.int64)
+        assert hist.ndim == 1 and hist.size % 2 == 0
+        m = min(hist.size, past.size)
+        if m:
+            past[past.size - m:] = hist[hist.size - m:]
+    s = np.concatenate([past, x.astype(np.int64)]).reshape(-1, 2)  # s[T - 1 + n] = x[n]
+    a = np.zeros((n, 2), dtype=np.int64)
+    for k in range(T):
+        a += h[k] * s[T - 1 - k: T - 1 - k + n]
+    v = (a + 8192) >> 14
+    y = np.clip(v, -32768, 32767)
+    return y.astype(np.int16).reshape(-1), int(np.count_nonzero(y != v))
+
+
+def lowpass(cutoff_hz, sample_rate, n_taps):
+    """gal_synth_fir_lowpass in double, operation for operation as the header states it: a Hamming-windowed sinc, rounded to Q14, the
+    centre tap adjusted so that the taps sum to 16384."""
+    assert n_taps % 2 == 1 and 3 <= n_taps <= 127 and 0.0 < cutoff_hz < sample_rate / 2
+    pi = np.float64(3.14159265358979323846)
+    fc = np.float64(cutoff_hz) / np.float64(sample_rate)
+    M = n_taps - 1
+    ws = np.zeros(n_taps, dtype=np.float64)
+    S = np.float64(0.0)
+    for k in range(n_taps):
+        t = np.float64(k - M // 2)
+        s = np.float64(2.0) * fc if k == M // 2 else np.sin(np.float64(2.0) * pi * fc * t) / (pi * t)
+        w = np.float64(0.54) - np.float64(0.46) * np.cos(np.float64(2.0) * pi * np.float64(k) / np.float64(M))
+        ws[k] = w * s
+        S = S + ws[k]
+    q = np.zeros(n_taps, dtype=np.int64)
+    for k in range(n_taps):
+        v = np.float64(16384.0) * ws[k] / S
+        q[k] = int(np.floor(abs(v) + 0.5)) * (1 if v >= 0 else -1)  # llround: ties away from zero
+    q[M // 2] += GAL_FIR_UNITY - int(q.sum())
+    return q.astype(np.int16)
+
+
+def random_taps(rng, T):
+    """T random int16 taps with sum |h| = 65535 exactly (the largest gal_synth_fir_check admits; T = 1 cannot reach it: -32768, the
+    largest single tap) and |h[0]| >= 20000, so that a full-scale sample of h[0]'s sign is clamped: 20000 x 32767 > 16384 x 32768."""
+    if T == 1:
+        return np.array([-32768], dtype=np.int16)
+    if T == 2:
+        return np.array([32767, -32768], dtype=np.int16)
+    m = np.zeros(T, dtype=np.int64)
+    m[0] = int(rng.integers(20000, 30001))
+    rest = 65535 - int(m[0])
+    w = rng.integers(1, 20001, size=T - 1).astype(np.float64)
+    m[1:] = np.minimum(np.floor(w * (rest / w.sum())).astype(np.int64), 32767)
+    rem = 65535 - int(m.sum())
+    for k in range(1, T):
+        add = min(rem, 32767 - int(m[k]))
+        m[k] += add
+        rem -= add
+    assert rem == 0 and int(m.sum()) == 65535
+    h = m * rng.choice([-1, 1], size=T)
+    return h.astype(np.int16)
