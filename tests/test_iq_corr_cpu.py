@@ -192,3 +192,38 @@ def test_model_cn0_of_a_noisy_stream(pkg, one_satellite):
     tol = 3 * 10 / math.log(10) * se
     print("C/N0 %.3f dB-Hz (asked 45), Pp / Pn %.2f, 3 standard errors %.2f dB" % (cn0, ratio, tol))
     assert abs(cn0 - 45.0) <= tol
+
+
+def test_model_fills_an_int32_within_128_samples(pkg):
+    """The standing request of tests/test_iq_corr_gpu.py::test_full_scale_input reaches what it claims.  The carrier table's loudest
+    entry with cos and sin of one sign has |cos| + |sin| = 354 (250 sqrt 2, rounded per entry), so the sample (-32768, -32768) is
+    wiped to |Re| = 32768 x 354 = 11.6 M -- 0.71 of the 2 x 32768 x 250 that iq_corr.hip's kSub = 128 is sized for -- and, the code
+    and the carrier standing, every sample adds it with one sign: 128 consecutive samples sum to 1.48 x 10^9, above 2^30 and below
+    2^31.  An int32 accumulator over 256 samples would wrap (kSub is tight within a factor of 2), and the whole buffer's sum needs
+    the int64 it is handed to."""
+    T = pkg.tables()
+    c, s = T["cos512"].astype(np.int64), T["sin512"].astype(np.int64)
+    i = int(np.argmax(np.abs(c + s)))
+    amp = int(abs(c[i] + s[i]))
+    assert amp == (np.abs(c) + np.abs(s)).max() and 350 <= amp <= 2 * 251
+    n = 8190
+    q = {"prn": 50, "code_ph0": (8183 << 32) + 17, "code_dph": 0, "carr_ph0": i << 23, "carr_dph": 0, "dopp0": 0, "max_periods": 1, "n_delay": 2,
+         "delay0": 8183}
+    v = np.full(2 * n, -32768, dtype=np.int64)
+    # the model's per-sample wiped values: (I + iQ) conj(w) with w = (cos, sin)[carr_ph0 >> 23] for every sample
+    re = v[0::2] * c[i] + v[1::2] * s[i]
+    im = v[1::2] * c[i] - v[0::2] * s[i]
+    assert (np.abs(re) == 32768 * amp).all() and np.abs(im).max() <= 32768 * 2
+    window = np.abs(np.convolve(re, np.ones(128, dtype=np.int64), mode="valid"))  # every sum of 128 consecutive samples
+    assert 2 ** 30 < int(window.max()) == 128 * 32768 * amp < 2 ** 31
+    assert 256 * 32768 * amp > 2 ** 31 and n * 32768 * amp > 2 ** 36
+    out = corr_model.correlate(v, q, T)
+    b, _ = corr_model.replicas(T, 50)
+    # delay 8183 of half chip 8183 reads b[0]; the next delay (8184 = 0) reads b[8183]
+    assert out.shape == (1, 1, 2, 4) and out[0, 0, 0, 0] == b[0] * re.sum() and out[0, 0, 1, 0] == b[8183] * re.sum()
+    assert abs(int(out[0, 0, 0, 0])) == n * 32768 * amp
+    # the sign trick of the kernel's walk, (x ^ s) - s with s = 0 or -1, is x or -x for every value the wipe-off can give: |x| is at
+    # most 32768 x 2 x 251 < 2^31, so -x never meets INT32_MIN, the one value it would leave unchanged
+    x = np.array([32768 * amp, -32768 * amp, 32768 * 502, -32768 * 502, 0, 1, -1], dtype=np.int32)
+    for sgn in (0, -1):
+        assert np.array_equal((x ^ np.int32(sgn)) - np.int32(sgn), x if sgn == 0 else -x)

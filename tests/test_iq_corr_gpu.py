@@ -241,3 +241,140 @@ def test_cn0_of_a_single_satellite_and_quantisation_loss(pkg, eng):
         assert 0.0 < loss["ibit"] <= book["ibit"] + tol
         assert 0.0 < loss["ibyte_coarse"] <= book["ibyte_coarse"] + tol
         assert abs(loss["ibyte"]) <= book["ibyte"] + tol
+
+
+# ---- full-scale input, every lane split of the delays, the largest code rate -------------------------------------------------------
+N_OWN = 8190  # samples of the buffers below: four tiles of 2048 less 2
+OUT_GUARD = 16  # int64 behind the sums that the kernel must leave alone
+
+
+def _own(host_bytes):
+    """A device buffer of the tests' own with 64 spare bytes behind it: (device tensor, host bytes), as batch12's."""
+    import torch
+
+    host = np.concatenate([np.ascontiguousarray(host_bytes).view(np.uint8).ravel(), np.zeros(64, dtype=np.uint8)])
+    dev = torch.from_numpy(host).cuda()
+    torch.cuda.synchronize()
+    return dev, host
+
+
+@pytest.fixture(scope="module")
+def own():
+    """Buffers no synthesis would write: ishort all (-32768, -32768), random full-range, and (-32768, 32767), (32767, -32768) in turn;
+    ibyte of -128, -127 and 127 only, its first 300 samples all -128; ibit of random bytes."""
+    rng = np.random.default_rng(812)
+    j = np.arange(2 * N_OWN)
+    byte = rng.choice(np.array([-128, -127, 127], dtype=np.int8), size=2 * N_OWN)
+    byte[:600] = -128
+    return {
+        "ishort_min": ("ishort", _own(np.full(2 * N_OWN, -32768, dtype=np.int16))),
+        "ishort_random": ("ishort", _own(rng.integers(-32768, 32768, size=2 * N_OWN, dtype=np.int16))),
+        "ishort_alternating": ("ishort", _own(np.where((j // 2 + j) % 2 == 0, -32768, 32767).astype(np.int16))),
+        "ibyte_edges": ("ibyte", _own(byte)),
+        "ibit_random": ("ibit", _own(rng.integers(0, 256, size=(N_OWN + 3) // 4, dtype=np.uint8))),
+    }
+
+
+def _check_guarded(pkg, eng, own, name, n_samples, reqs, tables):
+    """As _check, with the sums written to a device buffer of the test's own that is OUT_GUARD int64 longer than they are."""
+    import torch
+
+    fmt, (dev, host) = own[name]
+    sizes = [pkg.corr_out_bytes(q) // 8 for q in reqs]
+    out = torch.full((sum(sizes) + OUT_GUARD,), 0x5a5a5a5a5a5a, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    assert eng.correlate(dev.data_ptr(), fmt, n_samples, reqs, out_ptr=out.data_ptr()) is None
+    eng.iq_saturated()  # the fence
+    got = out.cpu().numpy()
+    assert (got[sum(sizes):] == 0x5a5a5a5a5a5a).all(), "the kernel wrote behind the sums"
+    v = corr_model.values(host, fmt, n_samples)
+    off, res = 0, []
+    for r, (q, size) in enumerate(zip(reqs, sizes)):
+        want = corr_model.correlate(v, q, tables)
+        g = got[off:off + size].reshape(want.shape)
+        assert np.array_equal(g, want), (name, r, q, int(np.count_nonzero(g != want)))
+        res.append(g)
+        off += size
+    return res
+
+
+def _loudest_carrier_phase(tables):
+    """carr_ph0 of the carrier table's entry with the largest |cos| + |sin| among those where the two have one sign: there the
+    (-32768, -32768) sample gives the largest |Re| of x conj(w) there is, 32768 (|cos| + |sin|)."""
+    c, s = tables["cos512"].astype(np.int64), tables["sin512"].astype(np.int64)
+    i = int(np.argmax(np.abs(c + s)))
+    assert abs(c[i] + s[i]) == (np.abs(c) + np.abs(s)).max()
+    return i << 23, int(abs(c[i] + s[i]))
+
+
+def _moving(first, dph=3 << 30, **grid):
+    """The request of test_period_boundary_at_a_tile_edge: period 1 starts at sample `first`."""
+    q = {"prn": 5, "code_ph0": corr_model.L - first * dph, "code_dph": dph, "carr_ph0": 12345, "carr_dph": -BIN_250HZ * 7, "max_periods": 2,
+         "delay0": -2, "n_delay": 5, "dopp0": -9, "dopp_step": 9, "n_dopp": 3}
+    q.update(grid)
+    return q
+
+
+@pytest.mark.parametrize("name", ["ishort_min", "ishort_random", "ishort_alternating", "ibyte_edges"])
+def test_full_scale_input(pkg, eng, own, name):
+    """int16 at its ends (and int8 at -128, which the ibyte writer never makes): a standing code and a standing carrier at the table's
+    loudest phase, so that every sample adds 32768 x (|cos| + |sin|) = 11.6 M with one sign and 128 samples fill an int32
+    accumulator to more than 2^30 (tests/test_iq_corr_cpu.py has the arithmetic); and the ordinary moving request.  A lane walks
+    128 consecutive samples only where its segment of the tile is that long: with 2 delays the 256 lanes split the tile into 128
+    segments of 16 samples, so the standing request is also made with 17 delays (8 segments of 256 samples: two int32 accumulations
+    each) and with 129 (one delay per lane, the whole tile of 2048 samples: sixteen)."""
+    T = pkg.tables()
+    ph, amp = _loudest_carrier_phase(T)
+    assert 2 ** 30 < 128 * 32768 * amp < 2 ** 31
+    standing = {"prn": 50, "code_ph0": (8183 << 32) + 17, "code_dph": 0, "carr_ph0": ph, "carr_dph": 0, "dopp0": 0, "max_periods": 1, "n_delay": 2,
+                "delay0": 8183}
+    reqs = [standing, _moving(3000), dict(standing, carr_ph0=ph ^ (1 << 31), prn=1, delay0=0), dict(standing, n_delay=17),
+            dict(standing, n_delay=129, delay_step=63)]
+    assert [(2048 * kd // 256) for kd, _, _ in map(_lanes_per_segment, (2, 17, 129))] == [16, 256, 2048]  # samples per segment
+    got = _check_guarded(pkg, eng, own, name, N_OWN, reqs, T)
+    _check_guarded(pkg, eng, own, name, 4097, reqs, T)
+    if name == "ishort_min":  # the sums are what the bound speaks of: every sample at full weight, one sign
+        assert abs(int(got[0][0, 0, 0, 0])) == N_OWN * 32768 * amp > 2 ** 36
+
+
+DELAY_COUNTS = (9, 16, 17, 33, 64, 100, 128, 129, 256, 257, 300)
+
+
+def _lanes_per_segment(n_delay):
+    """galk_launch_corr (csrc/iq_corr.hip), restated: kd = the power of two >= n_delay, at most the block's 256 lanes; the block's
+    lanes are 256 / kd segments of the tile per delay, and it takes ceil(n_delay / kd) trips over the delays."""
+    kd = 1
+    while kd < n_delay and kd < 256:
+        kd <<= 1
+    return kd, 256 // kd, -(-n_delay // kd)
+
+
+@pytest.mark.parametrize("n_delay", DELAY_COUNTS)
+def test_every_split_of_the_lanes(pkg, eng, own, n_delay):
+    """16, 8, 4 and 2 segments of the tile per delay (summed through LDS, the lanes beyond kd idle behind it), full and partly
+    filled, one delay per lane at the switch (129), and a second trip over the delays that only some lanes take (257, 300) -- with a
+    period boundary inside the second tile (sample 3000), where max_periods = 2 goes on into period 1 and max_periods = 1 ends the
+    tile there."""
+    shapes = [_lanes_per_segment(k) for k in DELAY_COUNTS]
+    assert {kd for kd, _, _ in shapes} == {16, 32, 64, 128, 256} and {nseg for _, nseg, _ in shapes} == {16, 8, 4, 2, 1}
+    assert [s for s in shapes if s[2] > 1] == [(256, 1, 2), (256, 1, 2)] and 257 % 256 and 300 % 256  # a partial second trip
+    assert _lanes_per_segment(128) == (128, 2, 1) and _lanes_per_segment(129) == (256, 1, 1) and _lanes_per_segment(256) == (256, 1, 1)
+    assert {_lanes_per_segment(k)[0] for k in (1, 3, 5, 8184)} == {1, 4, 8, 256}  # what the tests above reach
+    assert 2048 < 3000 < 4096
+    T = pkg.tables()
+    reqs = [_moving(3000, n_delay=n_delay, n_dopp=2, max_periods=2), _moving(3000, n_delay=n_delay, n_dopp=2, max_periods=1)]
+    got = _check_guarded(pkg, eng, own, "ishort_random", N_OWN, reqs, T)
+    assert got[0][1].any() and np.array_equal(got[0][0], got[1][0])
+
+
+@pytest.mark.parametrize("name", ["ishort_random", "ibyte_edges", "ibit_random"])
+def test_one_half_chip_per_sample(pkg, eng, own, name):
+    """code_dph = 2^32, the largest admitted: a tile of 2048 samples spans exactly 2048 half chips.  Period 1 starts at sample 2047,
+    2048 (the first of the second tile) and 2049; and at sample 1, so that period 2 starts at 8185, inside the last tile."""
+    T = pkg.tables()
+    dph = 1 << 32
+    reqs = [_moving(first, dph=dph, n_delay=5) for first in (2047, 2048, 2049)] + [_moving(1, dph=dph, n_delay=5, max_periods=3)]
+    assert all(q["code_dph"] == 1 << 32 and 0 <= q["code_ph0"] < corr_model.L for q in reqs)
+    got = _check_guarded(pkg, eng, own, name, N_OWN, reqs, T)
+    assert got[3][2].any()  # five samples of period 2
+    _check_guarded(pkg, eng, own, name, 2049, reqs[:3], T)

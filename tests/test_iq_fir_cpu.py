@@ -110,3 +110,38 @@ def test_fir_lowpass_refusals(pkg):
     assert not out.any()  # a refused call writes nothing
     with pytest.raises(pkg.synth.GalSynthError):
         pkg.synth.fir_lowpass(1.0e6, fs, 64)
+
+
+def worst_taps(T, sign):
+    """T taps of one sign at the admitted bound: sign -1 gives -32768 first and the rest sharing 32767 (sum |h| = 65535); +1 gives
+    32767 first and the rest sharing 32768 (65535 for T >= 3; two non-negative int16 taps reach 65534 only)."""
+    first = 32768 if sign < 0 else 32767
+    m = np.zeros(T, dtype=np.int64)
+    m[0] = first
+    rest = min(65535 - first, 32767 * (T - 1))
+    m[1:] = rest // (T - 1)
+    m[1: 1 + rest - int(m[1:].sum())] += 1
+    assert int(m.sum()) == (65535 if T > 2 or sign < 0 else 65534) and m.max() <= first
+    return (sign * m).astype(np.int16)
+
+
+@pytest.mark.parametrize("T", [2, 5, 128])
+def test_model_reaches_the_int32_bound_of_the_accumulator(T):
+    """The inputs of tests/test_iq_fir_gpu.py::test_aligned_worst_case reach what they claim: every tap negative with the first at
+    -32768, every sample -32768 on both rails -- from sample T - 1 on a[n] = 65535 x 32768, and a + 8192 = 2 147 459 072, the bound
+    DESIGN.md section 15 states, 24 576 below 2^31.  Every output clamps."""
+    n = 1025
+    taps = worst_taps(T, -1)
+    assert taps[0] == -32768 and (T != 2 or taps[1] == -32767) and (taps <= 0).all() and fir_model.check(taps)
+    x = np.full(2 * n, -32768, dtype=np.int16)
+    a = np.convolve(x[0::2].astype(np.int64), taps.astype(np.int64))[:n]  # a[n] = sum_k h[k] x[n - k] in int64, zeros in front
+    assert int((a + 8192).max()) == 65535 * 32768 + 8192 == 2147459072 < 2 ** 31
+    assert (a[T - 1:] == 65535 * 32768).all() and (np.diff(a[:T]) >= 0).all()  # the partial sums only grow towards it
+    assert int(taps[0]) * -32768 + int(taps[1]) * -32768 <= 65535 * 32768  # the largest pair of products, one dot product's worth
+    y, sat = fir_model.fir(x, taps)
+    assert sat == 2 * n and (y == 32767).all()
+    # the other sign: all taps >= 0 against +32767, just inside the bound
+    pos = worst_taps(T, +1)
+    assert (pos >= 0).all() and fir_model.check(pos)
+    y, sat = fir_model.fir(np.full(2 * n, 32767, dtype=np.int16), pos)
+    assert sat == 2 * n and (y == 32767).all()

@@ -199,3 +199,110 @@ def test_engine_output_filtered_and_parity_kept(pkg):
         assert np.array_equal(got, want), _differ(got, want)
         plain, _, _ = eng.run_host(p)
         assert np.array_equal(plain, ref)
+
+
+# ---- the int32 accumulator at its bound, and the tap table at every shape ----------------------------------------------------------
+def _worst_taps(T, sign):
+    """T taps of one sign at the admitted bound (tests/test_iq_fir_cpu.py: worst_taps, and the witness that they reach it): sign -1
+    gives -32768 first and the rest sharing 32767 (sum |h| = 65535); +1 gives 32767 first and the rest sharing 32768 (65535 for
+    T >= 3; two non-negative int16 taps reach 65534 only)."""
+    first = 32768 if sign < 0 else 32767
+    m = np.zeros(T, dtype=np.int64)
+    m[0] = first
+    rest = min(65535 - first, 32767 * (T - 1))
+    m[1:] = rest // (T - 1)
+    m[1: 1 + rest - int(m[1:].sum())] += 1
+    assert int(m.sum()) == (65535 if T > 2 or sign < 0 else 65534) and m.max() <= first
+    return (sign * m).astype(np.int16)
+
+
+def _one_call_and_cuts(eng, taps, x, cuts):
+    want, want_sat = fir_model.fir(x, taps)
+    eng.fir_set(taps)
+    got, sat = _fir_call(eng, x)
+    assert np.array_equal(got, want), "one call: " + _differ(got, want)
+    assert sat == want_sat
+    eng.fir_set(taps)
+    got, sat = _stream_in_cuts(eng, x, cuts)
+    assert np.array_equal(got, want), "in cuts: " + _differ(got, want)
+    assert sat == want_sat
+    return want_sat
+
+
+@pytest.mark.parametrize("T", [2, 5, 128])
+def test_aligned_worst_case(pkg, T):
+    """Every product of one sign at full scale: the int32 accumulator (and a single v_dot2_i32_i16, whose two products are the first
+    two taps') at a + 8192 = 65535 x 32768 + 8192, 24 576 below 2^31.  Every output clamps and is counted.  1025 samples are one
+    tile and one sample; they are cut as the calls of CUTS that fit into them, then the rest."""
+    n = 1025
+    cuts = CUTS[:6]
+    assert sum(cuts) < n < sum(CUTS[:7])
+    with pkg.SynthEngine(samples_per_epoch=N, n_slots=16, device=0) as eng:
+        neg = _worst_taps(T, -1)
+        assert neg[0] == -32768 and (T != 2 or neg[1] == -32767) and (neg <= 0).all()
+        assert _one_call_and_cuts(eng, neg, np.full(2 * n, -32768, dtype=np.int16), cuts) == 2 * n
+        pos = _worst_taps(T, +1)
+        assert (pos >= 0).all()
+        assert _one_call_and_cuts(eng, pos, np.full(2 * n, 32767, dtype=np.int16), cuts) == 2 * n
+
+
+@pytest.mark.parametrize("T", [2, 5, 128])
+def test_sign_matched_worst_case(pkg, T):
+    """Taps of mixed signs at sum |h| = 65535, the first at -32768, and an input matched to them in sign around a few samples n0:
+    on the I rail x[n0 - k] = -32768 sign(h[k]) (as far as an int16 goes: +32767), every product negative; on the Q rail the opposite
+    sign, every product positive.  The n0 are the first and the last sample of a tile, the last of a wave and the first of the next
+    (samples 255 and 256 of a tile), and sample T - 1, whose window is the stream's first T samples; random full-range int16 elsewhere."""
+    n = 3073
+    rng = np.random.default_rng(500 + T)
+    taps = (_worst_taps(T, -1).astype(np.int64) * np.concatenate([[1], rng.choice([-1, 1], size=T - 1)])).astype(np.int16)
+    assert taps[0] == -32768 and int(np.abs(taps.astype(np.int64)).sum()) == 65535 and (T == 2 or ((taps > 0).any() and (taps[1:] < 0).any()))
+    x = rng.integers(-32768, 32768, size=(n, 2), dtype=np.int16)
+    sgn = np.sign(taps.astype(np.int64))
+    centres = (T - 1, 1024, 1024 + 255, 2048 + 256, 2048 + 1023)
+    for n0 in centres:
+        assert n0 - (T - 1) >= 0
+        k = np.arange(T)
+        x[n0 - k, 0] = np.clip(-32768 * sgn, -32768, 32767)
+        x[n0 - k, 1] = np.clip(32768 * sgn, -32768, 32767)
+    assert all(b - (T - 1) > a for a, b in zip(centres, centres[1:]))  # the windows do not overlap
+    x = x.reshape(-1)
+    want, _ = fir_model.fir(x, taps)
+    for n0 in centres:  # far beyond the clamp on both rails, in opposite directions
+        assert want[2 * n0] == -32768 and want[2 * n0 + 1] == 32767
+    with pkg.SynthEngine(samples_per_epoch=N, n_slots=16, device=0) as eng:
+        assert _one_call_and_cuts(eng, taps, x, CUTS) > 0
+
+
+TABLE_TAPS = (6, 7, 8, 9, 10, 14, 17, 64, 65, 66, 125, 127)
+TABLE_SIZES = SIZES
+
+
+def _table_shape(T):
+    """galk_fir_table (csrc/iq_fir.hip), restated: the halo is T - 1 rounded up to a multiple of 4 samples, a trip of the kernel's
+    loop takes two tap pairs of the Hs / 2 + 1 there are."""
+    Hs = (T - 1 + 3) & ~3
+    return Hs, (Hs // 2 + 1 + 1) // 2
+
+
+@pytest.mark.parametrize("T", TABLE_TAPS)
+def test_kernel_against_the_model_at_every_table_shape(pkg, T):
+    """test_kernel_against_the_model at the tap counts between its own: T = 2, 3, 0, 1 (mod 4) at halos of 8, 12, 16, 64, 68, 124 and
+    128 samples, where the table's zero padding in front of the first tap and behind the last has every length it can have."""
+    shapes = [_table_shape(t) for t in TABLE_TAPS]
+    assert {hs % 8 for hs, _ in shapes} == {0, 4} and {hs for hs, _ in shapes} == {8, 12, 16, 64, 68, 124, 128}
+    assert {trips for _, trips in shapes} == {3, 4, 5, 17, 18, 32, 33}
+    assert {t % 4 for t in TABLE_TAPS} == {0, 1, 2, 3}
+    assert [_table_shape(t) for t in TAPS] == [(0, 1), (4, 2), (4, 2), (4, 2), (4, 2), (64, 17), (128, 33)]  # what the first test reaches
+    rng = np.random.default_rng(9000 + T)
+    taps = fir_model.random_taps(rng, T)
+    full = rng.integers(-32768, 32768, size=2 * max(TABLE_SIZES), dtype=np.int16)
+    full[:32] = 32767 if taps[0] >= 0 else -32768  # the first 16 samples at full scale, of the first tap's sign: the clamp fires
+    with pkg.SynthEngine(samples_per_epoch=N, n_slots=16, device=0) as eng:
+        for n in TABLE_SIZES:
+            x = full[: 2 * n]
+            want, want_sat = fir_model.fir(x, taps)
+            assert want_sat > 0
+            eng.fir_set(taps)  # a new stream for every size
+            got, sat = _fir_call(eng, x)
+            assert np.array_equal(got, want), "T %d, n %d: %s" % (T, n, _differ(got, want))
+            assert sat == want_sat, (T, n)

@@ -168,3 +168,28 @@ def test_cli_prints_the_power_choices(pkg, tmp_path):
     assert "signal gain 1 (chosen)" in _cli("--cn0", "45", "-o", str(tmp_path / "x.ishort")).stderr
     r = _cli("--cn0", "45", "--prn-power", "5:16", "-o", str(tmp_path / "x.ishort"))
     assert "signal gain 0.5 (chosen)" in r.stderr, r.stderr
+
+
+def test_model_at_the_int32_bound_of_the_narrow_sum():
+    """The inputs of tests/test_iq_gain_gpu.py::test_wsum_at_the_int32_bound reach what they claim: with all three parts at -32768 the
+    row [32767, 32767, 1] (sum 65535, the largest the int32 instance of k_iq_wsum takes) gives w = -65535 x 32768, which an int32
+    holds with the rounding 64 added; the rows that sum to 65536 and 65537 give -2^31 exactly and -2^31 - 32768, and 65537 x -32768
+    does not fit an int32: those calls need the int64 instance.  At +32767 all three fit, the sign decides."""
+    spe, n_epochs = 4, 2
+    rows = ([32767, 32767, 1], [32767, 32767, 2], [32767, 32767, 3])
+    lo, hi = -2 ** 31, 2 ** 31 - 1
+    for level in (-32768, 32767):
+        parts = np.full((3, n_epochs * spe * 2), level, dtype=np.int16)
+        for row in rows:
+            g = np.tile(row, (n_epochs, 1))
+            w = (g.astype(np.int64)[0][:, None] * parts[:, : 2 * spe].astype(np.int64)).sum(axis=0)  # the model's w of epoch 0
+            assert (w == sum(row) * level).all()
+            y, sat = gain_model.wsum(parts, g, spe)
+            assert (y == level).all() and sat == parts.shape[1]  # |(w + 64) >> 7| = 16.7 M: every value clamps, to the parts' own level
+            if level < 0:
+                assert (lo <= int(w[0]) and int(w[0]) + 64 <= hi) == (sum(row) <= 65536)
+            else:
+                assert lo <= int(w[0]) and int(w[0]) + 64 <= hi
+    assert -65535 * 32768 == -2147450880 and lo <= -65535 * 32768 and -65535 * 32768 + 64 <= hi
+    assert 65535 * 32767 + 64 <= hi
+    assert 65536 * -32768 == lo and 65537 * -32768 < lo  # the host sends any row above 65535 to the int64 instance

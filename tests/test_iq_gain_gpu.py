@@ -237,3 +237,171 @@ def test_bad_arguments_and_call_order(pkg, batch):
         eng.run_gains(p, g, out.data_ptr())
         eng.iq_wsum([a.data_ptr(), b.data_ptr()], g2, out.data_ptr())
         eng.iq_saturated()
+
+
+# ---- k_iq_wsum's launch geometry, part counts and int32 edge ----------------------------------------------------------------------
+# galk_launch_iq_wsum (csrc/iq_gain.hip), restated: a grid of (bx, by) blocks of 256 lanes, at most 2048 blocks in all.
+#   by   = min(n_epochs, 2048)                block y takes the epochs y, y + by, y + 2 by, ...
+#   need = ceil((spe / 4) / 256)              blocks that give every 16-byte vector (4 complex samples) of an epoch a lane of its own
+#   cap  = 2048 / by
+#   bx   = min(need, cap), at least 1         lane t of block x takes the epoch's whole vectors x 256 + t, + bx 256, + 2 bx 256, ...
+# The up to three samples in front of an epoch's first whole vector and behind its last are taken by block x = 0, one per lane.
+K_BLOCKS, K_LANES = 2048, 256
+
+
+def _launch(spe, n_epochs):
+    by = min(n_epochs, K_BLOCKS)
+    need, cap = (spe // 4 + K_LANES - 1) // K_LANES, K_BLOCKS // by
+    bx = max(1, min(need, cap))
+    a = np.arange(n_epochs, dtype=np.int64) * spe
+    vec = (a + spe) // 4 - (a + 3) // 4  # whole vectors of every epoch
+    return {"by": by, "bx": bx, "need": need, "cap": cap, "y_trips": -(-n_epochs // by), "vec": vec, "x_stride": bx * K_LANES,
+            "x_trips": -(-vec // (bx * K_LANES))}
+
+
+def _edge_parts(rng, n_parts, n_epochs, spe):
+    """Random full-range int16; the first 8 values of every epoch +32767 on all parts at once, the next 8 -32768."""
+    x = rng.integers(-32768, 32768, size=(n_parts, n_epochs, 2 * spe), dtype=np.int16)
+    x[:, :, :8] = 32767
+    x[:, :, 8:16] = -32768
+    return x.reshape(n_parts, -1)
+
+
+def _edge_gains(rng, n_epochs, n_parts, wide):
+    """Per row one of EDGE_GAINS in a random column, a small one of them in another, random fill small enough that the row sums to at
+    most 65535 (the int32 instance).  wide: every third row all 32767 -- a sum above 65535, the int64 instance for the call."""
+    lim = (65535 - 32767 - 129) // max(1, n_parts - 2)
+    g = rng.integers(0, lim + 1, size=(n_epochs, n_parts))
+    rows = np.arange(n_epochs)
+    col = rng.integers(0, n_parts, size=n_epochs)
+    g[rows, (col + 1) % n_parts] = rng.choice(EDGE_GAINS[:4], size=n_epochs)
+    edge = rng.choice(EDGE_GAINS, size=n_epochs)
+    edge[:len(EDGE_GAINS)] = EDGE_GAINS[:n_epochs]  # every one of them at least once where there are five epochs
+    g[rows, col] = edge
+    assert g.sum(axis=1).max() <= 65535
+    if wide:
+        g[1::3] = 32767
+        assert g.sum(axis=1).max() > 65535
+    return g
+
+
+GUARD = 16  # int16 values behind the output that the kernel must leave alone
+
+
+def _wsum_guarded(eng, spe, parts, gains, epochs_per_model_call=None):
+    """One gal_synth_iq_wsum call against gain_model.wsum (in pieces of whole epochs where asked: the sum is separable per epoch), bytes
+    and saturation count; the output buffer is GUARD values longer than the call and must come back untouched there."""
+    import torch
+
+    devs = [_dev(p) for p in parts]
+    out = torch.full((parts.shape[1] + GUARD,), 0x5a5a, dtype=torch.int16, device="cuda")
+    torch.cuda.synchronize()
+    before = eng.iq_saturated()
+    eng.iq_wsum([d.data_ptr() for d in devs], gains, out.data_ptr())
+    sat = eng.iq_saturated() - before
+    got = out.cpu().numpy()
+    assert (got[parts.shape[1]:] == 0x5a5a).all(), "the kernel wrote behind the last epoch"
+    got = got[:parts.shape[1]]
+    n_epochs = gains.shape[0]
+    step = epochs_per_model_call or n_epochs
+    want_sat = 0
+    for e0 in range(0, n_epochs, step):
+        lo, hi = e0 * spe * 2, min(n_epochs, e0 + step) * spe * 2
+        want, s = gain_model.wsum(parts[:, lo:hi], gains[e0:e0 + step], spe)
+        want_sat += s
+        bad = np.flatnonzero(got[lo:hi] != want)
+        assert bad.size == 0, "%d values differ, the first at value %d = epoch %d, value %d of it" % (
+            bad.size, lo + bad[0], (lo + bad[0]) // (2 * spe), (lo + bad[0]) % (2 * spe))
+    assert sat == want_sat
+    return want_sat
+
+
+# (spe, n_epochs, n_parts) and what _launch must say about it
+GEOMETRIES = {
+    "epochs_beyond_the_grid": (1030, 2051, 3),
+    "uneven_x_stride": (4101, 600, 5),
+    "seven_sample_epochs": (7, 4100, 2),
+    "cli_batch": (260000, 128, 2),
+}
+
+
+def _geometry_holds(name, spe, n_epochs, n_parts):
+    L = _launch(spe, n_epochs)
+    if spe == 1030:
+        # by = 2048 < 2051: blocks y = 0, 1, 2 take a second epoch; cap = 1 < need = 2: the one x block walks 257 vectors in two trips,
+        # the second with one lane; the epochs begin at value offsets 0 and 2 of a vector in turn
+        assert (L["by"], L["y_trips"], n_epochs - L["by"]) == (2048, 2, 3)
+        assert (L["cap"], L["need"], L["bx"]) == (1, 2, 1) and (L["vec"] == 257).all() and (L["x_trips"] == 2).all()
+        assert spe % 4 == 2 and set((np.arange(n_epochs) * spe) % 4) == {0, 2}
+    elif spe == 4101:
+        # cap = 3 < need = 5: three x blocks, stride 768, over 1024 or 1025 vectors: a second trip that 256 or 257 of 768 lanes take
+        assert (L["by"], L["y_trips"]) == (600, 1) and (L["cap"], L["need"], L["bx"], L["x_stride"]) == (3, 5, 3, 768)
+        assert set(L["vec"]) == {1024, 1025} and (L["x_trips"] == 2).all() and set(L["vec"] - 768) == {256, 257}
+        assert spe % 2 == 1 and set((np.arange(n_epochs) * spe) % 4) == {0, 1, 2, 3} and (n_parts // 4, n_parts % 4) == (1, 1)
+    elif spe == 7:
+        # 4100 = 2 x 2048 + 4: two whole rounds of the y grid, four blocks go a third time; one whole vector per epoch, three samples
+        # for the head / tail lanes, at every alignment
+        assert (L["by"], L["y_trips"], n_epochs - 2 * L["by"]) == (2048, 3, 4) and L["bx"] == 1
+        assert (L["vec"] == 1).all() and set((np.arange(n_epochs) * spe) % 4) == {0, 1, 2, 3}
+    else:
+        # 128-epoch batches of 260 000 samples: cap = 16 < need = 254, every lane makes 15 or 16 trips over 65 000 vectors
+        assert (spe, n_epochs) == (260000, 128)
+        assert (L["by"], L["cap"], L["need"], L["bx"], L["x_stride"]) == (128, 16, 254, 16, 4096)
+        assert (L["vec"] == 65000).all() and (L["x_trips"] == 16).all() and 65000 % 4096 != 0
+
+
+@pytest.mark.parametrize("name", list(GEOMETRIES))
+def test_wsum_stride_loops(pkg, name):
+    """Shapes at which blocks take a second epoch (e += gridDim.y) and lanes a second vector (i += stride), with epochs that begin and
+    end inside a 16-byte vector; both instances where three or more parts can sum beyond 65535."""
+    spe, n_epochs, n_parts = GEOMETRIES[name]
+    _geometry_holds(name, spe, n_epochs, n_parts)
+    rng = np.random.default_rng(spe + n_epochs)
+    parts = _edge_parts(rng, n_parts, n_epochs, spe)
+    with pkg.SynthEngine(samples_per_epoch=spe, n_slots=16, device=0) as eng:
+        for wide in (False, True)[: 2 if n_parts >= 3 else 1]:
+            sat = _wsum_guarded(eng, spe, parts, _edge_gains(rng, n_epochs, n_parts, wide), epochs_per_model_call=max(1, 2 ** 21 // spe))
+            assert sat > 0
+
+
+@pytest.mark.parametrize("n_parts,wide", [(k, False) for k in (2, 4, 5, 7, 8, 9, 63, 64)] + [(k, True) for k in (4, 5, 7, 8, 9, 63, 64)])
+def test_wsum_part_counts(pkg, n_parts, wide):
+    """The part loop takes four parts per trip and the rest one by one: 0, 1, 2 and 15, 16 whole trips with every remainder, up to
+    GAL_ENGINE_MAX_CHAN = 64 parts; in int32 (rows that sum to at most 65535) and in int64 (rows of 32767s)."""
+    spe, n_epochs = 1030, 3
+    assert {k // 4 for k in (2, 4, 5, 7, 8, 9, 63, 64)} == {0, 1, 2, 15, 16} and {k % 4 for k in (2, 4, 5, 7, 8, 9, 63, 64)} == {0, 1, 2, 3}
+    rng = np.random.default_rng(7000 + n_parts)
+    parts = _edge_parts(rng, n_parts, n_epochs, spe)
+    with pkg.SynthEngine(samples_per_epoch=spe, n_slots=16, device=0) as eng:
+        sat = _wsum_guarded(eng, spe, parts, _edge_gains(rng, n_epochs, n_parts, wide))
+        assert sat > 0 or not wide
+
+
+INT32_EDGE_ROWS = ([32767, 32767, 1], [32767, 32767, 2], [32767, 32767, 3])  # sums 65535 (the last the int32 instance takes), 65536, 65537
+
+
+def test_wsum_at_the_int32_bound(pkg):
+    """Full scale on every part against rows that sum to 65535, 65536 and 65537: w = -65535 x 32768 = -2 147 450 880 still fits the
+    int32 instance, the other two rows must go to the int64 one (65537 x -32768 < -2^31; tests/test_iq_gain_cpu.py has the
+    arithmetic).  Every value clamps; the count must be the model's."""
+    spe, n_epochs = 1030, 3
+    assert [sum(r) for r in INT32_EDGE_ROWS] == [65535, 65536, 65537]
+    with pkg.SynthEngine(samples_per_epoch=spe, n_slots=16, device=0) as eng:
+        for level in (-32768, 32767):
+            parts = np.full((3, n_epochs * spe * 2), level, dtype=np.int16)
+            for row in INT32_EDGE_ROWS:
+                assert _wsum_guarded(eng, spe, parts, np.tile(row, (n_epochs, 1))) == parts.shape[1]
+            # the three rows in one call (the int64 instance), and the 65535 row between two small ones (the int32 instance)
+            assert _wsum_guarded(eng, spe, parts, np.array(INT32_EDGE_ROWS)) == parts.shape[1]
+            _wsum_guarded(eng, spe, parts, np.array([[1, 0, 128], INT32_EDGE_ROWS[0], [0, 129, 1]]))
+
+
+def test_wsum_gain_table_regrows_between_calls(pkg):
+    """One handle, 3 epochs, then 4100 (the device table of the first call is too small: freed and made anew behind the first call's
+    kernel), then 3 again (the larger table is kept)."""
+    spe, n_parts = 7, 3
+    rng = np.random.default_rng(4100)
+    with pkg.SynthEngine(samples_per_epoch=spe, n_slots=16, device=0) as eng:
+        for n_epochs in (3, 4100, 3):
+            parts = _edge_parts(rng, n_parts, n_epochs, spe)
+            _wsum_guarded(eng, spe, parts, _edge_gains(rng, n_epochs, n_parts, n_epochs == 4100))
