@@ -24,6 +24,9 @@
 // --fir <file> | --fir-lowpass cutoff_hz[,n_taps] (not in the reference): a front-end (IF) FIR filter over the int16 stream, behind noise
 // and interference and in front of the format (gal_synth_iq_fir); the file does not depend on -B.
 //
+// --oversample M (not in the reference): synthesis, gains, noise and interference at M x 2.6 MS/s, then ONE decimating FIR filter back to
+// 2.6 MS/s (gal_synth_iq_firdec) in front of the format; --fir / --fir-lowpass then give the decimator's taps.
+//
 // --monitor <file> (not in the reference): the built-in receiver check -- every --monitor-every'th epoch (default 10) the first 25 code
 // periods of every active channel are despread, in the buffer as it is written (behind noise and format), with the planned replica
 // (gal_synth_correlate); one CSV line per (epoch, PRN) with the measured C/N0 and where the peak lies.  Read-only: the IQ is the same.
@@ -118,6 +121,13 @@ void usage(const char *prog)
            "                   taps in Q14 (16384 = 1.0), one per line, 1..128 of them, sum of |tap| <= 65535\n"
            "  --fir-lowpass <cutoff_hz>[,n_taps] the same with a Hamming-windowed sinc low-pass (n_taps odd, 3..127, default 63; the taps\n"
            "                   are printed on stderr); not together with --fir\n"
+           "  --oversample <M> Synthesise, weight, add noise and interference at M x 2.6 MS/s (M = 2..15) and bring the stream back to\n"
+           "                   2.6 MS/s with one decimating FIR filter in front of the format: the file has the size and rate it has\n"
+           "                   without the option.  --jam frequencies are then admitted up to +-M x 1.3 MHz.  --fir <file> then holds the\n"
+           "                   decimator's taps at the high rate (1..512), --fir-lowpass designs them at the high rate (n_taps odd, 3..511);\n"
+           "                   with neither: a low-pass at 1.17 MHz with 32 M + 1 taps (printed on stderr).  The automatic --iq-shift\n"
+           "                   uses the sigma behind the filter, sigma x sqrt(sum h^2) / 16384.  --monitor needs taps whose\n"
+           "                   (n_taps - 1) is a multiple of 2 M (a delay of whole output samples).  Default -B: max(8, 128 / M)\n"
            "  --monitor <file> Despread the output with the planned replicas and write one CSV line per monitored epoch and PRN:\n"
            "                   time, PRN, planned Doppler, measured C/N0 (composite E1B + E1C), peak ratio, strongest of the delays\n"
            "                   -1 / 0 / +1 half chip and of the Doppler offsets -1 / 0 / +1 bin of 250 Hz; a summary per PRN on stderr\n"
@@ -635,7 +645,7 @@ int main(int argc, char *argv[])
     int batch_epochs = 128, n_writers = -1, sites_gpus = 0, sites_per_gpu = 1;
     const char *iq_format_arg = "ishort", *iq_shift_arg = nullptr;
     const char *monitor_arg = nullptr, *monitor_every_arg = nullptr;
-    const char *fir_arg = nullptr, *fir_lowpass_arg = nullptr;
+    const char *fir_arg = nullptr, *fir_lowpass_arg = nullptr, *oversample_arg = nullptr;
     bool power_model = false;
     const char *antenna_arg = nullptr;
     std::vector<const char *> prn_power_args;
@@ -645,7 +655,7 @@ int main(int argc, char *argv[])
     sc.udp_loopback = 1;              // ... on every interface; the default listener here takes local datagrams only
 
     enum { OPT_STRICT = 1000, OPT_SITES, OPT_WRITERS, OPT_GPUS, OPT_PER_GPU, OPT_EXACT, OPT_SHIFT_TOE, OPT_REF_T, OPT_IQ_FORMAT, OPT_IQ_SHIFT, OPT_CN0, OPT_NOISE_SEED,
-           OPT_NOISE_STREAM, OPT_SIGNAL_GAIN, OPT_MONITOR, OPT_MONITOR_EVERY, OPT_JAM, OPT_POWER_MODEL, OPT_ANTENNA, OPT_PRN_POWER, OPT_FIR, OPT_FIR_LOWPASS };
+           OPT_NOISE_STREAM, OPT_SIGNAL_GAIN, OPT_MONITOR, OPT_MONITOR_EVERY, OPT_JAM, OPT_POWER_MODEL, OPT_ANTENNA, OPT_PRN_POWER, OPT_FIR, OPT_FIR_LOWPASS, OPT_OVERSAMPLE };
     static const struct option long_opts[] = {{"strict", no_argument, nullptr, OPT_STRICT},
                                               {"exact-replay", no_argument, nullptr, OPT_EXACT},
                                               {"shift-toe", no_argument, nullptr, OPT_SHIFT_TOE},
@@ -668,6 +678,7 @@ int main(int argc, char *argv[])
                                               {"prn-power", required_argument, nullptr, OPT_PRN_POWER},
                                               {"fir", required_argument, nullptr, OPT_FIR},
                                               {"fir-lowpass", required_argument, nullptr, OPT_FIR_LOWPASS},
+                                              {"oversample", required_argument, nullptr, OPT_OVERSAMPLE},
                                               {nullptr, 0, nullptr, 0}};
     std::vector<std::string> child_args;  // --sites: everything but -l / -o / --sites / --gpus / --per-gpu / --noise-stream goes to the children
     int opt;
@@ -677,7 +688,7 @@ int main(int argc, char *argv[])
                 child_args.push_back(opt == OPT_STRICT ? "--strict" : opt == OPT_EXACT ? "--exact-replay" : opt == OPT_SHIFT_TOE ? "--shift-toe" : opt == OPT_REF_T ? "--ref-T"
                                      : opt == OPT_IQ_FORMAT ? "--iq-format" : opt == OPT_IQ_SHIFT ? "--iq-shift" : opt == OPT_CN0 ? "--cn0"
                                      : opt == OPT_NOISE_SEED ? "--noise-seed" : opt == OPT_SIGNAL_GAIN ? "--signal-gain" : opt == OPT_MONITOR_EVERY ? "--monitor-every" : opt == OPT_JAM ? "--jam" : opt == OPT_POWER_MODEL ? "--power-model"
-                                     : opt == OPT_ANTENNA ? "--antenna" : opt == OPT_PRN_POWER ? "--prn-power" : opt == OPT_FIR ? "--fir" : opt == OPT_FIR_LOWPASS ? "--fir-lowpass" : "--writers");
+                                     : opt == OPT_ANTENNA ? "--antenna" : opt == OPT_PRN_POWER ? "--prn-power" : opt == OPT_FIR ? "--fir" : opt == OPT_FIR_LOWPASS ? "--fir-lowpass" : opt == OPT_OVERSAMPLE ? "--oversample" : "--writers");
             } else {
                 char name[3] = {'-', (char)opt, 0};
                 child_args.push_back(name);
@@ -743,6 +754,7 @@ int main(int argc, char *argv[])
         case OPT_PRN_POWER: prn_power_args.push_back(optarg); break;
         case OPT_FIR: fir_arg = optarg; break;
         case OPT_FIR_LOWPASS: fir_lowpass_arg = optarg; break;
+        case OPT_OVERSAMPLE: oversample_arg = optarg; break;
         case 'n': case 'g': case 'G': case 'a': case 'p': case 'i': case 'U': case 'b': break;
         case ':':
         case '?':
@@ -823,7 +835,22 @@ int main(int argc, char *argv[])
     }
     const double sig_peak = 4100.0 * power_peak;  // the largest |x| of the signal sum: 4100 in the reference's scenarios
     // noise floor: checked here too.  Without --cn0 nothing below differs from a build without it.
-    const double kSampleRate = 2.6e6;
+    // --oversample M: everything in front of the decimator runs at M x 2.6 MS/s (kSampleRate); the file and --monitor at kOutRate.
+    // Without the option M = 1 and the two are the same number.
+    int osr = 1;
+    if (oversample_arg) {
+        char *end = nullptr;
+        const long v = strtol(oversample_arg, &end, 10);
+        if (!*oversample_arg || *end || v < 2 || v > 15) {
+            fprintf(stderr, "ERROR: --oversample '%s' out of range (2..15: the engine synthesises at up to 40 MS/s).\n", oversample_arg);
+            exit(1);
+        }
+        osr = (int)v;
+    }
+    const bool dec_on = osr > 1;
+    const double kOutRate = 2.6e6;
+    const int kOutSamplesPerEpoch = 260000;
+    const double kSampleRate = (double)osr * 2.6e6;
     bool noise_on = false;
     gal_iq_noise_t noise;
     memset(&noise, 0, sizeof(noise));
@@ -906,14 +933,14 @@ int main(int argc, char *argv[])
         }
         noise_on = true;
         const double sigma = noise.sigma_q4 / 16.0;
-        if (iq_format == GAL_IQ_IBYTE && !iq_shift_arg) {  // the smallest shift with 127 x 2^s >= 4 sigma + the --jam amplitudes
+        if (iq_format == GAL_IQ_IBYTE && !iq_shift_arg && !dec_on) {  // the smallest shift with 127 x 2^s >= 4 sigma + the --jam amplitudes
             iq_shift = 0;
             while (iq_shift < 15 && 127.0 * (double)(1 << iq_shift) < 4.0 * sigma + jam_unit * gain) ++iq_shift;
         }
         if (!sitesfile[0]) {  // (--sites: every child prints its own)
             fprintf(stderr, "Noise floor: C/N0 %g dB-Hz -> sigma %.1f LSB, signal gain %g%s, seed %llu, stream %u", cn0, sigma, gain,
                     signal_gain_arg ? "" : " (chosen)", (unsigned long long)noise.seed, noise.stream);
-            if (iq_format == GAL_IQ_IBYTE) fprintf(stderr, ", --iq-shift %d%s", iq_shift, iq_shift_arg ? "" : " (chosen)");
+            if (iq_format == GAL_IQ_IBYTE && (!dec_on || iq_shift_arg)) fprintf(stderr, ", --iq-shift %d%s", iq_shift, iq_shift_arg ? "" : " (chosen)");
             fprintf(stderr, "\n");
         }
     }
@@ -988,8 +1015,9 @@ int main(int argc, char *argv[])
     }
     // front-end filter: checked here too, before any device work.  Without --fir / --fir-lowpass nothing below differs from a build
     // without them.
-    int16_t fir_taps[GAL_FIR_MAX_TAPS];
+    int16_t fir_taps[GAL_FIRDEC_MAX_TAPS];
     int n_fir = 0;
+    const int fir_max = dec_on ? GAL_FIRDEC_MAX_TAPS : GAL_FIR_MAX_TAPS;  // --oversample: the taps are the decimator's
     if (fir_arg && fir_lowpass_arg) {
         fprintf(stderr, "ERROR: --fir and --fir-lowpass exclude each other.\n");
         exit(1);
@@ -1014,8 +1042,8 @@ int main(int argc, char *argv[])
                 fprintf(stderr, "ERROR: --fir %s, line %d: not an integer tap in -32768..32767 (Q14: 16384 = 1.0).\n", fir_arg, lineno);
                 exit(1);
             }
-            if (n_fir == GAL_FIR_MAX_TAPS) {
-                fprintf(stderr, "ERROR: --fir %s holds more than %d taps.\n", fir_arg, GAL_FIR_MAX_TAPS);
+            if (n_fir == fir_max) {
+                fprintf(stderr, "ERROR: --fir %s holds more than %d taps.\n", fir_arg, fir_max);
                 exit(1);
             }
             fir_taps[n_fir++] = (int16_t)v;
@@ -1025,7 +1053,7 @@ int main(int argc, char *argv[])
             fprintf(stderr, "ERROR: --fir %s holds no tap.\n", fir_arg);
             exit(1);
         }
-        if (gal_synth_fir_check(fir_taps, n_fir) != GAL_OK) {
+        if ((dec_on ? gal_synth_firdec_check(fir_taps, n_fir, osr) : gal_synth_fir_check(fir_taps, n_fir)) != GAL_OK) {
             fprintf(stderr, "ERROR: --fir %s: %s\n", fir_arg, gal_synth_last_error());
             exit(1);
         }
@@ -1044,7 +1072,7 @@ int main(int argc, char *argv[])
             fprintf(stderr, "ERROR: --fir-lowpass '%s' is not cutoff_hz[,n_taps].\n", fir_lowpass_arg);
             exit(1);
         }
-        if (gal_synth_fir_lowpass(fc, kSampleRate, (int32_t)nt, fir_taps) != GAL_OK) {
+        if ((dec_on ? gal_synth_firdec_lowpass(fc, kSampleRate, (int32_t)nt, fir_taps) : gal_synth_fir_lowpass(fc, kSampleRate, (int32_t)nt, fir_taps)) != GAL_OK) {
             fprintf(stderr, "ERROR: --fir-lowpass %s: %s\n", fir_lowpass_arg, gal_synth_last_error());
             exit(1);
         }
@@ -1055,8 +1083,42 @@ int main(int argc, char *argv[])
             fprintf(stderr, "\n");
         }
     }
+    if (dec_on && n_fir == 0) {  // the default decimator: 0.45 x the output rate, a delay of 16 output samples
+        const double fc = 0.45 * kOutRate;
+        n_fir = 32 * osr + 1;
+        if (gal_synth_firdec_lowpass(fc, kSampleRate, n_fir, fir_taps) != GAL_OK) {
+            fprintf(stderr, "ERROR: --oversample %d: %s\n", osr, gal_synth_last_error());
+            exit(1);
+        }
+        if (!sitesfile[0]) {
+            fprintf(stderr, "Front-end filter: low-pass, cutoff %g Hz, %d taps (Q14):", fc, n_fir);
+            for (int k = 0; k < n_fir; ++k) fprintf(stderr, " %d", fir_taps[k]);
+            fprintf(stderr, "\n");
+        }
+    }
     const bool fir_on = n_fir > 0;
-    const int fir_delay = fir_on ? (n_fir - 1) / 2 : 0;  // of a symmetric filter, in samples: what --monitor follows
+    // the delay of a symmetric filter, in OUTPUT samples: what --monitor follows
+    int fir_delay = fir_on ? (n_fir - 1) / 2 : 0;
+    if (dec_on) {
+        if (monitor_arg && (n_fir - 1) % (2 * osr) != 0) {
+            fprintf(stderr, "ERROR: --monitor with --oversample %d needs taps whose (n_taps - 1) is a multiple of %d: %d taps delay the stream by %g output samples, "
+                            "and the monitor follows whole samples only.\n", osr, 2 * osr, n_fir, (n_fir - 1) / (2.0 * osr));
+            exit(1);
+        }
+        fir_delay = (n_fir - 1) / (2 * osr);
+        if (iq_format == GAL_IQ_IBYTE && !iq_shift_arg && noise_on) {
+            // the smallest shift with 127 x 2^s >= 4 sigma' + the --jam amplitudes, sigma' = sigma sqrt(sum h^2) / 16384 behind the filter
+            double e2 = 0.0;
+            for (int k = 0; k < n_fir; ++k) e2 += (double)fir_taps[k] * (double)fir_taps[k];
+            const double sigma_out = noise.sigma_q4 / 16.0 * sqrt(e2) / 16384.0;
+            iq_shift = 0;
+            while (iq_shift < 15 && 127.0 * (double)(1 << iq_shift) < 4.0 * sigma_out + jam_unit * gain) ++iq_shift;
+            if (!sitesfile[0]) fprintf(stderr, "Decimator: sigma %.1f LSB behind the filter, --iq-shift %d (chosen)\n", sigma_out, iq_shift);
+        }
+        if (!sitesfile[0])
+            fprintf(stderr, "Oversampling: %d x 2.6 MS/s = %g MS/s in front of the decimator, %d taps, delay %g output samples\n", osr, kSampleRate / 1e6,
+                    n_fir, (n_fir - 1) / (2.0 * osr));
+    }
     const double iq_bytes_per_sample = (double)gal_synth_iq_bytes(iq_format, 4) / 4.0;
     if (sitesfile[0]) {
         // several listeners cannot share a port: the sites run without the position listener unless -P names a base port, in
@@ -1072,6 +1134,7 @@ int main(int argc, char *argv[])
         printf("[+] File sink not specified. Using galileosim.%s\n", kIqNames[iq_format]);
         snprintf(outfile, sizeof(outfile), "galileosim.%s", kIqNames[iq_format]);
     }
+    if (dec_on && !have_batch) batch_epochs = 128 / osr > 8 ? 128 / osr : 8;  // the device buffers keep their size
     if (realtime && !have_batch) batch_epochs = 1;  // paced output: position updates take effect within 0.1 s
     if (batch_epochs < 1) batch_epochs = 1;
     sc.nav_file = navfile;
@@ -1112,15 +1175,15 @@ int main(int argc, char *argv[])
     gal_synth_cfg_t cfg;
     memset(&cfg, 0, sizeof(cfg));
     cfg.sample_rate = kSampleRate;
-    cfg.samples_per_epoch = 260000;
+    cfg.samples_per_epoch = osr * kOutSamplesPerEpoch;
     cfg.n_slots = sc.n_slots;
     cfg.device = getenv("GAL_DEVICE") ? atoi(getenv("GAL_DEVICE")) : -1;
     if (cboc) cfg.flags |= GAL_CFG_CBOC;
     if (exact_replay) cfg.flags |= GAL_CFG_EXACT_REPLAY;
     // bytes per epoch in the output format: the per-batch split of the copies cuts at epoch boundaries, so every piece must be whole
     // bytes -- for ibit 260 000 % 4 == 0
-    const size_t epoch_bytes = gal_synth_iq_bytes(iq_format, (size_t)cfg.samples_per_epoch);
-    if (iq_format == GAL_IQ_IBIT && cfg.samples_per_epoch % 4 != 0) {
+    const size_t epoch_bytes = gal_synth_iq_bytes(iq_format, (size_t)kOutSamplesPerEpoch);
+    if (iq_format == GAL_IQ_IBIT && kOutSamplesPerEpoch % 4 != 0) {
         fprintf(stderr, "ERROR: ibit needs a multiple of 4 samples per epoch.\n");
         exit(1);
     }
@@ -1148,7 +1211,7 @@ int main(int argc, char *argv[])
         exit(1);
     }
     stage("gal_synth_create");
-    if (fir_on && gal_synth_fir_set(eng, fir_taps, n_fir) != GAL_OK) {
+    if (fir_on && (dec_on ? gal_synth_firdec_set(eng, fir_taps, n_fir, osr, 0) : gal_synth_fir_set(eng, fir_taps, n_fir)) != GAL_OK) {
         fprintf(stderr, "ERROR: %s\n", gal_synth_last_error());
         exit(1);
     }
@@ -1170,7 +1233,7 @@ int main(int argc, char *argv[])
         }
         d_out[i] = d_iq[i];
         if (fir_on) {
-            if (hipMalloc((void **)&d_fir[i], (size_t)cfg.samples_per_epoch * 4 * batch_epochs) != hipSuccess) {
+            if (hipMalloc((void **)&d_fir[i], (size_t)kOutSamplesPerEpoch * 4 * batch_epochs) != hipSuccess) {
                 fprintf(stderr, "ERROR: buffer allocation failed\n");
                 exit(1);
             }
@@ -1194,7 +1257,7 @@ int main(int argc, char *argv[])
     memset(&mon_shape, 0, sizeof(mon_shape));
     mon_shape.max_periods = kMonPeriods;
     mon_shape.delay_step = 1;
-    mon_shape.dopp_step = (int32_t)llround(kMonBinHz / kSampleRate * 4294967296.0);
+    mon_shape.dopp_step = (int32_t)llround(kMonBinHz / kOutRate * 4294967296.0);
     mon_shape.dopp0 = -mon_shape.dopp_step;
     mon_shape.n_dopp = 3;
     const size_t mon_epochs_max = (size_t)(batch_epochs + monitor_every - 1) / monitor_every + 1;
@@ -1344,7 +1407,7 @@ int main(int argc, char *argv[])
             }
             for (int e = 0; e < n; ++e) {
                 if ((emitted + e) % monitor_every) continue;
-                const size_t ob = gal_synth_iq_bytes(iq_format, (size_t)e * cfg.samples_per_epoch);
+                const size_t ob = gal_synth_iq_bytes(iq_format, (size_t)e * kOutSamplesPerEpoch);
                 int skip = iq_format == GAL_IQ_IBIT ? (int)((16 - ob % 16) % 16) * 4 : 0;
                 if (fir_on && skip < fir_delay) {  // the filtered stream lags by fir_delay: start there or later, on the same 16-byte grid
                     const int g = iq_format == GAL_IQ_IBIT ? 64 : iq_format == GAL_IQ_IBYTE ? 8 : 4;  // samples per 16 bytes
@@ -1354,7 +1417,7 @@ int main(int argc, char *argv[])
                     const gal_chan_epoch_t &rec = rows_ptr[(size_t)e * sc.n_slots + s];
                     if (rec.prn <= 0) continue;
                     gal_corr_req_t q = mon_shape;
-                    if (gal_corr_from_epoch(&rec, kSampleRate, skip - fir_delay, &q) != GAL_OK) continue;  // (a record the monitor cannot follow)
+                    if (gal_corr_from_epoch(&rec, kOutRate, skip - fir_delay, &q) != GAL_OK) continue;  // (a record the monitor cannot follow)
                     MonEntry me;
                     me.t = (emitted + e) * 0.1;
                     me.f_carr = rec.f_carr;
@@ -1408,7 +1471,7 @@ int main(int argc, char *argv[])
             break;
         }
         // (the stream has drained up to this batch's synthesis: the sums of the batch before it are on the host)
-        if (monitor_fp && mon[cur ^ 1].pending) monitor_flush(mon[cur ^ 1], monitor_fp, kSampleRate, mon_shape, mon_sum);
+        if (monitor_fp && mon[cur ^ 1].pending) monitor_flush(mon[cur ^ 1], monitor_fp, kOutRate, mon_shape, mon_sum);
         const double tb_synth = ms_since(tb0);
         if (batch_timing)
             fprintf(stderr, "[timing] batch at %7.2f ms: %3d epochs, waited %.2f ms for rows, %.2f for a free slot, %s %.2f\n",
@@ -1418,13 +1481,24 @@ int main(int argc, char *argv[])
         if (fir_on) {
             // noise / interference into the int16 batch in place, the filter into d_fir[cur], the plain format conversion from there
             // (ishort: the copies read d_fir[cur] itself); the filter's history runs on from batch to batch inside the handle
-            const size_t n_samples = (size_t)n * cfg.samples_per_epoch;
+            // --oversample: the batch is n x M x 260 000 samples up to the decimator, which keeps n x 260 000 of them
+            const size_t n_samples = (size_t)n * cfg.samples_per_epoch, n_kept = (size_t)n * kOutSamplesPerEpoch;
             int crc = GAL_OK;
             if (mix_on)
                 crc = gal_synth_iq_convert_interf(eng, d_iq[cur], n_samples, (uint64_t)emitted * (uint64_t)cfg.samples_per_epoch, &noise, interf, n_jam,
                                                   GAL_IQ_ISHORT, 0, d_iq[cur]);
-            if (crc == GAL_OK) crc = gal_synth_iq_fir(eng, d_iq[cur], n_samples, d_fir[cur]);
-            if (crc == GAL_OK && iq_format != GAL_IQ_ISHORT) crc = gal_synth_iq_convert(eng, d_fir[cur], n_samples, iq_format, iq_shift, d_out[cur]);
+            if (crc == GAL_OK && dec_on) {
+                size_t got = 0;
+                crc = gal_synth_iq_firdec(eng, d_iq[cur], n_samples, d_fir[cur], &got);
+                if (crc == GAL_OK && got != n_kept) {
+                    fprintf(stderr, "\nERROR: the decimator kept %zu samples of the batch, not %zu\n", got, n_kept);
+                    rc = 1;
+                    break;
+                }
+            } else if (crc == GAL_OK) {
+                crc = gal_synth_iq_fir(eng, d_iq[cur], n_samples, d_fir[cur]);
+            }
+            if (crc == GAL_OK && iq_format != GAL_IQ_ISHORT) crc = gal_synth_iq_convert(eng, d_fir[cur], n_kept, iq_format, iq_shift, d_out[cur]);
             if (crc != GAL_OK) {
                 fprintf(stderr, "\nERROR: %s\n", gal_synth_last_error());
                 rc = 1;
@@ -1459,8 +1533,8 @@ int main(int argc, char *argv[])
             while (i < mon_epoch.size() && mon_ok) {
                 size_t j = i;
                 while (j < mon_epoch.size() && mon_epoch[j] == mon_epoch[i]) ++j;
-                const size_t ob = gal_synth_iq_bytes(iq_format, (size_t)mon_epoch[i] * cfg.samples_per_epoch) + gal_synth_iq_bytes(iq_format, (size_t)mon_skip[i]);
-                mon_ok = gal_synth_correlate(eng, (const char *)d_out[cur] + ob, iq_format, (size_t)cfg.samples_per_epoch - mon_skip[i],
+                const size_t ob = gal_synth_iq_bytes(iq_format, (size_t)mon_epoch[i] * kOutSamplesPerEpoch) + gal_synth_iq_bytes(iq_format, (size_t)mon_skip[i]);
+                mon_ok = gal_synth_correlate(eng, (const char *)d_out[cur] + ob, iq_format, (size_t)kOutSamplesPerEpoch - mon_skip[i],
                                              &mon_reqs[2 * i], (int32_t)(2 * (j - i)), (int64_t *)(mon[cur].dev + mon[cur].entries[i].off)) == GAL_OK;
                 i = j;
             }
@@ -1527,7 +1601,7 @@ int main(int argc, char *argv[])
     if (monitor_fp) {
         if (hipStreamSynchronize(stream) != hipSuccess) rc = 1;
         for (int i = 0; i < 2 && rc == 0; ++i)
-            if (mon[i].pending) monitor_flush(mon[i], monitor_fp, kSampleRate, mon_shape, mon_sum);
+            if (mon[i].pending) monitor_flush(mon[i], monitor_fp, kOutRate, mon_shape, mon_sum);
         if (fclose(monitor_fp) != 0) {
             fprintf(stderr, "ERROR: writing the monitor file %s failed\n", monitor_arg);
             rc = 1;

@@ -96,6 +96,9 @@ hipError_t galk_launch_iq_pass(int format, const int16_t *in, uint64_t n_val, ui
 hipError_t galk_launch_iq_fir(const int16_t *in, int16_t *out, uint64_t n, const uint32_t *table_dev, int n_trips, int hs, const uint32_t *hist_in,
                               uint32_t *hist_out, unsigned long long *sat, hipStream_t st);
 void galk_fir_table(const int16_t *h, int n_taps, uint32_t *table, int *n_trips, int *hs);
+hipError_t galk_launch_iq_firdec(const int16_t *in, int16_t *out, uint64_t n, uint64_t n_out, int i0, int n_taps, int decim,
+                                 const uint32_t *table_dev, const uint32_t *hist_in, uint32_t *hist_out, unsigned long long *sat, hipStream_t st);
+int galk_firdec_table(const int16_t *h, int n_taps, int decim, uint32_t *table, int *trips);
 hipError_t galk_launch_iq_wsum(const int16_t *const *parts_dev, const int *gain_dev, int n_parts, int n_epochs, int samples_per_epoch, int wide,
                                int16_t *out, unsigned long long *sat, hipStream_t st);
 hipError_t galk_launch_corr(int format, const void *buf, uint64_t n_eff, uint64_t code_ph0, uint64_t code_dph, uint32_t carr_ph0,
@@ -345,6 +348,14 @@ struct gal_synth {
     int fir_cur = 0;                              // the history buffer the next call reads (it writes the other)
     hipEvent_t ev_fir = nullptr;
     bool fir_pending = false;
+    // gal_synth_firdec_set / gal_synth_iq_firdec (iq_firdec.hip): the same for the decimator, a slot of its own; fd_phase = the
+    // global index of the next input sample modulo fd_decim
+    uint32_t *d_fd = nullptr;
+    uint32_t *h_fd = nullptr;
+    int fd_taps = 0, fd_decim = 0, fd_phase = 0;  // fd_taps 0: no decimator set
+    int fd_cur = 0;
+    hipEvent_t ev_fd = nullptr;
+    bool fd_pending = false;
 };
 
 // The stream the handle works on: the caller's (gal_synth_set_stream), or one of its own, made at first need.
@@ -580,6 +591,9 @@ int gal_synth_destroy(gal_synth_t *h)
     if (h->d_fir) hipFree(h->d_fir);
     if (h->h_fir) hipHostFree(h->h_fir);
     if (h->ev_fir) hipEventDestroy(h->ev_fir);
+    if (h->d_fd) hipFree(h->d_fd);
+    if (h->h_fd) hipHostFree(h->h_fd);
+    if (h->ev_fd) hipEventDestroy(h->ev_fd);
     if (h->d_lut) hipFree(h->d_lut);
     if (h->d_str) hipFree(h->d_str);
     if (h->h_up) hipHostFree(h->h_up);
@@ -2021,16 +2035,16 @@ int gal_synth_fir_check(const int16_t *taps_q14, int32_t n_taps)
     return GAL_OK;
 }
 
-int gal_synth_fir_lowpass(double cutoff_hz, double sample_rate, int32_t n_taps, int16_t *taps_q14)
+// the Hamming-windowed sinc of both low-pass designers, as include/galsynth.h states it; `check` = the admission of the caller's filter
+static int lowpass_design(const char *who, double cutoff_hz, double sample_rate, int32_t n_taps, int max_odd, int16_t *taps_q14)
 {
-    const char *who = "gal_synth_fir_lowpass";
     if (!taps_q14) return fail(GAL_E_INVAL, "%s: null taps", who);
-    if (n_taps < 3 || n_taps > 127 || !(n_taps & 1)) return fail(GAL_E_INVAL, "%s: %d taps (odd, 3..127)", who, n_taps);
+    if (n_taps < 3 || n_taps > max_odd || !(n_taps & 1)) return fail(GAL_E_INVAL, "%s: %d taps (odd, 3..%d)", who, n_taps, max_odd);
     if (!std::isfinite(cutoff_hz) || !std::isfinite(sample_rate) || sample_rate <= 0.0 || !(cutoff_hz > 0.0) || !(cutoff_hz < sample_rate / 2))
         return fail(GAL_E_INVAL, "%s: cutoff %g Hz must lie inside (0, sample_rate / 2 = %g Hz)", who, cutoff_hz, sample_rate / 2);
     const double pi = 3.14159265358979323846, fc = cutoff_hz / sample_rate;
     const int M = n_taps - 1;
-    double ws[GAL_FIR_MAX_TAPS], S = 0.0;
+    double ws[GAL_FIRDEC_MAX_TAPS], S = 0.0;
     for (int k = 0; k <= M; ++k) {
         const double t = (double)(k - M / 2);
         const double s = k == M / 2 ? 2.0 * fc : sin(2.0 * pi * fc * t) / (pi * t);
@@ -2039,21 +2053,28 @@ int gal_synth_fir_lowpass(double cutoff_hz, double sample_rate, int32_t n_taps, 
         S += ws[k];
     }
     if (!std::isfinite(S) || S == 0.0) return fail(GAL_E_INVAL, "%s: the window's sum is %g", who, S);
-    long long q[GAL_FIR_MAX_TAPS], sum = 0;
+    long long q[GAL_FIRDEC_MAX_TAPS], sum = 0;
     for (int k = 0; k <= M; ++k) {
         q[k] = llround(16384.0 * ws[k] / S);
         sum += q[k];
     }
     q[M / 2] += 16384 - sum;
-    int16_t out[GAL_FIR_MAX_TAPS];
+    int16_t out[GAL_FIRDEC_MAX_TAPS];
+    long asum = 0;
     for (int k = 0; k <= M; ++k) {
         if (q[k] < -32768 || q[k] > 32767) return fail(GAL_E_INVAL, "%s: tap %d = %lld does not fit an int16", who, k, q[k]);
         out[k] = (int16_t)q[k];
+        asum += std::abs((long)out[k]);
     }
-    const int rc = gal_synth_fir_check(out, n_taps);
-    if (rc) return rc;
+    if (asum > 65535)
+        return fail(GAL_E_INVAL, "%s: the taps' absolute values sum to %ld, more than 65535 (16384 = 1.0): the int32 accumulator could wrap", who, asum);
     memcpy(taps_q14, out, sizeof(int16_t) * (size_t)n_taps);
     return GAL_OK;
+}
+
+int gal_synth_fir_lowpass(double cutoff_hz, double sample_rate, int32_t n_taps, int16_t *taps_q14)
+{
+    return lowpass_design("gal_synth_fir_lowpass", cutoff_hz, sample_rate, n_taps, GAL_FIR_MAX_TAPS - 1, taps_q14);
 }
 
 int gal_synth_fir_set(gal_synth_t *h, const int16_t *taps_q14, int32_t n_taps)
@@ -2131,6 +2152,123 @@ int gal_synth_iq_fir(gal_synth_t *h, const int16_t *in_dev, size_t n_samples, in
     h->fir_cur ^= 1;
     HIP_TRY(hipEventRecord(h->ev_fir, st));
     h->fir_pending = true;
+    return GAL_OK;
+}
+
+// ---- decimating front-end filter (iq_firdec.hip) --------------------------------------------------------------------------------------
+static constexpr int kFdTableWords = 640;  // min(M, T) branches x trips x 4 words <= T - 1 + 5 M (galk_firdec_table checks it)
+static constexpr int kFdHist = 512;        // complex samples of history, as iq_firdec.hip keeps them
+
+int gal_synth_firdec_check(const int16_t *taps_q14, int32_t n_taps, int32_t decim)
+{
+    const char *who = "gal_synth_firdec_check";
+    if (!taps_q14) return fail(GAL_E_INVAL, "%s: null taps", who);
+    if (n_taps < 1 || n_taps > GAL_FIRDEC_MAX_TAPS) return fail(GAL_E_INVAL, "%s: %d taps (1..%d)", who, n_taps, GAL_FIRDEC_MAX_TAPS);
+    if (decim < 2 || decim > GAL_FIRDEC_MAX_DECIM) return fail(GAL_E_INVAL, "%s: decimation %d (2..%d)", who, decim, GAL_FIRDEC_MAX_DECIM);
+    long sum = 0;
+    for (int k = 0; k < n_taps; ++k) sum += std::abs((long)taps_q14[k]);
+    if (sum > 65535)
+        return fail(GAL_E_INVAL, "%s: the taps' absolute values sum to %ld, more than 65535 (16384 = 1.0): the int32 accumulator could wrap", who, sum);
+    return GAL_OK;
+}
+
+int gal_synth_firdec_lowpass(double cutoff_hz, double sample_rate_in, int32_t n_taps, int16_t *taps_q14)
+{
+    return lowpass_design("gal_synth_firdec_lowpass", cutoff_hz, sample_rate_in, n_taps, GAL_FIRDEC_MAX_TAPS - 1, taps_q14);
+}
+
+uint64_t gal_synth_firdec_out_samples(uint64_t first_sample, uint64_t n_in, int32_t decim)
+{
+    if (decim < 2 || decim > GAL_FIRDEC_MAX_DECIM || first_sample + n_in < first_sample) return 0;
+    const uint64_t M = (uint64_t)decim, end = first_sample + n_in;
+    // ceil(a / M) = a / M + (a % M != 0), without a + M - 1 (which could wrap)
+    return (end / M + (end % M != 0)) - (first_sample / M + (first_sample % M != 0));
+}
+
+int gal_synth_firdec_set(gal_synth_t *h, const int16_t *taps_q14, int32_t n_taps, int32_t decim, uint64_t first_sample)
+{
+    const char *who = "gal_synth_firdec_set";
+    if (!h) return fail(GAL_E_INVAL, "null handle");
+    if (n_taps != 0) {
+        const int rc = gal_synth_firdec_check(taps_q14, n_taps, decim);
+        if (rc) return rc;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->fd_pending) {  // the table and the histories belong to the kernel in flight
+        HIP_TRY(hipEventSynchronize(h->ev_fd));
+        h->fd_pending = false;
+    }
+    if (n_taps == 0) {
+        if (h->d_fd) hipFree(h->d_fd);
+        if (h->h_fd) hipHostFree(h->h_fd);
+        h->d_fd = h->h_fd = nullptr;
+        h->fd_taps = 0;
+        return GAL_OK;
+    }
+    hipStream_t st = handle_stream(h);
+    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
+    const size_t table_bytes = sizeof(uint32_t) * kFdTableWords, bytes = table_bytes + 2 * sizeof(uint32_t) * kFdHist;
+    if (!h->ev_fd) HIP_TRY(hipEventCreateWithFlags(&h->ev_fd, hipEventDisableTiming));
+    if (!h->d_fd) {
+        uint32_t *d = nullptr, *p = nullptr;
+        if (hipMalloc((void **)&d, bytes) != hipSuccess || hipHostMalloc((void **)&p, table_bytes, hipHostMallocDefault) != hipSuccess) {
+            if (d) hipFree(d);
+            return fail(GAL_E_NOMEM, "%s: the filter table of %zu bytes could not be allocated", who, bytes);
+        }
+        h->d_fd = d;
+        h->h_fd = p;
+        h->fd_taps = 0;
+    }
+    // from here on the decimator in force is gone: a failure leaves the handle without one
+    h->fd_taps = 0;
+    memset(h->h_fd, 0, table_bytes);
+    int trips = 0;
+    const int words = galk_firdec_table(taps_q14, n_taps, decim, h->h_fd, &trips);
+    if (words <= 0 || words > kFdTableWords) return fail(GAL_E_INVAL, "%s: no kernel shape for %d taps at decimation %d", who, n_taps, decim);
+    HIP_TRY(hipMemcpyAsync(h->d_fd, h->h_fd, table_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(h->d_fd + kFdTableWords, 0, 2 * sizeof(uint32_t) * kFdHist, st));
+    HIP_TRY(hipEventRecord(h->ev_fd, st));  // (the upload reads h_fd: the next call waits for it as for a kernel)
+    h->fd_pending = true;
+    h->fd_taps = n_taps;
+    h->fd_decim = decim;
+    h->fd_phase = (int)(first_sample % (uint64_t)decim);
+    h->fd_cur = 0;
+    return GAL_OK;
+}
+
+int gal_synth_iq_firdec(gal_synth_t *h, const int16_t *in_dev, size_t n_in, int16_t *out_dev, size_t *n_out)
+{
+    const char *who = "gal_synth_iq_firdec";
+    if (!h) return fail(GAL_E_INVAL, "null handle");
+    if (!n_out) return fail(GAL_E_INVAL, "%s: null n_out", who);
+    if (!in_dev || !out_dev || ((uintptr_t)in_dev & 15) || ((uintptr_t)out_dev & 15))
+        return fail(GAL_E_INVAL, "%s: device pointers must be non-null and 16-byte aligned", who);
+    if ((uint64_t)n_in >> 41) return fail(GAL_E_INVAL, "%s: n_in must be below 2^41", who);
+    if (!h->fd_taps) return fail(GAL_E_STATE, "%s: no decimator set (call gal_synth_firdec_set first)", who);
+    if (n_in == 0) {
+        *n_out = 0;
+        return GAL_OK;
+    }
+    const uint64_t outs = gal_synth_firdec_out_samples((uint64_t)h->fd_phase, (uint64_t)n_in, h->fd_decim);
+    const size_t in_bytes = 4 * n_in, out_bytes = 4 * (size_t)outs;
+    const char *x = (const char *)in_dev, *o = (const char *)out_dev;
+    if (x < o + out_bytes && o < x + in_bytes) return fail(GAL_E_INVAL, "%s: input and output overlap (tiles read their neighbours' input)", who);
+    if (hits_batch_in_flight(h, in_dev, in_bytes)) return fail(GAL_E_STATE, "%s: input of the batch in flight (call gal_synth_finish first)", who);
+    if (outs && hits_batch_in_flight(h, out_dev, out_bytes)) return fail(GAL_E_STATE, "%s: output of the batch in flight (call gal_synth_finish first)", who);
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = handle_stream(h);
+    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
+    const int rc = ensure_sat_counter(h, st);
+    if (rc) return rc;
+    uint32_t *const hist = h->d_fd + kFdTableWords;
+    const int i0 = (h->fd_decim - h->fd_phase) % h->fd_decim;  // the local index of the first input whose global index M divides
+    HIP_TRY(galk_launch_iq_firdec(in_dev, out_dev, (uint64_t)n_in, outs, i0, h->fd_taps, h->fd_decim, h->d_fd, hist + h->fd_cur * kFdHist,
+                                  hist + (h->fd_cur ^ 1) * kFdHist, h->d_iq_sat, st));
+    h->fd_cur ^= 1;
+    h->fd_phase = (int)(((uint64_t)h->fd_phase + (uint64_t)n_in) % (uint64_t)h->fd_decim);
+    HIP_TRY(hipEventRecord(h->ev_fd, st));
+    h->fd_pending = true;
+    *n_out = (size_t)outs;
     return GAL_OK;
 }
 

@@ -35,6 +35,8 @@ GAL_GAIN_MAX = 32767
 GAL_GAIN_PATTERN_LEN = 37
 GAL_FIR_MAX_TAPS = 128  # front-end filter (gal_synth_fir_set): taps in Q14
 GAL_FIR_UNITY = 16384
+GAL_FIRDEC_MAX_TAPS = 512  # decimating front-end filter (gal_synth_firdec_set)
+GAL_FIRDEC_MAX_DECIM = 16
 GAL_ENGINE_MAX_CHAN = 64
 
 # gal_chan_epoch_t (176 bytes)
@@ -186,6 +188,11 @@ EXPORTED_SYMBOLS = (
     "gal_synth_fir_lowpass",
     "gal_synth_fir_set",
     "gal_synth_iq_fir",
+    "gal_synth_firdec_check",
+    "gal_synth_firdec_lowpass",
+    "gal_synth_firdec_out_samples",
+    "gal_synth_firdec_set",
+    "gal_synth_iq_firdec",
     "gal_synth_corr_out_bytes",
     "gal_synth_correlate",
     "gal_tables_e1b",
@@ -270,6 +277,16 @@ def load_library(hooks=False):
     lib.gal_synth_fir_set.restype = ctypes.c_int
     lib.gal_synth_iq_fir.argtypes = [vp, vp, ctypes.c_size_t, vp]
     lib.gal_synth_iq_fir.restype = ctypes.c_int
+    lib.gal_synth_firdec_check.argtypes = [vp, i32, i32]
+    lib.gal_synth_firdec_check.restype = ctypes.c_int
+    lib.gal_synth_firdec_lowpass.argtypes = [ctypes.c_double, ctypes.c_double, i32, vp]
+    lib.gal_synth_firdec_lowpass.restype = ctypes.c_int
+    lib.gal_synth_firdec_out_samples.argtypes = [ctypes.c_uint64, ctypes.c_uint64, i32]
+    lib.gal_synth_firdec_out_samples.restype = ctypes.c_uint64
+    lib.gal_synth_firdec_set.argtypes = [vp, vp, i32, i32, ctypes.c_uint64]
+    lib.gal_synth_firdec_set.restype = ctypes.c_int
+    lib.gal_synth_iq_firdec.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.POINTER(ctypes.c_size_t)]
+    lib.gal_synth_iq_firdec.restype = ctypes.c_int
     lib.gal_synth_corr_out_bytes.argtypes = [ctypes.POINTER(_CorrReq)]
     lib.gal_synth_corr_out_bytes.restype = ctypes.c_size_t
     lib.gal_synth_correlate.argtypes = [vp, vp, i32, ctypes.c_size_t, ctypes.POINTER(_CorrReq), i32, vp]
@@ -396,6 +413,33 @@ def fir_lowpass(cutoff_hz, sample_rate, n_taps=63):
     if rc != 0:
         raise GalSynthError(rc, lib.gal_synth_last_error().decode())
     return t[: int(n_taps)].copy()
+
+
+def firdec_check(taps, decim):
+    """gal_synth_firdec_check (no GPU needed): raises GalSynthError unless the Q14 taps and the decimation are admitted -- 1 ..
+    GAL_FIRDEC_MAX_TAPS taps with sum |h| <= 65535, decim 2 .. GAL_FIRDEC_MAX_DECIM."""
+    lib = load_library()
+    t = _fir_taps(taps, "firdec_check")
+    rc = lib.gal_synth_firdec_check(t.ctypes.data if t.size else None, int(t.size), int(decim))
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+
+
+def firdec_lowpass(cutoff_hz, sample_rate_in, n_taps):
+    """gal_synth_firdec_lowpass (no GPU needed): the low-pass of fir_lowpass for the decimator, n_taps odd, 3 .. 511, designed at the
+    rate of the decimator's INPUT stream."""
+    lib = load_library()
+    t = np.zeros(GAL_FIRDEC_MAX_TAPS, dtype=np.int16)
+    rc = lib.gal_synth_firdec_lowpass(float(cutoff_hz), float(sample_rate_in), int(n_taps), t.ctypes.data)
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+    return t[: int(n_taps)].copy()
+
+
+def firdec_out_samples(first_sample, n_in, decim):
+    """gal_synth_firdec_out_samples (no GPU needed): the outputs a call of n_in inputs keeps when its first input has the global index
+    first_sample -- the number of m with first_sample <= decim * m < first_sample + n_in."""
+    return int(load_library().gal_synth_firdec_out_samples(int(first_sample), int(n_in), int(decim)))
 
 
 def _corr_struct(req):
@@ -631,6 +675,23 @@ class SynthEngine:
         address in_ptr -> out_ptr (both 16-byte aligned, not overlapping).  The handle carries the filter's history from call to call:
         any cut of a stream into calls gives the same bytes.  iq_saturated() is the fence and counts the clamped values."""
         self._check(self._lib.gal_synth_iq_fir(self._h, ctypes.c_void_p(int(in_ptr)), int(n_samples), ctypes.c_void_p(int(out_ptr))))
+
+    def firdec_set(self, taps, decim=2, first_sample=0):
+        """gal_synth_firdec_set: give the handle the decimating front-end filter `taps` (int16 Q14, 1 .. GAL_FIRDEC_MAX_TAPS, sum |h|
+        <= 65535) at the decimation decim (2 .. GAL_FIRDEC_MAX_DECIM) and start a stream whose next input sample has the global index
+        first_sample (the history is zeroed); None or an empty sequence frees it.  Independent of fir_set."""
+        t = _fir_taps(taps if taps is not None else [], "firdec_set")
+        self._check(self._lib.gal_synth_firdec_set(self._h, t.ctypes.data if t.size else None, int(t.size), int(decim), int(first_sample)))
+
+    def iq_firdec(self, in_ptr, n_in, out_ptr):
+        """gal_synth_iq_firdec, enqueued on the handle's stream: consume the next n_in complex int16 input samples at device address
+        in_ptr and write the outputs whose decim * m falls into them from device address out_ptr on (both 16-byte aligned, not
+        overlapping); returns their number.  Any cut of the input stream into calls gives the same bytes.  iq_saturated() is the fence
+        and counts the clamped values."""
+        n_out = ctypes.c_size_t(0)
+        self._check(self._lib.gal_synth_iq_firdec(self._h, ctypes.c_void_p(int(in_ptr)), int(n_in), ctypes.c_void_p(int(out_ptr)),
+                                                  ctypes.byref(n_out)))
+        return int(n_out.value)
 
     def run_gains(self, params, gain_q7, iq_dev_ptr, state_in=None):
         """gal_synth_run_gains: the batch with per-slot, per-epoch Q7 gains gain_q7 [n_epochs, n_slots] (128 = unity) into the device

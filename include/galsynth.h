@@ -481,6 +481,51 @@ int gal_synth_fir_set(gal_synth_t *h, const int16_t *taps_q14, int32_t n_taps);
 int gal_synth_iq_fir(gal_synth_t *h, const int16_t *in_dev, size_t n_samples, int16_t *out_dev);
 
 /*
+ * Decimating front-end filter: the stream is synthesised, weighted and given its noise and interference at M
+ * times the output rate, and ONE pass filters it and keeps every M-th sample -- what a front-end does that filters wide and then
+ * samples.  Only the kept outputs are computed.  A FIXED INTEGER FUNCTION of its inputs (tests/firdec_model.py states it in numpy).
+ *
+ * x[n] = (I, Q)[n], the complex int16 samples of the WHOLE INPUT (high-rate) stream, n the global index, x[n] = 0 for n < 0;
+ * h[0 .. T-1] real int16 taps in Q14, 1 <= T <= GAL_FIRDEC_MAX_TAPS; the decimation 2 <= M <= GAL_FIRDEC_MAX_DECIM.  Per rail:
+ *   a[m] = sum over k of h[k] x[M m - k]
+ *   y[m] = clamp((a[m] + 8192) >> 14, -32768, 32767)          (arithmetic shift)
+ * so y[m] is sample M m of what gal_synth_iq_fir defines for the same taps.  A value the clamp changes counts once in the handle's
+ * saturation counter; only kept outputs count.  Taps are admitted only with sum |h[k]| <= 65535: a is exact in an int32 for any
+ * int16 input, in any order of accumulation.  A symmetric filter of T taps with T - 1 a multiple of 2 M delays the OUTPUT stream by
+ * (T - 1) / (2 M) samples.
+ */
+#define GAL_FIRDEC_MAX_TAPS 512
+#define GAL_FIRDEC_MAX_DECIM 16
+/* GAL_OK if taps and decimation are admitted, else GAL_E_INVAL: a null pointer, n_taps outside 1..GAL_FIRDEC_MAX_TAPS, decim outside
+ * 2..GAL_FIRDEC_MAX_DECIM, sum |h[k]| > 65535.  Host only, needs no GPU. */
+int gal_synth_firdec_check(const int16_t *taps_q14, int32_t n_taps, int32_t decim);
+/* The low-pass of gal_synth_fir_lowpass, operation for operation as stated there, for the decimator: n_taps odd, 3 .. 511;
+ * sample_rate_in is the rate of the INPUT stream.  The refusals are those of gal_synth_fir_lowpass.  Host only, needs no GPU. */
+int gal_synth_firdec_lowpass(double cutoff_hz, double sample_rate_in, int32_t n_taps, int16_t *taps_q14);
+/* The outputs a call of n_in input samples keeps when its first input sample has the global index first_sample: the number of m with
+ * first_sample <= M m < first_sample + n_in = ceil((first_sample + n_in) / M) - ceil(first_sample / M).  0 for decim outside
+ * 2..GAL_FIRDEC_MAX_DECIM or a sum beyond 2^64.  Host only, needs no GPU. */
+uint64_t gal_synth_firdec_out_samples(uint64_t first_sample, uint64_t n_in, int32_t decim);
+/* Give the handle a decimator and START A STREAM whose next input sample has the global index first_sample (only first_sample mod
+ * decim matters): the taps (HOST memory, copied before the call returns) go to the device and the history -- the last 512 input
+ * samples -- is zeroed.  n_taps = 0 (taps and decim are then not looked at) frees it.  The decimator has a slot, a tap table and a
+ * history of its own: the filter of gal_synth_fir_set is independent of it and untouched.  The call waits (on the host) for a
+ * decimator kernel of this handle that is still in flight.  GAL_E_INVAL for a null handle and whatever gal_synth_firdec_check refuses
+ * -- the decimator in force, its history and its position then stay as they are; GAL_E_NOMEM if the table cannot be had. */
+int gal_synth_firdec_set(gal_synth_t *h, const int16_t *taps_q14, int32_t n_taps, int32_t decim, uint64_t first_sample);
+/* Enqueue on the handle's stream: consume the NEXT n_in input samples of the stream (in_dev, DEVICE memory, n_in x 4 bytes) and write
+ * the outputs y[m] whose M m falls into them, contiguously from out_dev (DEVICE memory); *n_out = their number =
+ * gal_synth_firdec_out_samples(position, n_in, M), known when the call returns (the handle advances its position on the host, at
+ * enqueue time).  ANY CUT OF THE INPUT STREAM INTO CALLS GIVES THE BYTES OF ONE CALL: calls shorter than M, shorter than T - 1, not
+ * multiples of M, and calls that keep no output (n_in = 0: nothing happens).  Nothing is written behind output *n_out - 1.  The rules
+ * of gal_synth_iq_fir: 16-byte aligned pointers, GAL_E_STATE for a buffer of the batch in flight and with no decimator set,
+ * gal_synth_iq_saturated is the fence and the counter.  Any overlap of [out_dev, + 4 *n_out) with [in_dev, + 4 n_in) is refused.
+ * GAL_E_INVAL for a null handle, a null or misaligned pointer, a null n_out, an overlap, n_in >= 2^41.
+ * Sharding: a caller that starts in the middle of a stream calls gal_synth_firdec_set with its own first_sample -- best the index of
+ * the first of the T - 1 inputs in front of its range, with which it primes the history; what those produce it discards. */
+int gal_synth_iq_firdec(gal_synth_t *h, const int16_t *in_dev, size_t n_in, int16_t *out_dev, size_t *n_out);
+
+/*
  * Correlator bank and C/N0 monitor (not in the reference): despread a device buffer of output IQ with the engine's own replica of one
  * satellite and get, per code period, delay and Doppler bin, the complex correlation sums of the E1B and the E1C component.  Read-only
  * on the buffer, in any of the three formats.  Like the formats and the noise floor it is a FIXED INTEGER FUNCTION of its inputs: the
