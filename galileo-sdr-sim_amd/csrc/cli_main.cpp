@@ -27,6 +27,9 @@
 // --oversample M (not in the reference): synthesis, gains, noise and interference at M x 2.6 MS/s, then ONE decimating FIR filter back to
 // 2.6 MS/s (gal_synth_iq_firdec) in front of the format; --fir / --fir-lowpass then give the decimator's taps.
 //
+// --agc [target_rms], --iq-format i2bit (not in the reference): a block AGC in front of the quantiser, behind everything above, and the
+// 2-bit format it makes possible (gal_synth_iq_agc); --agc-log <file> writes the gain of every block.
+//
 // --monitor <file> (not in the reference): the built-in receiver check -- every --monitor-every'th epoch (default 10) the first 25 code
 // periods of every active channel are despread, in the buffer as it is written (behind noise and format), with the planned replica
 // (gal_synth_correlate); one CSV line per (epoch, PRN) with the measured C/N0 and where the peak lies.  Read-only: the IQ is the same.
@@ -103,7 +106,20 @@ void usage(const char *prog)
            "                   -P <port>: site k listens on port + k (default: no position listener)\n"
            "  --iq-format <f>  Output format: ishort (interleaved int16, the default), ibyte (interleaved int8: rounded\n"
            "                   x >> shift, clamped to +-127), ibit (1 bit per value, x > 0, packed MSB first)\n"
+           "                   i2bit (2 bits per value: sign and magnitude against --i2bit-threshold, 4 values per byte, MSB first;\n"
+           "                   implies --agc; default output name galileosim.i2bit)\n"
            "  --iq-shift <n>   ibyte only: right shift 0..15 before the clamp (default 5)\n"
+           "  --agc [rms]      Block AGC in front of the quantiser, behind gains, noise, interference and --fir / the decimator: the power of\n"
+           "                   the last --agc-window blocks sets the gain of the next block, so that the rms per rail becomes `rms` int16\n"
+           "                   LSB (default: 32 x 2^shift for ibyte, 2048 for ishort, the threshold for i2bit); not with ibit.  With --agc the\n"
+           "                   automatic --iq-shift of --cn0 / --jam leaves the --jam amplitudes out -- the AGC makes that room --: it is the\n"
+           "                   smallest shift with 127 x 2^shift >= 4 sigma (--cn0), or >= the largest signal sum (--jam alone)\n"
+           "  --agc-block <n>  with --agc: complex samples per block, 16..65536 (default 2600 = 1 ms)\n"
+           "  --agc-window <n> with --agc: blocks averaged, 1..64, block x window <= 65536 (default 8)\n"
+           "  --agc-init-rms <r> with --agc: the rms assumed in front of the stream (default: the noise sigma of --cn0, behind --fir or\n"
+           "                   the decimator sigma x sqrt(sum h^2) / 16384; without --cn0 750)\n"
+           "  --agc-log <file> with --agc: CSV, one line per block: time of its first sample, gain (4096 = 1.0), gain in dB\n"
+           "  --i2bit-threshold <n> i2bit only: the magnitude threshold, 1..32767 (default 1024)\n"
            "  --cn0 <dBHz>     Add a white Gaussian noise floor: C/N0 of one satellite's composite E1B + E1C signal (E1B alone is\n"
            "                   3 dB lower); every format; the same bytes for the same options on any machine (default: no noise)\n"
            "  --noise-seed <n> with --cn0: seed of the noise, 0 .. 2^64 - 1 (default 1)\n"
@@ -112,7 +128,8 @@ void usage(const char *prog)
            "                   5 sigma of noise + the largest signal sum + the --jam amplitudes inside int16)\n"
            "  --jam <spec>     Add an interference source, up to 4 times: js_db,f_hz[,f_hi_hz,sweep_us[,period_us,on_us]] -- J/S in dB against\n"
            "                   one satellite's composite signal, a CW tone at f_hz from the centre, or a chirp from f_hz to f_hi_hz that\n"
-           "                   restarts every sweep_us microseconds, on for on_us of every period_us; with or without --cn0\n"
+           "                   restarts every sweep_us microseconds, on for on_us of every period_us (f_hi_hz = sweep_us = 0: a pulsed\n"
+           "                   CW tone); with or without --cn0\n"
            "  --power-model    Per-satellite signal power from the path loss: gain = 23 222 km / distance (a satellite at the zenith is\n"
            "                   about unity); --cn0 and --jam then hold for a satellite at unity gain\n"
            "  --antenna <file> Receiver antenna pattern: 37 attenuations in dB, one per 5 degrees off the zenith (default: isotropic)\n"
@@ -329,7 +346,11 @@ bool parse_jam(const char *arg, JamSpec *j)
         p = end + 1;
     }
     if (n != 2 && n != 4 && n != 6) return false;
-    if (n >= 4 && !(v[3] > 0.0)) return false;  // a chirp needs a sweep time
+    if (n == 6 && v[2] == 0.0 && v[3] == 0.0) {
+        // a pulsed CW tone: no chirp
+    } else if (n >= 4 && !(v[3] > 0.0)) {
+        return false;  // a chirp needs a sweep time
+    }
     j->js_db = v[0];
     j->f_lo = v[1];
     j->f_hi = v[2];
@@ -646,6 +667,8 @@ int main(int argc, char *argv[])
     const char *iq_format_arg = "ishort", *iq_shift_arg = nullptr;
     const char *monitor_arg = nullptr, *monitor_every_arg = nullptr;
     const char *fir_arg = nullptr, *fir_lowpass_arg = nullptr, *oversample_arg = nullptr;
+    bool agc_given = false;
+    const char *agc_arg = nullptr, *agc_block_arg = nullptr, *agc_window_arg = nullptr, *agc_init_arg = nullptr, *agc_log_arg = nullptr, *i2bit_thr_arg = nullptr;
     bool power_model = false;
     const char *antenna_arg = nullptr;
     std::vector<const char *> prn_power_args;
@@ -655,7 +678,8 @@ int main(int argc, char *argv[])
     sc.udp_loopback = 1;              // ... on every interface; the default listener here takes local datagrams only
 
     enum { OPT_STRICT = 1000, OPT_SITES, OPT_WRITERS, OPT_GPUS, OPT_PER_GPU, OPT_EXACT, OPT_SHIFT_TOE, OPT_REF_T, OPT_IQ_FORMAT, OPT_IQ_SHIFT, OPT_CN0, OPT_NOISE_SEED,
-           OPT_NOISE_STREAM, OPT_SIGNAL_GAIN, OPT_MONITOR, OPT_MONITOR_EVERY, OPT_JAM, OPT_POWER_MODEL, OPT_ANTENNA, OPT_PRN_POWER, OPT_FIR, OPT_FIR_LOWPASS, OPT_OVERSAMPLE };
+           OPT_NOISE_STREAM, OPT_SIGNAL_GAIN, OPT_MONITOR, OPT_MONITOR_EVERY, OPT_JAM, OPT_POWER_MODEL, OPT_ANTENNA, OPT_PRN_POWER, OPT_FIR, OPT_FIR_LOWPASS, OPT_OVERSAMPLE,
+           OPT_AGC, OPT_AGC_BLOCK, OPT_AGC_WINDOW, OPT_AGC_INIT, OPT_AGC_LOG, OPT_I2BIT_THR };
     static const struct option long_opts[] = {{"strict", no_argument, nullptr, OPT_STRICT},
                                               {"exact-replay", no_argument, nullptr, OPT_EXACT},
                                               {"shift-toe", no_argument, nullptr, OPT_SHIFT_TOE},
@@ -679,16 +703,27 @@ int main(int argc, char *argv[])
                                               {"fir", required_argument, nullptr, OPT_FIR},
                                               {"fir-lowpass", required_argument, nullptr, OPT_FIR_LOWPASS},
                                               {"oversample", required_argument, nullptr, OPT_OVERSAMPLE},
+                                              {"agc", optional_argument, nullptr, OPT_AGC},
+                                              {"agc-block", required_argument, nullptr, OPT_AGC_BLOCK},
+                                              {"agc-window", required_argument, nullptr, OPT_AGC_WINDOW},
+                                              {"agc-init-rms", required_argument, nullptr, OPT_AGC_INIT},
+                                              {"agc-log", required_argument, nullptr, OPT_AGC_LOG},
+                                              {"i2bit-threshold", required_argument, nullptr, OPT_I2BIT_THR},
                                               {nullptr, 0, nullptr, 0}};
     std::vector<std::string> child_args;  // --sites: everything but -l / -o / --sites / --gpus / --per-gpu / --noise-stream goes to the children
     int opt;
     while ((opt = getopt_long(argc, argv, "e:n:o:u:g:l:T:t:d:G:a:p:iI:U:b:vB:P:rC", long_opts, nullptr)) != -1) {
-        if (opt != 'l' && opt != 'o' && opt != 'P' && opt != OPT_SITES && opt != OPT_GPUS && opt != OPT_PER_GPU && opt != OPT_NOISE_STREAM && opt != OPT_MONITOR && opt != '?' && opt != ':') {
+        // `--agc 4096`: getopt takes an optional argument only as --agc=4096; a following word that begins like a number is the target
+        if (opt == OPT_AGC && !optarg && optind < argc && ((argv[optind][0] >= '0' && argv[optind][0] <= '9') || argv[optind][0] == '.'))
+            optarg = argv[optind++];
+        if (opt != 'l' && opt != 'o' && opt != 'P' && opt != OPT_SITES && opt != OPT_GPUS && opt != OPT_PER_GPU && opt != OPT_NOISE_STREAM && opt != OPT_MONITOR && opt != OPT_AGC_LOG && opt != '?' && opt != ':') {
             if (opt >= 1000) {
                 child_args.push_back(opt == OPT_STRICT ? "--strict" : opt == OPT_EXACT ? "--exact-replay" : opt == OPT_SHIFT_TOE ? "--shift-toe" : opt == OPT_REF_T ? "--ref-T"
                                      : opt == OPT_IQ_FORMAT ? "--iq-format" : opt == OPT_IQ_SHIFT ? "--iq-shift" : opt == OPT_CN0 ? "--cn0"
                                      : opt == OPT_NOISE_SEED ? "--noise-seed" : opt == OPT_SIGNAL_GAIN ? "--signal-gain" : opt == OPT_MONITOR_EVERY ? "--monitor-every" : opt == OPT_JAM ? "--jam" : opt == OPT_POWER_MODEL ? "--power-model"
-                                     : opt == OPT_ANTENNA ? "--antenna" : opt == OPT_PRN_POWER ? "--prn-power" : opt == OPT_FIR ? "--fir" : opt == OPT_FIR_LOWPASS ? "--fir-lowpass" : opt == OPT_OVERSAMPLE ? "--oversample" : "--writers");
+                                     : opt == OPT_ANTENNA ? "--antenna" : opt == OPT_PRN_POWER ? "--prn-power" : opt == OPT_FIR ? "--fir" : opt == OPT_FIR_LOWPASS ? "--fir-lowpass" : opt == OPT_OVERSAMPLE ? "--oversample"
+                                     : opt == OPT_AGC ? "--agc" : opt == OPT_AGC_BLOCK ? "--agc-block" : opt == OPT_AGC_WINDOW ? "--agc-window" : opt == OPT_AGC_INIT ? "--agc-init-rms"
+                                     : opt == OPT_I2BIT_THR ? "--i2bit-threshold" : "--writers");
             } else {
                 char name[3] = {'-', (char)opt, 0};
                 child_args.push_back(name);
@@ -755,6 +790,12 @@ int main(int argc, char *argv[])
         case OPT_FIR: fir_arg = optarg; break;
         case OPT_FIR_LOWPASS: fir_lowpass_arg = optarg; break;
         case OPT_OVERSAMPLE: oversample_arg = optarg; break;
+        case OPT_AGC: agc_given = true; agc_arg = optarg; break;
+        case OPT_AGC_BLOCK: agc_block_arg = optarg; break;
+        case OPT_AGC_WINDOW: agc_window_arg = optarg; break;
+        case OPT_AGC_INIT: agc_init_arg = optarg; break;
+        case OPT_AGC_LOG: agc_log_arg = optarg; break;
+        case OPT_I2BIT_THR: i2bit_thr_arg = optarg; break;
         case 'n': case 'g': case 'G': case 'a': case 'p': case 'i': case 'U': case 'b': break;
         case ':':
         case '?':
@@ -779,13 +820,88 @@ int main(int argc, char *argv[])
     }
     if (sc.time_overwrite) sc.time_overwrite = shift_toe ? 2 : 1;
     // output format: checked here, before any device work
-    static const char *const kIqNames[] = {"ishort", "ibyte", "ibit"};  // GAL_IQ_ISHORT, GAL_IQ_IBYTE, GAL_IQ_IBIT
+    static const char *const kIqNames[] = {"ishort", "ibyte", "ibit", "i2bit"};  // GAL_IQ_ISHORT, GAL_IQ_IBYTE, GAL_IQ_IBIT, GAL_IQ_I2BIT
     int iq_format = -1, iq_shift = 0;
-    for (int f = 0; f < 3; ++f)
+    for (int f = 0; f < 4; ++f)
         if (strcmp(iq_format_arg, kIqNames[f]) == 0) iq_format = f;
     if (iq_format < 0) {
-        fprintf(stderr, "ERROR: unknown --iq-format '%s' (accepted: ishort, ibyte, ibit).\n", iq_format_arg);
+        fprintf(stderr, "ERROR: unknown --iq-format '%s' (accepted: ishort, ibyte, ibit, i2bit).\n", iq_format_arg);
         exit(1);
+    }
+    // AGC: the strings are checked here, before any device work; the parameters are made below, once shift and sigma are known.
+    // Without --agc and i2bit nothing below differs from a build without them.
+    const bool agc_on = agc_given || iq_format == GAL_IQ_I2BIT;  // the 2-bit format implies the AGC
+    if (!agc_on && (agc_block_arg || agc_window_arg || agc_init_arg || agc_log_arg)) {
+        fprintf(stderr, "ERROR: --agc-block, --agc-window, --agc-init-rms and --agc-log need --agc.\n");
+        exit(1);
+    }
+    if (agc_on && iq_format == GAL_IQ_IBIT) {
+        fprintf(stderr, "ERROR: --agc does not go with --iq-format ibit: a sign needs no gain control.\n");
+        exit(1);
+    }
+    if (monitor_arg && iq_format == GAL_IQ_I2BIT) {
+        fprintf(stderr, "ERROR: --monitor does not read --iq-format i2bit (ishort and ibyte, with or without --agc, it does).\n");
+        exit(1);
+    }
+    int i2bit_thr = 1024;
+    if (i2bit_thr_arg) {
+        char *end = nullptr;
+        const long v = strtol(i2bit_thr_arg, &end, 10);
+        if (iq_format != GAL_IQ_I2BIT) {
+            fprintf(stderr, "ERROR: --i2bit-threshold applies to --iq-format i2bit only.\n");
+            exit(1);
+        }
+        if (!*i2bit_thr_arg || *end || v < 1 || v > 32767) {
+            fprintf(stderr, "ERROR: --i2bit-threshold '%s' out of range (1..32767).\n", i2bit_thr_arg);
+            exit(1);
+        }
+        i2bit_thr = (int)v;
+    }
+    long agc_block = 2600, agc_window = 8;
+    double agc_target = 0.0, agc_init = -1.0;  // (0 / < 0: the defaults, known further down)
+    if (agc_on) {
+        char *end = nullptr;
+        if (agc_block_arg) {
+            agc_block = strtol(agc_block_arg, &end, 10);
+            if (!*agc_block_arg || *end || agc_block < GAL_AGC_MIN_BLOCK || agc_block > GAL_AGC_MAX_BLOCK) {
+                fprintf(stderr, "ERROR: --agc-block '%s' out of range (%d..%d samples).\n", agc_block_arg, GAL_AGC_MIN_BLOCK, GAL_AGC_MAX_BLOCK);
+                exit(1);
+            }
+        }
+        if (agc_window_arg) {
+            agc_window = strtol(agc_window_arg, &end, 10);
+            if (!*agc_window_arg || *end || agc_window < 1 || agc_window > GAL_AGC_MAX_WINDOW) {
+                fprintf(stderr, "ERROR: --agc-window '%s' out of range (1..%d blocks).\n", agc_window_arg, GAL_AGC_MAX_WINDOW);
+                exit(1);
+            }
+        }
+        if (agc_block * agc_window > GAL_AGC_MAX_SPAN) {
+            fprintf(stderr, "ERROR: --agc-block %ld x --agc-window %ld = %ld samples, more than %d.\n", agc_block, agc_window, agc_block * agc_window,
+                    GAL_AGC_MAX_SPAN);
+            exit(1);
+        }
+        if (agc_arg) {
+            agc_target = strtod(agc_arg, &end);
+            if (!*agc_arg || *end || !(agc_target >= 1.0 / 256.0 && agc_target <= 32767.0)) {
+                fprintf(stderr, "ERROR: --agc '%s' is not a target rms in int16 LSB (up to 32767).\n", agc_arg);
+                exit(1);
+            }
+        }
+        if (agc_init_arg) {
+            agc_init = strtod(agc_init_arg, &end);
+            if (!*agc_init_arg || *end || !(agc_init >= 0.0 && agc_init <= 32768.0)) {
+                fprintf(stderr, "ERROR: --agc-init-rms '%s' out of range (0..32768 int16 LSB).\n", agc_init_arg);
+                exit(1);
+            }
+        }
+        if (agc_log_arg && (!*agc_log_arg || strcmp(agc_log_arg, "-") == 0)) {
+            fprintf(stderr, "ERROR: --agc-log needs a file name.\n");
+            exit(1);
+        }
+        if (agc_log_arg && sitesfile[0]) {
+            fprintf(stderr, "ERROR: --agc-log writes one file; it does not go with --sites.\n");
+            exit(1);
+        }
     }
     if (iq_shift_arg) {
         char *end = nullptr;
@@ -935,7 +1051,7 @@ int main(int argc, char *argv[])
         const double sigma = noise.sigma_q4 / 16.0;
         if (iq_format == GAL_IQ_IBYTE && !iq_shift_arg && !dec_on) {  // the smallest shift with 127 x 2^s >= 4 sigma + the --jam amplitudes
             iq_shift = 0;
-            while (iq_shift < 15 && 127.0 * (double)(1 << iq_shift) < 4.0 * sigma + jam_unit * gain) ++iq_shift;
+            while (iq_shift < 15 && 127.0 * (double)(1 << iq_shift) < 4.0 * sigma + (agc_on ? 0.0 : jam_unit * gain)) ++iq_shift;
         }
         if (!sitesfile[0]) {  // (--sites: every child prints its own)
             fprintf(stderr, "Noise floor: C/N0 %g dB-Hz -> sigma %.1f LSB, signal gain %g%s, seed %llu, stream %u", cn0, sigma, gain,
@@ -954,7 +1070,7 @@ int main(int argc, char *argv[])
             noise.gain_q16 = (uint32_t)llround(gain * 65536.0);  // (sigma_q4 0: nothing random is computed)
             if (iq_format == GAL_IQ_IBYTE && !iq_shift_arg) {  // the smallest shift with 127 x 2^s >= 4100 g + the amplitudes
                 iq_shift = 0;
-                while (iq_shift < 15 && 127.0 * (double)(1 << iq_shift) < (sig_peak + jam_unit) * gain) ++iq_shift;
+                while (iq_shift < 15 && 127.0 * (double)(1 << iq_shift) < (sig_peak + (agc_on ? 0.0 : jam_unit)) * gain) ++iq_shift;
             }
         }
         for (int k = 0; k < n_jam; ++k)
@@ -1112,14 +1228,53 @@ int main(int argc, char *argv[])
             for (int k = 0; k < n_fir; ++k) e2 += (double)fir_taps[k] * (double)fir_taps[k];
             const double sigma_out = noise.sigma_q4 / 16.0 * sqrt(e2) / 16384.0;
             iq_shift = 0;
-            while (iq_shift < 15 && 127.0 * (double)(1 << iq_shift) < 4.0 * sigma_out + jam_unit * gain) ++iq_shift;
+            while (iq_shift < 15 && 127.0 * (double)(1 << iq_shift) < 4.0 * sigma_out + (agc_on ? 0.0 : jam_unit * gain)) ++iq_shift;
             if (!sitesfile[0]) fprintf(stderr, "Decimator: sigma %.1f LSB behind the filter, --iq-shift %d (chosen)\n", sigma_out, iq_shift);
         }
         if (!sitesfile[0])
             fprintf(stderr, "Oversampling: %d x 2.6 MS/s = %g MS/s in front of the decimator, %d taps, delay %g output samples\n", osr, kSampleRate / 1e6,
                     n_fir, (n_fir - 1) / (2.0 * osr));
     }
-    const double iq_bytes_per_sample = (double)gal_synth_iq_bytes(iq_format, 4) / 4.0;
+    // AGC: the parameters, now that shift and sigma are known
+    gal_iq_agc_t agc;
+    memset(&agc, 0, sizeof(agc));
+    const int agc_param = iq_format == GAL_IQ_IBYTE ? iq_shift : iq_format == GAL_IQ_I2BIT ? i2bit_thr : 0;
+    FILE *agc_log_fp = nullptr;
+    if (agc_on) {
+        if (agc_target == 0.0) agc_target = iq_format == GAL_IQ_IBYTE ? 32.0 * (double)(1 << iq_shift) : iq_format == GAL_IQ_I2BIT ? (double)i2bit_thr : 2048.0;
+        if (agc_init < 0.0) {  // the noise sigma where the AGC sits: behind --fir or the decimator where there is one
+            agc_init = 750.0;  // (the sigma of 9-12 channels)
+            if (noise_on) {
+                agc_init = noise.sigma_q4 / 16.0;
+                if (fir_on) {
+                    double e2 = 0.0;
+                    for (int k = 0; k < n_fir; ++k) e2 += (double)fir_taps[k] * (double)fir_taps[k];
+                    agc_init *= sqrt(e2) / 16384.0;
+                }
+            }
+        }
+        if (gal_synth_agc_from_rms(agc_target, agc_init, (int32_t)agc_block, (int32_t)agc_window, &agc) != GAL_OK) {
+            fprintf(stderr, "ERROR: --agc: %s\n", gal_synth_last_error());
+            exit(1);
+        }
+        if (!sitesfile[0]) {
+            fprintf(stderr, "AGC: target rms %g LSB, blocks of %ld samples, window %ld blocks, initial rms %g LSB", agc_target, agc_block, agc_window, agc_init);
+            if (iq_format == GAL_IQ_IBYTE) fprintf(stderr, ", --iq-shift %d%s", iq_shift, iq_shift_arg ? "" : " (chosen)");
+            if (iq_format == GAL_IQ_I2BIT) fprintf(stderr, ", --i2bit-threshold %d", i2bit_thr);
+            fprintf(stderr, "\n");
+            if (agc_log_arg) {
+                agc_log_fp = fopen(agc_log_arg, "w");
+                if (!agc_log_fp) {
+                    fprintf(stderr, "ERROR: cannot write the AGC log %s.\n", agc_log_arg);
+                    exit(1);
+                }
+                fprintf(agc_log_fp, "time_s,gain_q12,gain_db\n");
+            }
+        }
+    }
+    // bytes of n samples in the output format: the AGC has its own count (i2bit is a format of the AGC call only)
+    const auto out_bytes = [&](size_t n) { return agc_on ? gal_synth_agc_out_bytes(iq_format, n) : gal_synth_iq_bytes(iq_format, n); };
+    const double iq_bytes_per_sample = (double)out_bytes(4) / 4.0;
     if (sitesfile[0]) {
         // several listeners cannot share a port: the sites run without the position listener unless -P names a base port, in
         // which case site k (in file order) listens on port + k
@@ -1182,7 +1337,7 @@ int main(int argc, char *argv[])
     if (exact_replay) cfg.flags |= GAL_CFG_EXACT_REPLAY;
     // bytes per epoch in the output format: the per-batch split of the copies cuts at epoch boundaries, so every piece must be whole
     // bytes -- for ibit 260 000 % 4 == 0
-    const size_t epoch_bytes = gal_synth_iq_bytes(iq_format, (size_t)kOutSamplesPerEpoch);
+    const size_t epoch_bytes = out_bytes((size_t)kOutSamplesPerEpoch);  // (i2bit: 260 000 % 2 == 0)
     if (iq_format == GAL_IQ_IBIT && kOutSamplesPerEpoch % 4 != 0) {
         fprintf(stderr, "ERROR: ibit needs a multiple of 4 samples per epoch.\n");
         exit(1);
@@ -1215,11 +1370,16 @@ int main(int argc, char *argv[])
         fprintf(stderr, "ERROR: %s\n", gal_synth_last_error());
         exit(1);
     }
+    if (agc_on && gal_synth_agc_set(eng, &agc, 0) != GAL_OK) {
+        fprintf(stderr, "ERROR: %s\n", gal_synth_last_error());
+        exit(1);
+    }
     if (batch_epochs > total) batch_epochs = total > 0 ? total : 1;
     const size_t batch_bytes = epoch_bytes * batch_epochs;  // in the output format
     // d_iq: the engine's int16 output; d_out: what the copies read -- d_iq itself for ishort (with --cn0: after the noise pass has
     // run in place), the converted batch otherwise
     // --fir: d_fir holds the filtered int16 batch, which then is what the format conversion (ishort: the copies) reads
+    // --agc: the AGC writes every format, ishort too, into d_out (it does not run in place)
     int16_t *d_iq[2] = {nullptr, nullptr};
     int16_t *d_fir[2] = {nullptr, nullptr};
     void *d_out[2] = {nullptr, nullptr};
@@ -1239,11 +1399,11 @@ int main(int argc, char *argv[])
             }
             d_out[i] = d_fir[i];
         }
-        if (iq_format != GAL_IQ_ISHORT && hipMalloc(&d_out[i], batch_bytes) != hipSuccess) {
+        if ((iq_format != GAL_IQ_ISHORT || agc_on) && hipMalloc(&d_out[i], batch_bytes) != hipSuccess) {
             fprintf(stderr, "ERROR: buffer allocation failed\n");
             exit(1);
         }
-        if ((iq_format != GAL_IQ_ISHORT || mix_on || power_on || fir_on) && hipEventCreateWithFlags(&converted[i], hipEventDisableTiming) != hipSuccess) {
+        if ((iq_format != GAL_IQ_ISHORT || mix_on || power_on || fir_on || agc_on) && hipEventCreateWithFlags(&converted[i], hipEventDisableTiming) != hipSuccess) {
             fprintf(stderr, "ERROR: buffer allocation failed\n");
             exit(1);
         }
@@ -1269,6 +1429,27 @@ int main(int argc, char *argv[])
                 fprintf(stderr, "ERROR: buffer allocation failed\n");
                 exit(1);
             }
+    // --agc-log: per batch slot the gains of the blocks that start in it, on the device and pinned on the host
+    struct AgcLog {
+        uint32_t *dev = nullptr, *host = nullptr;
+        size_t n = 0;
+        bool pending = false;
+    } agc_log[2];
+    uint64_t agc_logged = 0;  // blocks written to the log
+    if (agc_log_fp) {
+        const size_t g_bytes = ((size_t)batch_epochs * kOutSamplesPerEpoch / (size_t)agc_block + 2) * sizeof(uint32_t);
+        for (int i = 0; i < 2; ++i)
+            if (hipMalloc((void **)&agc_log[i].dev, g_bytes) != hipSuccess || hipHostMalloc((void **)&agc_log[i].host, g_bytes, hipHostMallocDefault) != hipSuccess) {
+                fprintf(stderr, "ERROR: buffer allocation failed\n");
+                exit(1);
+            }
+    }
+    // the lines of a batch whose gains have arrived (the stream has been waited for)
+    const auto agc_log_flush = [&](AgcLog &l) {
+        for (size_t k = 0; k < l.n; ++k, ++agc_logged)
+            fprintf(agc_log_fp, "%.9f,%u,%.4f\n", (double)agc_logged * (double)agc_block / kOutRate, l.host[k], 20.0 * log10((double)l.host[k] / 4096.0));
+        l.pending = false;
+    };
     stage("device + pinned buffers");
     // (a stream for the engine, made here: left to the engine it would be made inside the first gal_synth_plan -- 7-17 ms
     // of the run instead of the start-up)
@@ -1407,7 +1588,7 @@ int main(int argc, char *argv[])
             }
             for (int e = 0; e < n; ++e) {
                 if ((emitted + e) % monitor_every) continue;
-                const size_t ob = gal_synth_iq_bytes(iq_format, (size_t)e * kOutSamplesPerEpoch);
+                const size_t ob = out_bytes((size_t)e * kOutSamplesPerEpoch);
                 int skip = iq_format == GAL_IQ_IBIT ? (int)((16 - ob % 16) % 16) * 4 : 0;
                 if (fir_on && skip < fir_delay) {  // the filtered stream lags by fir_delay: start there or later, on the same 16-byte grid
                     const int g = iq_format == GAL_IQ_IBIT ? 64 : iq_format == GAL_IQ_IBYTE ? 8 : 4;  // samples per 16 bytes
@@ -1472,6 +1653,7 @@ int main(int argc, char *argv[])
         }
         // (the stream has drained up to this batch's synthesis: the sums of the batch before it are on the host)
         if (monitor_fp && mon[cur ^ 1].pending) monitor_flush(mon[cur ^ 1], monitor_fp, kOutRate, mon_shape, mon_sum);
+        if (agc_log_fp && agc_log[cur ^ 1].pending) agc_log_flush(agc_log[cur ^ 1]);
         const double tb_synth = ms_since(tb0);
         if (batch_timing)
             fprintf(stderr, "[timing] batch at %7.2f ms: %3d epochs, waited %.2f ms for rows, %.2f for a free slot, %s %.2f\n",
@@ -1498,7 +1680,22 @@ int main(int argc, char *argv[])
             } else if (crc == GAL_OK) {
                 crc = gal_synth_iq_fir(eng, d_iq[cur], n_samples, d_fir[cur]);
             }
-            if (crc == GAL_OK && iq_format != GAL_IQ_ISHORT) crc = gal_synth_iq_convert(eng, d_fir[cur], n_kept, iq_format, iq_shift, d_out[cur]);
+            if (crc == GAL_OK && agc_on) crc = gal_synth_iq_agc(eng, d_fir[cur], n_kept, iq_format, agc_param, d_out[cur], agc_log[cur].dev, &agc_log[cur].n);
+            else if (crc == GAL_OK && iq_format != GAL_IQ_ISHORT) crc = gal_synth_iq_convert(eng, d_fir[cur], n_kept, iq_format, iq_shift, d_out[cur]);
+            if (crc != GAL_OK) {
+                fprintf(stderr, "\nERROR: %s\n", gal_synth_last_error());
+                rc = 1;
+                break;
+            }
+        } else if (agc_on) {
+            // noise / interference into the int16 batch in place, then the AGC and the format from there into d_out[cur]; the AGC's
+            // state runs on from batch to batch inside the handle
+            const size_t n_samples = (size_t)n * cfg.samples_per_epoch;
+            int crc = GAL_OK;
+            if (mix_on)
+                crc = gal_synth_iq_convert_interf(eng, d_iq[cur], n_samples, (uint64_t)emitted * (uint64_t)cfg.samples_per_epoch, &noise, interf, n_jam,
+                                                  GAL_IQ_ISHORT, 0, d_iq[cur]);
+            if (crc == GAL_OK) crc = gal_synth_iq_agc(eng, d_iq[cur], n_samples, iq_format, agc_param, d_out[cur], agc_log[cur].dev, &agc_log[cur].n);
             if (crc != GAL_OK) {
                 fprintf(stderr, "\nERROR: %s\n", gal_synth_last_error());
                 rc = 1;
@@ -1518,7 +1715,15 @@ int main(int argc, char *argv[])
                 break;
             }
         }
-        if (iq_format != GAL_IQ_ISHORT || mix_on || power_on || fir_on) {  // what the copies read is enqueued on the engine's stream: they wait for it
+        if (agc_log_fp) {  // behind the AGC, on the same stream
+            if (agc_log[cur].n && hipMemcpyAsync(agc_log[cur].host, agc_log[cur].dev, agc_log[cur].n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) != hipSuccess) {
+                fprintf(stderr, "\nERROR: AGC log: copy of the gains failed\n");
+                rc = 1;
+                break;
+            }
+            agc_log[cur].pending = true;
+        }
+        if (iq_format != GAL_IQ_ISHORT || mix_on || power_on || fir_on || agc_on) {  // what the copies read is enqueued on the engine's stream: they wait for it
             if (hipEventRecord(converted[cur], stream) != hipSuccess || hipStreamWaitEvent(copy_stream[0], converted[cur], 0) != hipSuccess ||
                 hipStreamWaitEvent(copy_stream[1], converted[cur], 0) != hipSuccess) {
                 fprintf(stderr, "\nERROR: event after the IQ conversion failed\n");
@@ -1533,7 +1738,7 @@ int main(int argc, char *argv[])
             while (i < mon_epoch.size() && mon_ok) {
                 size_t j = i;
                 while (j < mon_epoch.size() && mon_epoch[j] == mon_epoch[i]) ++j;
-                const size_t ob = gal_synth_iq_bytes(iq_format, (size_t)mon_epoch[i] * kOutSamplesPerEpoch) + gal_synth_iq_bytes(iq_format, (size_t)mon_skip[i]);
+                const size_t ob = out_bytes((size_t)mon_epoch[i] * kOutSamplesPerEpoch) + out_bytes((size_t)mon_skip[i]);
                 mon_ok = gal_synth_correlate(eng, (const char *)d_out[cur] + ob, iq_format, (size_t)kOutSamplesPerEpoch - mon_skip[i],
                                              &mon_reqs[2 * i], (int32_t)(2 * (j - i)), (int64_t *)(mon[cur].dev + mon[cur].entries[i].off)) == GAL_OK;
                 i = j;
@@ -1621,6 +1826,20 @@ int main(int argc, char *argv[])
             hipHostFree(mon[i].host);
         }
     }
+    if (agc_log_fp) {
+        if (hipStreamSynchronize(stream) != hipSuccess) rc = 1;
+        for (int i = 0; i < 2 && rc == 0; ++i)  // (the older batch first)
+            if (agc_log[cur ^ i].pending) agc_log_flush(agc_log[cur ^ i]);
+        if (fclose(agc_log_fp) != 0) {
+            fprintf(stderr, "ERROR: writing the AGC log %s failed\n", agc_log_arg);
+            rc = 1;
+        }
+        fprintf(stderr, "AGC log (%s): %llu blocks of %ld samples\n", agc_log_arg, (unsigned long long)agc_logged, agc_block);
+        for (int i = 0; i < 2; ++i) {
+            hipFree(agc_log[i].dev);
+            hipHostFree(agc_log[i].host);
+        }
+    }
     if (gal_scen_eph_gaps(scen) > 0)
         fprintf(stderr, "NOTE: %d (satellite, refresh) pairs ran on a stale ephemeris record (see the warning above)\n",
                 gal_scen_eph_gaps(scen));
@@ -1631,7 +1850,7 @@ int main(int argc, char *argv[])
                 fprintf(stderr, "  PRN %2d: gain %5d .. %5d  (%+.2f .. %+.2f dB)\n", prn, prn_gain_lo[prn], prn_gain_hi[prn],
                         prn_gain_lo[prn] > 0 ? 20.0 * log10(prn_gain_lo[prn] / 128.0) : -INFINITY, prn_gain_hi[prn] > 0 ? 20.0 * log10(prn_gain_hi[prn] / 128.0) : -INFINITY);
     }
-    if (iq_format == GAL_IQ_IBYTE || mix_on || power_on || fir_on) {
+    if (iq_format == GAL_IQ_IBYTE || mix_on || power_on || fir_on || agc_on) {
         // (stderr: with -o - the data go to stdout)
         uint64_t n_sat = 0;
         const double n_val = (double)emitted * cfg.samples_per_epoch * 2;

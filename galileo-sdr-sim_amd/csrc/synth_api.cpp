@@ -99,6 +99,10 @@ void galk_fir_table(const int16_t *h, int n_taps, uint32_t *table, int *n_trips,
 hipError_t galk_launch_iq_firdec(const int16_t *in, int16_t *out, uint64_t n, uint64_t n_out, int i0, int n_taps, int decim,
                                  const uint32_t *table_dev, const uint32_t *hist_in, uint32_t *hist_out, unsigned long long *sat, hipStream_t st);
 int galk_firdec_table(const int16_t *h, int n_taps, int decim, uint32_t *table, int *trips);
+hipError_t galk_launch_iq_agc(const int16_t *in, uint64_t n, uint32_t off0, int format, int param, const gal_iq_agc_t *p,
+                              const unsigned long long *state_in, unsigned long long *state_out, void *scratch, void *out, uint32_t *gains_out,
+                              unsigned long long *sat, hipStream_t st);
+uint64_t galk_agc_scratch_bytes(uint64_t n, uint32_t off0, uint32_t block_len);
 hipError_t galk_launch_iq_wsum(const int16_t *const *parts_dev, const int *gain_dev, int n_parts, int n_epochs, int samples_per_epoch, int wide,
                                int16_t *out, unsigned long long *sat, hipStream_t st);
 hipError_t galk_launch_corr(int format, const void *buf, uint64_t n_eff, uint64_t code_ph0, uint64_t code_dph, uint32_t carr_ph0,
@@ -356,6 +360,19 @@ struct gal_synth {
     int fd_cur = 0;
     hipEvent_t ev_fd = nullptr;
     bool fd_pending = false;
+    // gal_synth_agc_set / gal_synth_iq_agc (iq_agc.hip): d_agc = the two state buffers of kAgcState words (a call reads agc_cur and
+    // writes the other); h_agc = the pinned copy of the first state the upload reads; d_agc_scr = the block sums and gains of the last
+    // call, grown on demand; agc_pos = the global index of the next sample; ev_agc = the last AGC kernel of the handle is done
+    unsigned long long *d_agc = nullptr;
+    unsigned long long *h_agc = nullptr;
+    void *d_agc_scr = nullptr;
+    size_t agc_scr_bytes = 0;
+    gal_iq_agc_t agc = {};
+    bool agc_on = false;
+    uint64_t agc_pos = 0;
+    int agc_cur = 0;
+    hipEvent_t ev_agc = nullptr;
+    bool agc_pending = false;
 };
 
 // The stream the handle works on: the caller's (gal_synth_set_stream), or one of its own, made at first need.
@@ -594,6 +611,10 @@ int gal_synth_destroy(gal_synth_t *h)
     if (h->d_fd) hipFree(h->d_fd);
     if (h->h_fd) hipHostFree(h->h_fd);
     if (h->ev_fd) hipEventDestroy(h->ev_fd);
+    if (h->d_agc) hipFree(h->d_agc);
+    if (h->h_agc) hipHostFree(h->h_agc);
+    if (h->d_agc_scr) hipFree(h->d_agc_scr);
+    if (h->ev_agc) hipEventDestroy(h->ev_agc);
     if (h->d_lut) hipFree(h->d_lut);
     if (h->d_str) hipFree(h->d_str);
     if (h->h_up) hipHostFree(h->h_up);
@@ -2269,6 +2290,184 @@ int gal_synth_iq_firdec(gal_synth_t *h, const int16_t *in_dev, size_t n_in, int1
     HIP_TRY(hipEventRecord(h->ev_fd, st));
     h->fd_pending = true;
     *n_out = (size_t)outs;
+    return GAL_OK;
+}
+
+// ---- block AGC and 2-bit quantiser (iq_agc.hip) ------------------------------------------------------------------------------------
+static constexpr int kAgcState = GAL_AGC_MAX_WINDOW + 1;  // words of one state buffer, as iq_agc.hip keeps them
+
+int gal_synth_agc_check(const gal_iq_agc_t *a)
+{
+    const char *who = "gal_synth_agc_check";
+    if (!a) return fail(GAL_E_INVAL, "%s: null argument", who);
+    if (a->block_len < GAL_AGC_MIN_BLOCK || a->block_len > GAL_AGC_MAX_BLOCK)
+        return fail(GAL_E_INVAL, "%s: block_len %u (%d..%d)", who, a->block_len, GAL_AGC_MIN_BLOCK, GAL_AGC_MAX_BLOCK);
+    if (a->window < 1 || a->window > GAL_AGC_MAX_WINDOW) return fail(GAL_E_INVAL, "%s: window %u (1..%d)", who, a->window, GAL_AGC_MAX_WINDOW);
+    if ((uint64_t)a->block_len * a->window > GAL_AGC_MAX_SPAN)
+        return fail(GAL_E_INVAL, "%s: block_len %u x window %u = %llu samples, more than %d: the window sum could pass 2^47", who, a->block_len,
+                    a->window, (unsigned long long)a->block_len * a->window, GAL_AGC_MAX_SPAN);
+    if (a->target_q8 < 1 || a->target_q8 > 32767u * 256u) return fail(GAL_E_INVAL, "%s: target_q8 %u (1..%u)", who, a->target_q8, 32767u * 256u);
+    if (a->gain_min_q12 < 1 || a->gain_min_q12 > a->gain_max_q12 || a->gain_max_q12 > GAL_AGC_GAIN_MAX)
+        return fail(GAL_E_INVAL, "%s: gain clamps %u .. %u (1 <= min <= max <= %u; 4096 = 1.0)", who, a->gain_min_q12, a->gain_max_q12, GAL_AGC_GAIN_MAX);
+    if (a->p_init > ((uint64_t)a->block_len << 31))
+        return fail(GAL_E_INVAL, "%s: p_init %llu is more than 2^31 x block_len = %llu", who, (unsigned long long)a->p_init,
+                    (unsigned long long)a->block_len << 31);
+    if (a->reserved != 0) return fail(GAL_E_INVAL, "%s: reserved %u (0)", who, a->reserved);
+    return GAL_OK;
+}
+
+size_t gal_synth_agc_out_bytes(int32_t format, size_t n_samples)
+{
+    switch (format) {
+    case GAL_IQ_ISHORT: return 4 * n_samples;
+    case GAL_IQ_IBYTE: return 2 * n_samples;
+    case GAL_IQ_I2BIT: return n_samples / 2 + (n_samples & 1);
+    default: return 0;
+    }
+}
+
+uint64_t gal_synth_agc_blocks(uint64_t first_sample, uint64_t n_samples, int32_t block_len)
+{
+    if (block_len < GAL_AGC_MIN_BLOCK || block_len > GAL_AGC_MAX_BLOCK || first_sample + n_samples < first_sample) return 0;
+    const uint64_t B = (uint64_t)block_len, end = first_sample + n_samples;
+    // ceil(a / B) = a / B + (a % B != 0), without a + B - 1 (which could wrap)
+    return (end / B + (end % B != 0)) - (first_sample / B + (first_sample % B != 0));
+}
+
+int gal_synth_agc_from_rms(double target_rms, double init_rms, int32_t block_len, int32_t window, gal_iq_agc_t *out)
+{
+    const char *who = "gal_synth_agc_from_rms";
+    if (!out) return fail(GAL_E_INVAL, "%s: null argument", who);
+    if (!std::isfinite(target_rms) || !std::isfinite(init_rms) || !(init_rms >= 0.0) || !(init_rms <= 32768.0) || !(target_rms >= 0.0) ||
+        !(target_rms <= 32768.0))
+        return fail(GAL_E_INVAL, "%s: target rms %g, initial rms %g (finite, 0..32768 int16 LSB)", who, target_rms, init_rms);
+    if (block_len < 0 || window < 0) return fail(GAL_E_INVAL, "%s: block_len %d, window %d", who, block_len, window);
+    gal_iq_agc_t a;
+    memset(&a, 0, sizeof(a));
+    a.block_len = (uint32_t)block_len;
+    a.window = (uint32_t)window;
+    a.target_q8 = (uint32_t)llround(target_rms * 256.0);
+    a.gain_min_q12 = 1;
+    a.gain_max_q12 = GAL_AGC_GAIN_MAX;
+    const double sq = init_rms * init_rms;
+    a.p_init = 2ull * (uint64_t)block_len * (uint64_t)llround(sq);
+    const int rc = gal_synth_agc_check(&a);
+    if (rc) return rc;
+    *out = a;
+    return GAL_OK;
+}
+
+int gal_synth_agc_set(gal_synth_t *h, const gal_iq_agc_t *agc, uint64_t first_sample)
+{
+    const char *who = "gal_synth_agc_set";
+    if (!h) return fail(GAL_E_INVAL, "null handle");
+    gal_iq_agc_t a;
+    if (agc) {
+        a = *agc;  // the caller's struct is not looked at again
+        const int rc = gal_synth_agc_check(&a);
+        if (rc) return rc;
+        if (first_sample >> 62) return fail(GAL_E_INVAL, "%s: first_sample must be below 2^62", who);
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->agc_pending) {  // the states and the scratch belong to the kernels in flight
+        HIP_TRY(hipEventSynchronize(h->ev_agc));
+        h->agc_pending = false;
+    }
+    if (!agc) {
+        if (h->d_agc) hipFree(h->d_agc);
+        if (h->h_agc) hipHostFree(h->h_agc);
+        if (h->d_agc_scr) hipFree(h->d_agc_scr);
+        h->d_agc = h->h_agc = nullptr;
+        h->d_agc_scr = nullptr;
+        h->agc_scr_bytes = 0;
+        h->agc_on = false;
+        return GAL_OK;
+    }
+    hipStream_t st = handle_stream(h);
+    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
+    const size_t state_bytes = sizeof(unsigned long long) * kAgcState;
+    if (!h->ev_agc) HIP_TRY(hipEventCreateWithFlags(&h->ev_agc, hipEventDisableTiming));
+    if (!h->d_agc) {
+        unsigned long long *d = nullptr, *p = nullptr;
+        if (hipMalloc((void **)&d, 2 * state_bytes) != hipSuccess || hipHostMalloc((void **)&p, state_bytes, hipHostMallocDefault) != hipSuccess) {
+            if (d) hipFree(d);
+            return fail(GAL_E_NOMEM, "%s: the state of %zu bytes could not be allocated", who, 2 * state_bytes);
+        }
+        h->d_agc = d;
+        h->h_agc = p;
+    }
+    // from here on the AGC in force is gone: a failure leaves the handle without one
+    h->agc_on = false;
+    for (int k = 0; k < kAgcState; ++k) h->h_agc[k] = k < (int)a.window ? a.p_init : 0ull;
+    HIP_TRY(hipMemcpyAsync(h->d_agc, h->h_agc, state_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(h->ev_agc, st));  // (the upload reads h_agc: the next call waits for it as for a kernel)
+    h->agc_pending = true;
+    h->agc = a;
+    h->agc_pos = first_sample;
+    h->agc_cur = 0;
+    h->agc_on = true;
+    return GAL_OK;
+}
+
+int gal_synth_iq_agc(gal_synth_t *h, const int16_t *in_dev, size_t n_samples, int32_t format, int32_t param, void *out_dev, uint32_t *gains_dev,
+                     size_t *n_gains)
+{
+    const char *who = "gal_synth_iq_agc";
+    if (!h) return fail(GAL_E_INVAL, "null handle");
+    if (format != GAL_IQ_ISHORT && format != GAL_IQ_IBYTE && format != GAL_IQ_I2BIT)
+        return fail(GAL_E_INVAL, "%s: format %d (GAL_IQ_ISHORT 0, GAL_IQ_IBYTE 1, GAL_IQ_I2BIT 3; a sign, GAL_IQ_IBIT, needs no gain control)", who, format);
+    if (format == GAL_IQ_IBYTE ? (param < 0 || param > 15) : format == GAL_IQ_I2BIT ? (param < 1 || param > 32767) : param != 0)
+        return fail(GAL_E_INVAL, "%s: param %d (the shift 0..15 for GAL_IQ_IBYTE, the threshold 1..32767 for GAL_IQ_I2BIT, 0 for GAL_IQ_ISHORT)", who, param);
+    if (!in_dev || !out_dev || ((uintptr_t)in_dev & 15) || ((uintptr_t)out_dev & 15))
+        return fail(GAL_E_INVAL, "%s: device pointers must be non-null and 16-byte aligned", who);
+    if ((uintptr_t)gains_dev & 3) return fail(GAL_E_INVAL, "%s: gains_dev must be 4-byte aligned", who);
+    if ((uint64_t)n_samples >> 41) return fail(GAL_E_INVAL, "%s: n_samples must be below 2^41", who);
+    if (!h->agc_on) return fail(GAL_E_STATE, "%s: no AGC set (call gal_synth_agc_set first)", who);
+    if (n_samples == 0) {
+        if (n_gains) *n_gains = 0;
+        return GAL_OK;
+    }
+    const uint32_t B = h->agc.block_len, off0 = (uint32_t)(h->agc_pos % B);
+    const uint64_t ng = gal_synth_agc_blocks(h->agc_pos, (uint64_t)n_samples, (int32_t)B);
+    const size_t in_bytes = 4 * n_samples, out_bytes = gal_synth_agc_out_bytes(format, n_samples), g_bytes = gains_dev ? 4 * (size_t)ng : 0;
+    const char *x = (const char *)in_dev, *o = (const char *)out_dev, *g = (const char *)gains_dev;
+    if (x < o + out_bytes && o < x + in_bytes) return fail(GAL_E_INVAL, "%s: input and output overlap", who);
+    if (g_bytes && ((x < g + g_bytes && g < x + in_bytes) || (o < g + g_bytes && g < o + out_bytes)))
+        return fail(GAL_E_INVAL, "%s: the gains overlap the input or the output", who);
+    if (hits_batch_in_flight(h, in_dev, in_bytes)) return fail(GAL_E_STATE, "%s: input of the batch in flight (call gal_synth_finish first)", who);
+    if (hits_batch_in_flight(h, out_dev, out_bytes)) return fail(GAL_E_STATE, "%s: output of the batch in flight (call gal_synth_finish first)", who);
+    if (g_bytes && hits_batch_in_flight(h, gains_dev, g_bytes)) return fail(GAL_E_STATE, "%s: gains in the batch in flight (call gal_synth_finish first)", who);
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = handle_stream(h);
+    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
+    const int rc = ensure_sat_counter(h, st);
+    if (rc) return rc;
+    // the scratch of this call: one per handle, grown when a call touches more blocks than any before it (only then the host waits
+    // for the kernels of the call before)
+    const uint64_t need = galk_agc_scratch_bytes((uint64_t)n_samples, off0, B);
+    if (need > h->agc_scr_bytes) {
+        if (h->agc_pending) {
+            HIP_TRY(hipEventSynchronize(h->ev_agc));
+            h->agc_pending = false;
+        }
+        if (h->d_agc_scr) hipFree(h->d_agc_scr);
+        h->d_agc_scr = nullptr;
+        h->agc_scr_bytes = 0;
+        const uint64_t cap = need + need / 4 + 256;
+        if (cap != (uint64_t)(size_t)cap || hipMalloc(&h->d_agc_scr, (size_t)cap) != hipSuccess) {
+            h->d_agc_scr = nullptr;
+            (void)hipGetLastError();
+            return fail(GAL_E_NOMEM, "%s: the scratch of %llu bytes (12 per block touched) could not be allocated", who, (unsigned long long)cap);
+        }
+        h->agc_scr_bytes = (size_t)cap;
+    }
+    HIP_TRY(galk_launch_iq_agc(in_dev, (uint64_t)n_samples, off0, format, param, &h->agc, h->d_agc + h->agc_cur * kAgcState,
+                               h->d_agc + (h->agc_cur ^ 1) * kAgcState, h->d_agc_scr, out_dev, gains_dev, h->d_iq_sat, st));
+    h->agc_cur ^= 1;
+    h->agc_pos += (uint64_t)n_samples;
+    HIP_TRY(hipEventRecord(h->ev_agc, st));
+    h->agc_pending = true;
+    if (n_gains) *n_gains = (size_t)ng;
     return GAL_OK;
 }
 

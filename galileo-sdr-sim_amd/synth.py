@@ -38,6 +38,16 @@ GAL_FIR_UNITY = 16384
 GAL_FIRDEC_MAX_TAPS = 512  # decimating front-end filter (gal_synth_firdec_set)
 GAL_FIRDEC_MAX_DECIM = 16
 GAL_ENGINE_MAX_CHAN = 64
+# block AGC and 2-bit quantiser (gal_synth_agc_set, gal_synth_iq_agc): the 2-bit format is a format of the AGC call only
+GAL_IQ_I2BIT = 3
+AGC_FORMATS = {"ishort": GAL_IQ_ISHORT, "ibyte": GAL_IQ_IBYTE, "i2bit": GAL_IQ_I2BIT}
+GAL_AGC_MIN_BLOCK = 16
+GAL_AGC_MAX_BLOCK = 65536
+GAL_AGC_MAX_WINDOW = 64
+GAL_AGC_MAX_SPAN = 65536
+GAL_AGC_GAIN_UNITY = 4096
+GAL_AGC_GAIN_MAX = 1 << 24
+I2BIT_THRESHOLD_DEFAULT = 1024  # the CLI's default --i2bit-threshold
 
 # gal_chan_epoch_t (176 bytes)
 CHAN_EPOCH_DTYPE = np.dtype(
@@ -126,6 +136,22 @@ INTERF_FIELDS = tuple(name for name, _ in _Interf._fields_ if name != "reserved"
 GAL_INTERF_MAX = 4
 
 
+class _Agc(ctypes.Structure):  # gal_iq_agc_t (32 bytes)
+    _fields_ = [
+        ("block_len", ctypes.c_uint32),
+        ("window", ctypes.c_uint32),
+        ("target_q8", ctypes.c_uint32),
+        ("gain_min_q12", ctypes.c_uint32),
+        ("gain_max_q12", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("p_init", ctypes.c_uint64),
+    ]
+
+
+AGC_FIELDS = ("block_len", "window", "target_q8", "gain_min_q12", "gain_max_q12", "p_init")
+assert ctypes.sizeof(_Agc) == 32
+
+
 class _CorrReq(ctypes.Structure):  # gal_corr_req_t (56 bytes)
     _fields_ = [
         ("prn", ctypes.c_int32),
@@ -193,6 +219,12 @@ EXPORTED_SYMBOLS = (
     "gal_synth_firdec_out_samples",
     "gal_synth_firdec_set",
     "gal_synth_iq_firdec",
+    "gal_synth_agc_check",
+    "gal_synth_agc_out_bytes",
+    "gal_synth_agc_blocks",
+    "gal_synth_agc_from_rms",
+    "gal_synth_agc_set",
+    "gal_synth_iq_agc",
     "gal_synth_corr_out_bytes",
     "gal_synth_correlate",
     "gal_tables_e1b",
@@ -287,6 +319,18 @@ def load_library(hooks=False):
     lib.gal_synth_firdec_set.restype = ctypes.c_int
     lib.gal_synth_iq_firdec.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.POINTER(ctypes.c_size_t)]
     lib.gal_synth_iq_firdec.restype = ctypes.c_int
+    lib.gal_synth_agc_check.argtypes = [ctypes.POINTER(_Agc)]
+    lib.gal_synth_agc_check.restype = ctypes.c_int
+    lib.gal_synth_agc_out_bytes.argtypes = [i32, ctypes.c_size_t]
+    lib.gal_synth_agc_out_bytes.restype = ctypes.c_size_t
+    lib.gal_synth_agc_blocks.argtypes = [ctypes.c_uint64, ctypes.c_uint64, i32]
+    lib.gal_synth_agc_blocks.restype = ctypes.c_uint64
+    lib.gal_synth_agc_from_rms.argtypes = [ctypes.c_double, ctypes.c_double, i32, i32, ctypes.POINTER(_Agc)]
+    lib.gal_synth_agc_from_rms.restype = ctypes.c_int
+    lib.gal_synth_agc_set.argtypes = [vp, ctypes.POINTER(_Agc), ctypes.c_uint64]
+    lib.gal_synth_agc_set.restype = ctypes.c_int
+    lib.gal_synth_iq_agc.argtypes = [vp, vp, ctypes.c_size_t, i32, i32, vp, vp, ctypes.POINTER(ctypes.c_size_t)]
+    lib.gal_synth_iq_agc.restype = ctypes.c_int
     lib.gal_synth_corr_out_bytes.argtypes = [ctypes.POINTER(_CorrReq)]
     lib.gal_synth_corr_out_bytes.restype = ctypes.c_size_t
     lib.gal_synth_correlate.argtypes = [vp, vp, i32, ctypes.c_size_t, ctypes.POINTER(_CorrReq), i32, vp]
@@ -440,6 +484,67 @@ def firdec_out_samples(first_sample, n_in, decim):
     """gal_synth_firdec_out_samples (no GPU needed): the outputs a call of n_in inputs keeps when its first input has the global index
     first_sample -- the number of m with first_sample <= decim * m < first_sample + n_in."""
     return int(load_library().gal_synth_firdec_out_samples(int(first_sample), int(n_in), int(decim)))
+
+
+def agc_format_code(fmt):
+    """"ishort" | "ibyte" | "i2bit" (or the GAL_IQ_* integer) -> the GAL_IQ_* integer of an AGC output format."""
+    if isinstance(fmt, str):
+        if fmt not in AGC_FORMATS:
+            raise ValueError("unknown AGC output format %r (accepted: %s)" % (fmt, ", ".join(AGC_FORMATS)))
+        return AGC_FORMATS[fmt]
+    return int(fmt)
+
+
+def _agc_struct(agc):
+    """dict with the fields of gal_iq_agc_t but `reserved` (block_len, window and target_q8 are required; the gain clamps default to
+    their widest, p_init to 0), or an _Agc."""
+    if isinstance(agc, _Agc):
+        return agc
+    unknown = set(agc) - set(AGC_FIELDS)
+    if unknown:
+        raise ValueError("agc: unknown keys %s" % sorted(unknown))
+    d = {"gain_min_q12": 1, "gain_max_q12": GAL_AGC_GAIN_MAX, "p_init": 0}
+    d.update(agc)
+    for k in ("block_len", "window", "target_q8"):
+        if k not in d:
+            raise ValueError("agc: %s is required" % k)
+    for k in AGC_FIELDS:
+        if not 0 <= int(d[k]) < (1 << 64 if k == "p_init" else 1 << 32):
+            raise ValueError("agc: %s = %r does not fit its field" % (k, d[k]))
+    return _Agc(int(d["block_len"]), int(d["window"]), int(d["target_q8"]), int(d["gain_min_q12"]), int(d["gain_max_q12"]), 0, int(d["p_init"]))
+
+
+def agc_check(agc):
+    """gal_synth_agc_check (no GPU needed): raises GalSynthError unless the AGC parameters are admitted -- block_len 16 .. 65536, window
+    1 .. 64, block_len x window <= 65536, target_q8 1 .. 32767 x 256, 1 <= gain_min_q12 <= gain_max_q12 <= 2^24, p_init <= 2^31 block_len."""
+    lib = load_library()
+    a = _agc_struct(agc)
+    rc = lib.gal_synth_agc_check(ctypes.byref(a))
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+
+
+def agc_from_rms(target_rms, init_rms, block_len=2600, window=8):
+    """gal_synth_agc_from_rms (no GPU needed): the `agc` dict of SynthEngine.agc_set for a wanted rms per rail and the rms assumed in
+    front of the stream, both in int16 LSB -- target_q8 = llround(256 target_rms), p_init = 2 block_len llround(init_rms^2), the gain
+    clamps at their widest."""
+    lib = load_library()
+    a = _Agc()
+    rc = lib.gal_synth_agc_from_rms(float(target_rms), float(init_rms), int(block_len), int(window), ctypes.byref(a))
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+    return {k: int(getattr(a, k)) for k in AGC_FIELDS}
+
+
+def agc_out_bytes(fmt, n_samples):
+    """gal_synth_agc_out_bytes (no GPU needed): 4 n ("ishort"), 2 n ("ibyte"), ceil(n / 2) ("i2bit"); 0 for any other integer format."""
+    return int(load_library().gal_synth_agc_out_bytes(agc_format_code(fmt), int(n_samples)))
+
+
+def agc_blocks(first_sample, n_samples, block_len):
+    """gal_synth_agc_blocks (no GPU needed): the blocks whose first sample lies in a call of n_samples that begins at the global index
+    first_sample -- the number of b with first_sample <= b block_len < first_sample + n_samples."""
+    return int(load_library().gal_synth_agc_blocks(int(first_sample), int(n_samples), int(block_len)))
 
 
 def _corr_struct(req):
@@ -692,6 +797,28 @@ class SynthEngine:
         self._check(self._lib.gal_synth_iq_firdec(self._h, ctypes.c_void_p(int(in_ptr)), int(n_in), ctypes.c_void_p(int(out_ptr)),
                                                   ctypes.byref(n_out)))
         return int(n_out.value)
+
+    def agc_set(self, agc, first_sample=0):
+        """gal_synth_agc_set: give the handle the block AGC `agc` (a dict with the fields of gal_iq_agc_t; agc_from_rms makes one) and
+        start a stream whose next sample has the global index first_sample (every block in front of it has the power p_init); None
+        frees it.  Independent of fir_set and firdec_set."""
+        if agc is None:
+            self._check(self._lib.gal_synth_agc_set(self._h, None, 0))
+            return
+        a = _agc_struct(agc)
+        self._check(self._lib.gal_synth_agc_set(self._h, ctypes.byref(a), int(first_sample)))
+
+    def iq_agc(self, in_ptr, n_samples, fmt, param, out_ptr, gains_ptr=None):
+        """gal_synth_iq_agc, enqueued on the handle's stream: consume the next n_samples complex int16 samples at device address in_ptr
+        and write them, gain-controlled, as `fmt` ("ishort" | "ibyte" | "i2bit") to device address out_ptr (agc_out_bytes(fmt,
+        n_samples) bytes; both 16-byte aligned, not overlapping).  param: the "ibyte" shift, the "i2bit" threshold, 0 for "ishort".
+        gains_ptr: None, or a device address that receives the uint32 Q12 gains of the blocks that start in the call.  Returns their
+        number.  Any cut of the stream into calls gives the same bytes and gains.  iq_saturated() is the fence and the counter."""
+        n_gains = ctypes.c_size_t(0)
+        self._check(self._lib.gal_synth_iq_agc(self._h, ctypes.c_void_p(int(in_ptr)), int(n_samples), agc_format_code(fmt), int(param),
+                                               ctypes.c_void_p(int(out_ptr)), ctypes.c_void_p(int(gains_ptr)) if gains_ptr else None,
+                                               ctypes.byref(n_gains)))
+        return int(n_gains.value)
 
     def run_gains(self, params, gain_q7, iq_dev_ptr, state_in=None):
         """gal_synth_run_gains: the batch with per-slot, per-epoch Q7 gains gain_q7 [n_epochs, n_slots] (128 = unity) into the device

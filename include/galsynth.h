@@ -526,6 +526,89 @@ int gal_synth_firdec_set(gal_synth_t *h, const int16_t *taps_q14, int32_t n_taps
 int gal_synth_iq_firdec(gal_synth_t *h, const int16_t *in_dev, size_t n_in, int16_t *out_dev, size_t *n_out);
 
 /*
+ * Block AGC and 2-bit quantiser (not in the reference): what a front-end does between its filter and its ADC --
+ * measure the power of the stream in blocks, set a gain from the last blocks, quantise.  The pass sits behind the gains, the noise,
+ * the interference and the filter or decimator, in front of (and including) the format.  A FIXED INTEGER FUNCTION of its inputs: the
+ * same bytes and gains on any machine, however the stream is cut into calls (tests/agc_model.py states it in numpy).
+ *
+ * y[n] = (I, Q)[n], the complex int16 samples of the WHOLE stream, n the global index; block b = the samples [b B, (b + 1) B).
+ *   P[b] = sum over the 2 B values of block b of y^2, exact in 64 bits.  For a stream that gal_synth_agc_set starts at first_sample:
+ *          P[b] = p_init for b < first_sample div B, and the samples in front of first_sample in its own block count as 0
+ *   Q[b] = P[b - W] + ... + P[b - 1]: the W blocks BEFORE b.  Feed-forward with one block of delay: every block's gain is known
+ *          before its first sample, which keeps the pass parallel and independent of how the stream is cut
+ *   ms_q16 = (Q[b] << 16) div (2 B W);  rms_q8 = isqrt(ms_q16), the floor of the square root
+ *   g[b] = clamp((target_q8 << 12) div max(rms_q8, 1), gain_min_q12, gain_max_q12)
+ *   z    = clamp((int64(y) g[b] + 2048) >> 12, -32768, 32767)   (arithmetic shift), per value, b the block of the value's sample
+ * z is then written in one of three formats:
+ *   GAL_IQ_ISHORT  z itself
+ *   GAL_IQ_IBYTE   the shift / round / +-127 rule of the format above applied to z
+ *   GAL_IQ_I2BIT   q = (z > thr) + (z > 0) + (z > -thr) - 2, in {-2, -1, 0, 1}, standing for the value 2 q + 1 = -3, -1, +1, +3; the code is
+ *                  q & 3, four codes per byte with value 4k in bits 7..6 (MSB first, as GAL_IQ_IBIT), the unused low bits of the last
+ *                  byte 0; ceil(n / 2) bytes for n complex samples; thr = 1 .. 32767
+ * Bounds: B W <= 65536, y^2 <= 2^30 and p_init <= 2^31 B give Q <= 2^47, so Q << 16 <= 2^63 fits an unsigned 64-bit word; ms_q16 <= 2^46
+ * and rms_q8 <= 2^23; g <= 2^24 and |y g| <= 2^39.
+ * A value counts once in the handle's saturation counter (gal_synth_iq_saturated) if the int16 clamp, or GAL_IQ_IBYTE's +-127 clamp,
+ * changed it; the 2-bit magnitude saturates by design and does not count.
+ * GAL_IQ_I2BIT is a format of gal_synth_iq_agc ONLY: gal_synth_iq_bytes(GAL_IQ_I2BIT, n) is 0 and the conversions and the correlator
+ * refuse it.  GAL_IQ_IBIT is refused by gal_synth_iq_agc: a sign needs no gain control.
+ */
+#define GAL_IQ_I2BIT 3
+#define GAL_AGC_MIN_BLOCK 16
+#define GAL_AGC_MAX_BLOCK 65536
+#define GAL_AGC_MAX_WINDOW 64
+#define GAL_AGC_MAX_SPAN 65536   /* block_len x window at most */
+#define GAL_AGC_GAIN_UNITY 4096
+#define GAL_AGC_GAIN_MAX (1u << 24)
+typedef struct gal_iq_agc {
+    uint32_t block_len;     /* B: complex samples per block, 16 .. 65536, any integer                                          */
+    uint32_t window;        /* W: blocks averaged, 1 .. 64, B W <= 65536                                                       */
+    uint32_t target_q8;     /* wanted rms per rail in int16 LSB x 256, 1 .. 32767 x 256                                        */
+    uint32_t gain_min_q12;  /* gain clamps, 4096 = 1.0: 1 <= gain_min_q12 <= gain_max_q12 <= 2^24                              */
+    uint32_t gain_max_q12;
+    uint32_t reserved;      /* 0                                                                                               */
+    uint64_t p_init;        /* the power assumed for every block in front of the stream, <= 2^31 B                             */
+} gal_iq_agc_t;             /* 32 bytes */
+/* GAL_OK if the parameters are admitted, else GAL_E_INVAL: a null pointer, block_len outside 16..65536, window outside 1..64,
+ * block_len x window > 65536, target_q8 outside 1..32767 x 256, gain_min_q12 < 1, gain_min_q12 > gain_max_q12, gain_max_q12 > 2^24,
+ * p_init > 2^31 x block_len, reserved != 0.  Host only, needs no GPU. */
+int gal_synth_agc_check(const gal_iq_agc_t *agc);
+/* Bytes that n_samples complex samples take in an AGC output format: 4 n (GAL_IQ_ISHORT), 2 n (GAL_IQ_IBYTE), ceil(n / 2)
+ * (GAL_IQ_I2BIT); 0 for any other format, GAL_IQ_IBIT included.  Needs no GPU. */
+size_t gal_synth_agc_out_bytes(int32_t format, size_t n_samples);
+/* The blocks whose FIRST sample lies in a call of n samples that begins at the global index first_sample: the number of b with
+ * first_sample <= b B < first_sample + n = ceil((first_sample + n) / B) - ceil(first_sample / B).  0 for block_len outside 16..65536
+ * or a sum beyond 2^64.  Host only, needs no GPU. */
+uint64_t gal_synth_agc_blocks(uint64_t first_sample, uint64_t n_samples, int32_t block_len);
+/* Parameters from rms values in int16 LSB per rail; host only, needs no GPU.  In double, operation for operation:
+ *   target_q8 = llround(target_rms x 256.0)
+ *   p_init    = 2 x block_len x llround(init_rms x init_rms)      (the product in double first, then llround, then integers)
+ * gain_min_q12 = 1, gain_max_q12 = 2^24 (the clamps at their widest), reserved = 0.  GAL_E_INVAL for a null `out`, an argument that is
+ * not finite, init_rms outside [0, 32768] and whatever gal_synth_agc_check refuses of the result (target_rms outside about
+ * [0.002, 32767], the block and the window). */
+int gal_synth_agc_from_rms(double target_rms, double init_rms, int32_t block_len, int32_t window, gal_iq_agc_t *out);
+/* Give the handle an AGC and START A STREAM whose next sample has the global index first_sample (< 2^62).  The state lives on the
+ * device: the power of the last W complete blocks (set to p_init) and the partial sum of the open block (0); the handle keeps the
+ * position, and with it the sample count of the open block, on the host.  agc == NULL frees it.  The AGC has a slot of its own,
+ * independent of the filters.  The call waits (on the host) for an AGC kernel of this handle that is still in flight.  GAL_E_INVAL for
+ * a null handle, first_sample >= 2^62 and whatever gal_synth_agc_check refuses -- the AGC in force, its state and its position then
+ * stay as they are; GAL_E_NOMEM if the state cannot be had. */
+int gal_synth_agc_set(gal_synth_t *h, const gal_iq_agc_t *agc, uint64_t first_sample);
+/* Enqueue on the handle's stream: consume the NEXT n_samples complex int16 samples of the stream (in_dev, DEVICE memory, n_samples x 4
+ * bytes) and write them, gain-controlled, in `format` to out_dev (DEVICE memory, gal_synth_agc_out_bytes(format, n_samples) bytes).
+ * param: the GAL_IQ_IBYTE shift 0..15, the GAL_IQ_I2BIT threshold 1..32767, 0 for GAL_IQ_ISHORT.  gains_dev may be NULL; otherwise
+ * (DEVICE memory, 4-byte aligned) it receives uint32 g[b] for the blocks that START in the call, gal_synth_agc_blocks(position,
+ * n_samples, B) of them.  n_gains may be NULL; otherwise *n_gains is that number, known when the call returns (the handle advances its
+ * position on the host, at enqueue time).  ANY CUT OF THE STREAM INTO CALLS GIVES THE BYTES AND THE GAINS OF ONE CALL: calls shorter
+ * than a block, calls that start or end inside one (n_samples = 0: nothing happens); for GAL_IQ_I2BIT where the cuts are at even sample
+ * counts, so that every call begins at a byte.  Every call writes into a buffer of its own, as gal_synth_iq_convert does.  The rules of
+ * gal_synth_iq_fir: 16-byte aligned in_dev and out_dev, GAL_E_STATE for a buffer of the batch in flight and with no AGC set,
+ * gal_synth_iq_saturated is the fence and the counter.  Any overlap of the output or the gains with the input, or of one with the
+ * other, is refused.  GAL_E_INVAL for a null handle, a null or misaligned pointer, GAL_IQ_IBIT or an unknown format, a param outside
+ * its range, an overlap, n_samples >= 2^41; GAL_E_NOMEM if the call's scratch (12 bytes per block touched) cannot be had. */
+int gal_synth_iq_agc(gal_synth_t *h, const int16_t *in_dev, size_t n_samples, int32_t format, int32_t param, void *out_dev,
+                     uint32_t *gains_dev, size_t *n_gains);
+
+/*
  * Correlator bank and C/N0 monitor (not in the reference): despread a device buffer of output IQ with the engine's own replica of one
  * satellite and get, per code period, delay and Doppler bin, the complex correlation sums of the E1B and the E1C component.  Read-only
  * on the buffer, in any of the three formats.  Like the formats and the noise floor it is a FIXED INTEGER FUNCTION of its inputs: the
