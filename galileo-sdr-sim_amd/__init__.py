@@ -14,6 +14,7 @@ Only what the hot path needs lives here:
 from .synth import (  # noqa: F401
     CHAN_EPOCH_DTYPE,
     CHAN_STATE_DTYPE,
+    ECHO_DTYPE,
     GAL_CH_RESTART,
     GAL_GAIN_MAX,
     GAL_GAIN_UNITY,
@@ -31,6 +32,9 @@ from .synth import (  # noqa: F401
     interf_make,
     iq_bytes,
     load_library,
+    mpath_check,
+    mpath_make,
+    mpath_rows,
     noise_from_cn0,
     pack_page,
     tables,

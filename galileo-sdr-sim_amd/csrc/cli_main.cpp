@@ -138,6 +138,11 @@ void usage(const char *prog)
            "                   taps in Q14 (16384 = 1.0), one per line, 1..128 of them, sum of |tap| <= 65535\n"
            "  --fir-lowpass <cutoff_hz>[,n_taps] the same with a Hamming-windowed sinc low-pass (n_taps odd, 3..127, default 63; the taps\n"
            "                   are printed on stderr); not together with --fir\n"
+           "  --multipath <f>  Echoes of single satellites, one per line of the file: prn,delay_m,rel_db,phase_deg[,fade_hz] (# comments) --\n"
+           "                   the satellite's own stream again, delay_m / c later (rounded to whole samples: 115 m at 2.6 MS/s, 7.7 m with\n"
+           "                   --oversample 15; at most 1024 samples), rel_db against the direct signal (at most +6 dB), turned by phase_deg and\n"
+           "                   rotating at fade_hz.  At most 32 lines, 4 per PRN; a PRN that is not in view has no effect.  Added on the GPU in\n"
+           "                   front of noise, --jam, the filters and the AGC; --monitor then shows the multipath.\n"
            "  --oversample <M> Synthesise, weight, add noise and interference at M x 2.6 MS/s (M = 2..15) and bring the stream back to\n"
            "                   2.6 MS/s with one decimating FIR filter in front of the format: the file has the size and rate it has\n"
            "                   without the option.  --jam frequencies are then admitted up to +-M x 1.3 MHz.  --fir <file> then holds the\n"
@@ -428,6 +433,73 @@ bool load_antenna(const char *path, double (&pat)[GAL_GAIN_PATTERN_LEN], std::st
     return true;
 }
 
+// --multipath <file>: one echo per line, prn,delay_m,rel_db,phase_deg[,fade_hz]; lines that begin with # and blank lines are skipped
+struct EchoSpec {
+    int prn;
+    double delay_m, rel_db, phase_deg, fade_hz;
+    gal_mpath_echo_t echo;  // made once the sample rate is known
+};
+constexpr int kEchoPerPrn = 4;
+
+bool load_multipath(const char *path, std::vector<EchoSpec> *out, std::string *why)
+{
+    FILE *fp = fopen(path, "r");
+    if (!fp) {
+        *why = "cannot read it";
+        return false;
+    }
+    char line[1024];
+    int lineno = 0, per_prn[GAL_NUM_PRN + 1] = {0};
+    bool ok = true;
+    while (ok && fgets(line, sizeof(line), fp)) {
+        ++lineno;
+        const char *p = line;
+        while (*p == ' ' || *p == '\t') ++p;
+        if (*p == '#' || *p == '\n' || *p == '\r' || !*p) continue;
+        EchoSpec e;
+        memset(&e, 0, sizeof(e));
+        double v[5] = {0, 0, 0, 0, 0};
+        int n = 0;
+        for (; n < 5; ++n) {
+            char *end = nullptr;
+            v[n] = strtod(p, &end);
+            if (end == p || !std::isfinite(v[n])) break;
+            p = end;
+            while (*p == ' ' || *p == '\t') ++p;
+            if (*p != ',') {
+                ++n;
+                break;
+            }
+            ++p;
+        }
+        while (*p == ' ' || *p == '\t' || *p == '\n' || *p == '\r') ++p;
+        const std::string at = "line " + std::to_string(lineno);
+        if (n < 4 || *p) {
+            *why = at + " is not prn,delay_m,rel_db,phase_deg[,fade_hz]";
+            ok = false;
+        } else if (v[0] != floor(v[0]) || v[0] < 1 || v[0] > GAL_NUM_PRN) {
+            *why = at + ": PRN outside 1.." + std::to_string(GAL_NUM_PRN);
+            ok = false;
+        } else if ((int)out->size() >= GAL_ECHO_MAX) {
+            *why = "more than " + std::to_string(GAL_ECHO_MAX) + " echoes";
+            ok = false;
+        } else if (++per_prn[(int)v[0]] > kEchoPerPrn) {
+            *why = at + ": more than " + std::to_string(kEchoPerPrn) + " echoes of PRN " + std::to_string((int)v[0]);
+            ok = false;
+        } else {
+            e.prn = (int)v[0];
+            e.delay_m = v[1], e.rel_db = v[2], e.phase_deg = v[3], e.fade_hz = v[4];
+            out->push_back(e);
+        }
+    }
+    fclose(fp);
+    if (ok && out->empty()) {
+        *why = "it holds no echo";
+        ok = false;
+    }
+    return ok;
+}
+
 // ---- --sites: one child process per receiver site ---------------------------------------------------------------
 struct Site {
     std::string llh, out;
@@ -666,7 +738,7 @@ int main(int argc, char *argv[])
     int batch_epochs = 128, n_writers = -1, sites_gpus = 0, sites_per_gpu = 1;
     const char *iq_format_arg = "ishort", *iq_shift_arg = nullptr;
     const char *monitor_arg = nullptr, *monitor_every_arg = nullptr;
-    const char *fir_arg = nullptr, *fir_lowpass_arg = nullptr, *oversample_arg = nullptr;
+    const char *fir_arg = nullptr, *fir_lowpass_arg = nullptr, *oversample_arg = nullptr, *multipath_arg = nullptr;
     bool agc_given = false;
     const char *agc_arg = nullptr, *agc_block_arg = nullptr, *agc_window_arg = nullptr, *agc_init_arg = nullptr, *agc_log_arg = nullptr, *i2bit_thr_arg = nullptr;
     bool power_model = false;
@@ -679,7 +751,7 @@ int main(int argc, char *argv[])
 
     enum { OPT_STRICT = 1000, OPT_SITES, OPT_WRITERS, OPT_GPUS, OPT_PER_GPU, OPT_EXACT, OPT_SHIFT_TOE, OPT_REF_T, OPT_IQ_FORMAT, OPT_IQ_SHIFT, OPT_CN0, OPT_NOISE_SEED,
            OPT_NOISE_STREAM, OPT_SIGNAL_GAIN, OPT_MONITOR, OPT_MONITOR_EVERY, OPT_JAM, OPT_POWER_MODEL, OPT_ANTENNA, OPT_PRN_POWER, OPT_FIR, OPT_FIR_LOWPASS, OPT_OVERSAMPLE,
-           OPT_AGC, OPT_AGC_BLOCK, OPT_AGC_WINDOW, OPT_AGC_INIT, OPT_AGC_LOG, OPT_I2BIT_THR };
+           OPT_AGC, OPT_AGC_BLOCK, OPT_AGC_WINDOW, OPT_AGC_INIT, OPT_AGC_LOG, OPT_I2BIT_THR, OPT_MULTIPATH };
     static const struct option long_opts[] = {{"strict", no_argument, nullptr, OPT_STRICT},
                                               {"exact-replay", no_argument, nullptr, OPT_EXACT},
                                               {"shift-toe", no_argument, nullptr, OPT_SHIFT_TOE},
@@ -709,6 +781,7 @@ int main(int argc, char *argv[])
                                               {"agc-init-rms", required_argument, nullptr, OPT_AGC_INIT},
                                               {"agc-log", required_argument, nullptr, OPT_AGC_LOG},
                                               {"i2bit-threshold", required_argument, nullptr, OPT_I2BIT_THR},
+                                              {"multipath", required_argument, nullptr, OPT_MULTIPATH},
                                               {nullptr, 0, nullptr, 0}};
     std::vector<std::string> child_args;  // --sites: everything but -l / -o / --sites / --gpus / --per-gpu / --noise-stream goes to the children
     int opt;
@@ -723,7 +796,7 @@ int main(int argc, char *argv[])
                                      : opt == OPT_NOISE_SEED ? "--noise-seed" : opt == OPT_SIGNAL_GAIN ? "--signal-gain" : opt == OPT_MONITOR_EVERY ? "--monitor-every" : opt == OPT_JAM ? "--jam" : opt == OPT_POWER_MODEL ? "--power-model"
                                      : opt == OPT_ANTENNA ? "--antenna" : opt == OPT_PRN_POWER ? "--prn-power" : opt == OPT_FIR ? "--fir" : opt == OPT_FIR_LOWPASS ? "--fir-lowpass" : opt == OPT_OVERSAMPLE ? "--oversample"
                                      : opt == OPT_AGC ? "--agc" : opt == OPT_AGC_BLOCK ? "--agc-block" : opt == OPT_AGC_WINDOW ? "--agc-window" : opt == OPT_AGC_INIT ? "--agc-init-rms"
-                                     : opt == OPT_I2BIT_THR ? "--i2bit-threshold" : "--writers");
+                                     : opt == OPT_I2BIT_THR ? "--i2bit-threshold" : opt == OPT_MULTIPATH ? "--multipath" : "--writers");
             } else {
                 char name[3] = {'-', (char)opt, 0};
                 child_args.push_back(name);
@@ -790,6 +863,7 @@ int main(int argc, char *argv[])
         case OPT_FIR: fir_arg = optarg; break;
         case OPT_FIR_LOWPASS: fir_lowpass_arg = optarg; break;
         case OPT_OVERSAMPLE: oversample_arg = optarg; break;
+        case OPT_MULTIPATH: multipath_arg = optarg; break;
         case OPT_AGC: agc_given = true; agc_arg = optarg; break;
         case OPT_AGC_BLOCK: agc_block_arg = optarg; break;
         case OPT_AGC_WINDOW: agc_window_arg = optarg; break;
@@ -949,7 +1023,24 @@ int main(int argc, char *argv[])
                     antenna_arg ? antenna_arg : "isotropic", prn_power_args.size(), prn_power_args.size() == 1 ? "" : "s", power_peak,
                     20.0 * log10(power_peak));
     }
-    const double sig_peak = 4100.0 * power_peak;  // the largest |x| of the signal sum: 4100 in the reference's scenarios
+    // --multipath: the file is read here, before any device work.  Without the option nothing below differs from a build without it.
+    // A satellite with echoes can reach 1 + sum alpha times its own amplitude: the largest such sum scales the headroom's signal term
+    std::vector<EchoSpec> echoes;
+    double echo_peak = 1.0;
+    if (multipath_arg) {
+        std::string why;
+        if (!load_multipath(multipath_arg, &echoes, &why)) {
+            fprintf(stderr, "ERROR: --multipath %s: %s.\n", multipath_arg, why.c_str());
+            exit(1);
+        }
+        double sum[GAL_NUM_PRN + 1] = {0};
+        for (const EchoSpec &e : echoes) {
+            sum[e.prn] += pow(10.0, e.rel_db / 20.0);
+            echo_peak = 1.0 + sum[e.prn] > echo_peak ? 1.0 + sum[e.prn] : echo_peak;
+        }
+    }
+    const bool mp_on = !echoes.empty();
+    const double sig_peak = 4100.0 * power_peak * echo_peak;  // the largest |x| of the signal sum: 4100 in the reference's scenarios
     // noise floor: checked here too.  Without --cn0 nothing below differs from a build without it.
     // --oversample M: everything in front of the decimator runs at M x 2.6 MS/s (kSampleRate); the file and --monitor at kOutRate.
     // Without the option M = 1 and the two are the same number.
@@ -967,6 +1058,20 @@ int main(int argc, char *argv[])
     const double kOutRate = 2.6e6;
     const int kOutSamplesPerEpoch = 260000;
     const double kSampleRate = (double)osr * 2.6e6;
+    const double kLight = 299792458.0;
+    for (size_t k = 0; k < echoes.size(); ++k) {  // the delays in samples of the rate the pass runs at
+        EchoSpec &e = echoes[k];
+        if (gal_synth_mpath_make(e.delay_m / kLight, e.rel_db, e.phase_deg, e.fade_hz, kSampleRate, &e.echo) != GAL_OK) {
+            fprintf(stderr, "ERROR: --multipath %s, echo %zu (PRN %d): %s\n", multipath_arg, k + 1, e.prn, gal_synth_last_error());
+            exit(1);
+        }
+        if (!sitesfile[0])
+            fprintf(stderr, "Multipath %zu: PRN %d, delay %u samples = %.2f m (asked %.2f m), amplitude %.4f (%.2f dB), phase %.2f deg, fading %.3f Hz\n",
+                    k + 1, e.prn, e.echo.delay, e.echo.delay / kSampleRate * kLight, e.delay_m, e.echo.alpha_q12 / 4096.0, e.rel_db,
+                    e.echo.ph0 / 4294967296.0 * 360.0, e.echo.dph / 4294967296.0 * kSampleRate);
+    }
+    if (mp_on && !sitesfile[0] && echo_peak > 1.0)
+        fprintf(stderr, "Multipath: %zu echo%s; a satellite reaches up to %.3f times its own amplitude\n", echoes.size(), echoes.size() == 1 ? "" : "es", echo_peak);
     bool noise_on = false;
     gal_iq_noise_t noise;
     memset(&noise, 0, sizeof(noise));
@@ -1403,7 +1508,7 @@ int main(int argc, char *argv[])
             fprintf(stderr, "ERROR: buffer allocation failed\n");
             exit(1);
         }
-        if ((iq_format != GAL_IQ_ISHORT || mix_on || power_on || fir_on || agc_on) && hipEventCreateWithFlags(&converted[i], hipEventDisableTiming) != hipSuccess) {
+        if ((iq_format != GAL_IQ_ISHORT || mix_on || power_on || mp_on || fir_on || agc_on) && hipEventCreateWithFlags(&converted[i], hipEventDisableTiming) != hipSuccess) {
             fprintf(stderr, "ERROR: buffer allocation failed\n");
             exit(1);
         }
@@ -1550,6 +1655,18 @@ int main(int argc, char *argv[])
     bool have_state = false;
     int emitted = 0, cur = 0, rc = 0, r = 0;
     int prn_gain_lo[GAL_NUM_PRN + 1], prn_gain_hi[GAL_NUM_PRN + 1];  // per-satellite signal power: the gains each PRN was given
+    std::vector<uint16_t> mp_gains;     // --multipath: the batch's gains [epochs][slots] ...
+    std::vector<gal_iq_echo_t> mp_rows; // ... its echo table [epochs][echoes in view] ...
+    std::vector<int32_t> slot_of;       // ... and per echo in view its slot and its line of the file
+    std::vector<const EchoSpec *> spec_of;
+    const auto note_gains = [&](const gal_chan_epoch_t *rows, const uint16_t *g, size_t count) {  // the summary's per-PRN range
+        for (size_t i = 0; i < count; ++i) {
+            const int prn = rows[i].prn;
+            if (prn < 1 || prn > GAL_NUM_PRN) continue;
+            prn_gain_lo[prn] = g[i] < prn_gain_lo[prn] ? g[i] : prn_gain_lo[prn];
+            prn_gain_hi[prn] = g[i] > prn_gain_hi[prn] ? g[i] : prn_gain_hi[prn];
+        }
+    };
     for (int i = 0; i <= GAL_NUM_PRN; ++i) prn_gain_lo[i] = GAL_GAIN_MAX + 1, prn_gain_hi[i] = -1;
     // (SIGINT: the batch in flight is finished and written, batches the producer has queued behind it are dropped)
     const bool batch_timing = getenv("GAL_CLI_TIMING") != nullptr;
@@ -1616,17 +1733,48 @@ int main(int argc, char *argv[])
                 }
             }
         }
-        if (power_on) {
+        if (power_on && !mp_on) {
             // one synthesis run per group of slots with equal gains, finished when the call returns, and the weighted sum enqueued
             // on the engine's stream behind them (include/galsynth.h)
             const uint16_t *gp = rb[r].gains.data();
-            for (size_t i = 0; i < (size_t)n * sc.n_slots; ++i) {
-                const int prn = rows_ptr[i].prn;
-                if (prn < 1 || prn > GAL_NUM_PRN) continue;
-                prn_gain_lo[prn] = gp[i] < prn_gain_lo[prn] ? gp[i] : prn_gain_lo[prn];
-                prn_gain_hi[prn] = gp[i] > prn_gain_hi[prn] ? gp[i] : prn_gain_hi[prn];
-            }
+            note_gains(rows_ptr, gp, (size_t)n * sc.n_slots);
             if (gal_synth_run_gains(eng, rows_ptr, n, have_state ? state.data() : nullptr, gp, d_iq[cur], state.data()) != GAL_OK) {
+                fprintf(stderr, "\nERROR: %s\n", gal_synth_last_error());
+                rc = 1;
+                break;
+            }
+        } else if (mp_on) {
+            // the gains of --power-model and its kin, or unity; an echo goes to the slot that carries its PRN in this batch (a PRN that
+            // is not in view: no echo), with a row per epoch from the slot's gain and the epoch's index in the whole stream
+            const int S = sc.n_slots;
+            if (power_on) {
+                mp_gains.assign(rb[r].gains.begin(), rb[r].gains.begin() + (size_t)n * S);
+                note_gains(rows_ptr, mp_gains.data(), (size_t)n * S);
+            } else {
+                mp_gains.assign((size_t)n * S, (uint16_t)GAL_GAIN_UNITY);
+            }
+            slot_of.clear();
+            spec_of.clear();
+            for (const EchoSpec &e : echoes) {
+                int slot = -1;
+                for (size_t i = 0; i < (size_t)n * S && slot < 0; ++i)
+                    if (rows_ptr[i].prn == e.prn) slot = (int)(i % S);
+                if (slot < 0) continue;
+                slot_of.push_back(slot);
+                spec_of.push_back(&e);
+            }
+            const int n_echo = (int)slot_of.size();
+            mp_rows.assign((size_t)n * (n_echo > 0 ? n_echo : 1), gal_iq_echo_t{});
+            bool ok = true;
+            for (int e = 0; e < n && ok; ++e)
+                for (int k = 0; k < n_echo && ok; ++k) {
+                    const size_t i = (size_t)e * S + slot_of[k];
+                    const bool here = rows_ptr[i].prn == spec_of[k]->prn;  // (the slot carries another satellite, or none, in this epoch: A = 0)
+                    ok = gal_synth_mpath_row(&spec_of[k]->echo, here ? mp_gains[i] : 0, (uint64_t)(emitted + e), cfg.samples_per_epoch,
+                                             &mp_rows[(size_t)e * n_echo + k]) == GAL_OK;
+                }
+            if (!ok || gal_synth_run_mpath(eng, rows_ptr, n, have_state ? state.data() : nullptr, mp_gains.data(), slot_of.data(), mp_rows.data(),
+                                           n_echo, d_iq[cur], state.data()) != GAL_OK) {
                 fprintf(stderr, "\nERROR: %s\n", gal_synth_last_error());
                 rc = 1;
                 break;
@@ -1646,7 +1794,7 @@ int main(int argc, char *argv[])
         // The IQ in d_iq[cur] is final only once gal_synth_finish() has returned: finish() may find the speculative
         // carrier chain unverified (or the replay check unhappy) and synthesise the batch again.  The copies are
         // therefore enqueued after it; they still run beside the front-end and the synthesis of the next batch.
-        if (!power_on && gal_synth_finish(eng, state.data(), nullptr) != GAL_OK) {
+        if (!power_on && !mp_on && gal_synth_finish(eng, state.data(), nullptr) != GAL_OK) {
             fprintf(stderr, "\nERROR: %s\n", gal_synth_last_error());
             rc = 1;
             break;
@@ -1658,7 +1806,10 @@ int main(int argc, char *argv[])
         if (batch_timing)
             fprintf(stderr, "[timing] batch at %7.2f ms: %3d epochs, waited %.2f ms for rows, %.2f for a free slot, %s %.2f\n",
                     std::chrono::duration<double, std::milli>(tb0 - t_start).count(), n, tb_rows, tb_slot - tb_rows,
-                    power_on ? "run_gains (every group's plan + execute + finish, the sum enqueued)" : "plan + execute + finish", tb_synth - tb_slot);
+                    mp_on      ? "run_mpath (every group's plan + execute + finish, the echo pass enqueued)"
+                    : power_on ? "run_gains (every group's plan + execute + finish, the sum enqueued)"
+                               : "plan + execute + finish",
+                    tb_synth - tb_slot);
         slot[cur].bytes = epoch_bytes * n;
         if (fir_on) {
             // noise / interference into the int16 batch in place, the filter into d_fir[cur], the plain format conversion from there
@@ -1723,7 +1874,7 @@ int main(int argc, char *argv[])
             }
             agc_log[cur].pending = true;
         }
-        if (iq_format != GAL_IQ_ISHORT || mix_on || power_on || fir_on || agc_on) {  // what the copies read is enqueued on the engine's stream: they wait for it
+        if (iq_format != GAL_IQ_ISHORT || mix_on || power_on || mp_on || fir_on || agc_on) {  // what the copies read is enqueued on the engine's stream: they wait for it
             if (hipEventRecord(converted[cur], stream) != hipSuccess || hipStreamWaitEvent(copy_stream[0], converted[cur], 0) != hipSuccess ||
                 hipStreamWaitEvent(copy_stream[1], converted[cur], 0) != hipSuccess) {
                 fprintf(stderr, "\nERROR: event after the IQ conversion failed\n");
@@ -1850,7 +2001,7 @@ int main(int argc, char *argv[])
                 fprintf(stderr, "  PRN %2d: gain %5d .. %5d  (%+.2f .. %+.2f dB)\n", prn, prn_gain_lo[prn], prn_gain_hi[prn],
                         prn_gain_lo[prn] > 0 ? 20.0 * log10(prn_gain_lo[prn] / 128.0) : -INFINITY, prn_gain_hi[prn] > 0 ? 20.0 * log10(prn_gain_hi[prn] / 128.0) : -INFINITY);
     }
-    if (iq_format == GAL_IQ_IBYTE || mix_on || power_on || fir_on || agc_on) {
+    if (iq_format == GAL_IQ_IBYTE || mix_on || power_on || mp_on || fir_on || agc_on) {
         // (stderr: with -o - the data go to stdout)
         uint64_t n_sat = 0;
         const double n_val = (double)emitted * cfg.samples_per_epoch * 2;

@@ -103,6 +103,9 @@ hipError_t galk_launch_iq_agc(const int16_t *in, uint64_t n, uint32_t off0, int 
                               const unsigned long long *state_in, unsigned long long *state_out, void *scratch, void *out, uint32_t *gains_out,
                               unsigned long long *sat, hipStream_t st);
 uint64_t galk_agc_scratch_bytes(uint64_t n, uint32_t off0, uint32_t block_len);
+hipError_t galk_launch_iq_echo(const int16_t *const *parts_dev, const int16_t *const *hist_in_dev, int16_t *const *hist_out_dev, const int *gain_dev,
+                               const void *rows_dev, const int *part_of_dev, int n_parts, int n_echo, int n_epochs, int samples_per_epoch, int wide,
+                               int16_t *out, unsigned long long *sat, hipStream_t st);
 hipError_t galk_launch_iq_wsum(const int16_t *const *parts_dev, const int *gain_dev, int n_parts, int n_epochs, int samples_per_epoch, int wide,
                                int16_t *out, unsigned long long *sat, hipStream_t st);
 hipError_t galk_launch_corr(int format, const void *buf, uint64_t n_eff, uint64_t code_ph0, uint64_t code_dph, uint32_t carr_ph0,
@@ -344,6 +347,16 @@ struct gal_synth {
     void *own_parts = nullptr;  // gal_synth_run_gains: the streams of the slot groups, one behind the other
     int gain_runs = 0;          // ... synthesis runs its last call took (gal_synth_gain_runs)
     size_t own_parts_bytes = 0;
+    // gal_synth_iq_mpath (iq_echo.hip): d_mp_hist = GAL_ECHO_LINES history lines x 2 buffers of GAL_ECHO_MAX_DELAY complex samples (a call
+    // reads buffer mp_cur[id] of a line it names and writes the other); h_mp / d_mp = the table of the last call (part, history-in and
+    // history-out pointers, gains, echo rows, part indices), pinned on the host and on the device; ev_mp = that call's kernels are done
+    uint32_t *d_mp_hist = nullptr;
+    uint8_t mp_cur[GAL_ECHO_LINES] = {};
+    char *h_mp = nullptr;
+    char *d_mp = nullptr;
+    size_t mp_bytes = 0;
+    hipEvent_t ev_mp = nullptr;
+    bool mp_pending = false;
     // gal_synth_fir_set / gal_synth_iq_fir (iq_fir.hip): the tap-pair table and the two history buffers of kFirHist complex samples, one
     // device block; h_fir = the pinned copy of the table the upload reads; ev_fir = the last filter kernel of the handle is done
     uint32_t *d_fir = nullptr;
@@ -605,6 +618,10 @@ int gal_synth_destroy(gal_synth_t *h)
     if (h->d_gain) hipFree(h->d_gain);
     if (h->h_gain) hipHostFree(h->h_gain);
     if (h->ev_gain) hipEventDestroy(h->ev_gain);
+    if (h->d_mp_hist) hipFree(h->d_mp_hist);
+    if (h->d_mp) hipFree(h->d_mp);
+    if (h->h_mp) hipHostFree(h->h_mp);
+    if (h->ev_mp) hipEventDestroy(h->ev_mp);
     if (h->d_fir) hipFree(h->d_fir);
     if (h->h_fir) hipHostFree(h->h_fir);
     if (h->ev_fir) hipEventDestroy(h->ev_fir);
@@ -2041,6 +2058,201 @@ int gal_synth_iq_wsum(gal_synth_t *h, const int16_t *const *parts_dev, int32_t n
     return GAL_OK;
 }
 
+// ---- per-satellite multipath (iq_echo.hip) ----------------------------------------------------------------------------------------
+int gal_synth_mpath_check(const gal_iq_echo_t *echo_rows, int32_t n_echo, int32_t n_epochs, const int32_t *part_of_echo, int32_t n_parts)
+{
+    const char *who = "gal_synth_mpath_check";
+    if (n_echo < 0 || n_echo > GAL_ECHO_MAX) return fail(GAL_E_INVAL, "%s: %d echoes (0..%d)", who, n_echo, GAL_ECHO_MAX);
+    if (n_epochs < 1 || n_parts < 1 || n_parts > GAL_ENGINE_MAX_CHAN)
+        return fail(GAL_E_INVAL, "%s: n_epochs %d (>= 1) or n_parts %d (1..%d)", who, n_epochs, n_parts, GAL_ENGINE_MAX_CHAN);
+    if (n_echo == 0) return GAL_OK;
+    if (!echo_rows || !part_of_echo) return fail(GAL_E_INVAL, "%s: null argument", who);
+    for (int r = 0; r < n_echo; ++r)
+        if (part_of_echo[r] < 0 || part_of_echo[r] >= n_parts)
+            return fail(GAL_E_INVAL, "%s: echo %d on part %d (0..%d)", who, r, part_of_echo[r], n_parts - 1);
+    for (int e = 0; e < n_epochs; ++e)
+        for (int r = 0; r < n_echo; ++r) {
+            const gal_iq_echo_t &q = echo_rows[(size_t)e * n_echo + r];
+            if (q.gain_q7 > GAL_GAIN_MAX) return fail(GAL_E_INVAL, "%s: gain %u of epoch %d, echo %d (0..%d)", who, q.gain_q7, e, r, GAL_GAIN_MAX);
+            if (q.delay > GAL_ECHO_MAX_DELAY)
+                return fail(GAL_E_INVAL, "%s: delay %u of epoch %d, echo %d (0..%d samples)", who, q.delay, e, r, GAL_ECHO_MAX_DELAY);
+            if (q.reserved != 0) return fail(GAL_E_INVAL, "%s: reserved = %u in epoch %d, echo %d (must be 0)", who, q.reserved, e, r);
+        }
+    return GAL_OK;
+}
+
+static bool mpath_echo_ok(const gal_mpath_echo_t *q) { return q->delay <= GAL_ECHO_MAX_DELAY && q->alpha_q12 <= 8192; }
+
+int gal_synth_mpath_make(double delay_s, double rel_db, double phase_deg, double fade_hz, double sample_rate, gal_mpath_echo_t *out)
+{
+    const char *who = "gal_synth_mpath_make";
+    if (!out) return fail(GAL_E_INVAL, "%s: null argument", who);
+    if (!std::isfinite(delay_s) || !std::isfinite(rel_db) || !std::isfinite(phase_deg) || !std::isfinite(fade_hz) || !std::isfinite(sample_rate) ||
+        sample_rate <= 0.0 || delay_s < 0.0)
+        return fail(GAL_E_INVAL, "%s: delay %g s (>= 0), %g dB, %g deg, %g Hz and the rate %g Hz (> 0) must be finite", who, delay_s, rel_db,
+                    phase_deg, fade_hz, sample_rate);
+    const double d = delay_s * sample_rate;
+    if (d > GAL_ECHO_MAX_DELAY + 0.5) return fail(GAL_E_INVAL, "%s: a delay of %g samples, more than %d", who, d, GAL_ECHO_MAX_DELAY);
+    const long long delay = llround(d);
+    if (delay > GAL_ECHO_MAX_DELAY) return fail(GAL_E_INVAL, "%s: a delay of %lld samples, more than %d", who, delay, GAL_ECHO_MAX_DELAY);
+    const double a = 4096.0 * pow(10.0, rel_db / 20.0);
+    if (!(a <= 8192.0)) return fail(GAL_E_INVAL, "%s: %g dB is an amplitude of %g, more than 2 (+6.02 dB)", who, rel_db, a / 4096.0);
+    const double turns = phase_deg / 360.0;
+    const long long ph0 = llround((turns - floor(turns)) * 4294967296.0);
+    const double step = fade_hz / sample_rate * 4294967296.0;
+    if (!(fabs(step) < 2147483647.5)) return fail(GAL_E_INVAL, "%s: a fading rate of %g Hz must lie inside +-sample_rate / 2", who, fade_hz);
+    const long long dph = llround(step);
+    if (dph < INT32_MIN || dph > INT32_MAX) return fail(GAL_E_INVAL, "%s: a fading rate of %g Hz must lie inside +-sample_rate / 2", who, fade_hz);
+    out->delay = (uint32_t)delay;
+    out->alpha_q12 = (uint32_t)llround(a);
+    out->ph0 = (uint32_t)(ph0 & 0xffffffffll);
+    out->dph = (int32_t)dph;
+    return GAL_OK;
+}
+
+int gal_synth_mpath_row(const gal_mpath_echo_t *echo, uint16_t slot_gain_q7, uint64_t epoch, int32_t samples_per_epoch, gal_iq_echo_t *row)
+{
+    const char *who = "gal_synth_mpath_row";
+    if (!echo || !row) return fail(GAL_E_INVAL, "%s: null argument", who);
+    if (samples_per_epoch < 1 || slot_gain_q7 > GAL_GAIN_MAX || !mpath_echo_ok(echo))
+        return fail(GAL_E_INVAL, "%s: samples_per_epoch %d (>= 1), gain %u (0..%d), delay %u (0..%d) or alpha_q12 %u (0..8192)", who,
+                    samples_per_epoch, slot_gain_q7, GAL_GAIN_MAX, echo->delay, GAL_ECHO_MAX_DELAY, echo->alpha_q12);
+    const uint32_t A = ((uint32_t)slot_gain_q7 * echo->alpha_q12 + 2048u) >> 12;
+    row->gain_q7 = (uint16_t)std::min<uint32_t>(A, GAL_GAIN_MAX);
+    row->delay = (uint16_t)echo->delay;
+    row->ph0 = echo->ph0 + (uint32_t)epoch * (uint32_t)samples_per_epoch * (uint32_t)echo->dph;  // (exact modulo 2^32)
+    row->dph = echo->dph;
+    row->reserved = 0;
+    return GAL_OK;
+}
+
+static constexpr size_t kMpLineWords = GAL_ECHO_MAX_DELAY;                          // one history line: complex samples = uint32
+static constexpr size_t kMpHistBytes = sizeof(uint32_t) * kMpLineWords * 2 * GAL_ECHO_LINES;  // two buffers per line
+
+static int mpath_wait(gal_synth *h)
+{
+    if (h->mp_pending) {
+        HIP_TRY(hipEventSynchronize(h->ev_mp));
+        h->mp_pending = false;
+    }
+    return GAL_OK;
+}
+
+int gal_synth_mpath_reset(gal_synth_t *h)
+{
+    if (!h) return fail(GAL_E_INVAL, "null handle");
+    if (!h->d_mp_hist) return GAL_OK;  // (the lines are made zeroed)
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = handle_stream(h);
+    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
+    const int rc = mpath_wait(h);  // (whatever stream the last call ran on)
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(h->d_mp_hist, 0, kMpHistBytes, st));
+    return GAL_OK;
+}
+
+int gal_synth_iq_mpath(gal_synth_t *h, const int16_t *const *parts_dev, int32_t n_parts, const int32_t *hist_id, const uint16_t *gain_q7,
+                       int32_t n_epochs, const int32_t *part_of_echo, const gal_iq_echo_t *echo_rows, int32_t n_echo, int16_t *out_dev)
+{
+    const char *who = "gal_synth_iq_mpath";
+    if (!h) return fail(GAL_E_INVAL, "null handle");
+    if (!parts_dev || !gain_q7 || n_parts < 1 || n_parts > GAL_ENGINE_MAX_CHAN || n_epochs < 1)
+        return fail(GAL_E_INVAL, "%s: null argument, n_parts %d (1..%d) or n_epochs %d (>= 1)", who, n_parts, GAL_ENGINE_MAX_CHAN, n_epochs);
+    if (!out_dev || ((uintptr_t)out_dev & 15)) return fail(GAL_E_INVAL, "%s: device pointers must be non-null and 16-byte aligned", who);
+    int rc = gal_synth_mpath_check(echo_rows, n_echo, n_epochs, part_of_echo, n_parts);
+    if (rc) return rc;
+    const size_t bytes = (size_t)n_epochs * (size_t)h->cfg.samples_per_epoch * 4;
+    const char *o = (const char *)out_dev, *oe = o + bytes;
+    for (int k = 0; k < n_parts; ++k) {
+        const char *x = (const char *)parts_dev[k];
+        if (!x || ((uintptr_t)x & 15)) return fail(GAL_E_INVAL, "%s: device pointers must be non-null and 16-byte aligned (part %d)", who, k);
+        if (x < oe && o < x + bytes) return fail(GAL_E_INVAL, "%s: part %d and the output overlap", who, k);
+        if (hits_batch_in_flight(h, x, bytes)) return fail(GAL_E_STATE, "%s: input of the batch in flight (call gal_synth_finish first)", who);
+    }
+    if (hits_batch_in_flight(h, out_dev, bytes)) return fail(GAL_E_STATE, "%s: output of the batch in flight (call gal_synth_finish first)", who);
+    int id[GAL_ENGINE_MAX_CHAN];
+    uint64_t named = 0;  // the lines this call names
+    for (int k = 0; k < n_parts; ++k) {
+        id[k] = hist_id ? hist_id[k] : k;
+        if (id[k] < -1 || id[k] >= GAL_ECHO_LINES) return fail(GAL_E_INVAL, "%s: hist_id %d of part %d (-1..%d)", who, id[k], k, GAL_ECHO_LINES - 1);
+        if (id[k] < 0) continue;
+        if (named >> id[k] & 1) return fail(GAL_E_INVAL, "%s: history line %d is named by two parts", who, id[k]);
+        named |= (uint64_t)1 << id[k];
+    }
+    for (int r = 0; r < n_echo; ++r)
+        if (id[part_of_echo[r]] < 0) return fail(GAL_E_INVAL, "%s: echo %d repeats part %d, which has no history line (hist_id -1)", who, r, part_of_echo[r]);
+    uint64_t row_max = 0;  // the largest of sum g + 2 sum A over the epochs: what w needs (iq_echo.hip)
+    for (int e = 0; e < n_epochs; ++e) {
+        uint64_t row = 0;
+        for (int k = 0; k < n_parts; ++k) {
+            const uint16_t g = gain_q7[(size_t)e * n_parts + k];
+            if (g > GAL_GAIN_MAX) return fail(GAL_E_INVAL, "%s: gain %u of epoch %d, part %d (0..%d)", who, g, e, k, GAL_GAIN_MAX);
+            row += g;
+        }
+        for (int r = 0; r < n_echo; ++r) row += 2 * (uint64_t)echo_rows[(size_t)e * n_echo + r].gain_q7;
+        row_max = std::max(row_max, row);
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = handle_stream(h);
+    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
+    rc = ensure_sat_counter(h, st);
+    if (rc) return rc;
+    if (!h->ev_mp) HIP_TRY(hipEventCreateWithFlags(&h->ev_mp, hipEventDisableTiming));
+    rc = mpath_wait(h);  // one table per handle: the call before has read it
+    if (rc) return rc;
+    if (!h->d_mp_hist) {
+        if (hipMalloc((void **)&h->d_mp_hist, kMpHistBytes) != hipSuccess) {
+            (void)hipGetLastError();
+            h->d_mp_hist = nullptr;
+            return fail(GAL_E_NOMEM, "%s: the history lines of %zu bytes could not be allocated", who, kMpHistBytes);
+        }
+        HIP_TRY(hipMemsetAsync(h->d_mp_hist, 0, kMpHistBytes, st));
+        memset(h->mp_cur, 0, sizeof(h->mp_cur));
+    }
+    // the table of this call: part pointers, history-in and history-out pointers, gains, echo rows, part indices
+    const size_t o_hin = sizeof(void *) * GAL_ENGINE_MAX_CHAN, o_hout = 2 * o_hin, o_gain = 3 * o_hin;
+    const size_t o_rows = align_up(o_gain + (size_t)n_epochs * n_parts * sizeof(int), 16);
+    const size_t o_pof = o_rows + (size_t)n_epochs * n_echo * sizeof(gal_iq_echo_t), need = o_pof + sizeof(int) * GAL_ECHO_MAX;
+    if (need > h->mp_bytes) {
+        if (h->h_mp) hipHostFree(h->h_mp);
+        if (h->d_mp) hipFree(h->d_mp);
+        h->h_mp = h->d_mp = nullptr;
+        h->mp_bytes = 0;
+        const size_t cap = need + need / 4;
+        if (hipHostMalloc((void **)&h->h_mp, cap, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&h->d_mp, cap) != hipSuccess) {
+            (void)hipGetLastError();
+            if (h->h_mp) hipHostFree(h->h_mp);
+            h->h_mp = nullptr;
+            return fail(GAL_E_NOMEM, "%s: the table of %zu bytes could not be allocated", who, cap);
+        }
+        h->mp_bytes = cap;
+    }
+    memset(h->h_mp, 0, o_gain);
+    memcpy(h->h_mp, parts_dev, sizeof(void *) * (size_t)n_parts);
+    uint32_t **const hin = (uint32_t **)(h->h_mp + o_hin), **const hout = (uint32_t **)(h->h_mp + o_hout);
+    for (int k = 0; k < n_parts; ++k) {
+        if (id[k] < 0) continue;
+        uint32_t *const line = h->d_mp_hist + (size_t)id[k] * 2 * kMpLineWords;
+        hin[k] = line + h->mp_cur[id[k]] * kMpLineWords;
+        hout[k] = line + (h->mp_cur[id[k]] ^ 1) * kMpLineWords;
+    }
+    int *const hg = (int *)(h->h_mp + o_gain);
+    for (size_t i = 0; i < (size_t)n_epochs * n_parts; ++i) hg[i] = gain_q7[i];
+    if (n_echo > 0) {
+        memcpy(h->h_mp + o_rows, echo_rows, (size_t)n_epochs * n_echo * sizeof(gal_iq_echo_t));
+        memcpy(h->h_mp + o_pof, part_of_echo, sizeof(int) * (size_t)n_echo);
+    }
+    HIP_TRY(hipMemcpyAsync(h->d_mp, h->h_mp, need, hipMemcpyHostToDevice, st));
+    HIP_TRY(galk_launch_iq_echo((const int16_t *const *)h->d_mp, (const int16_t *const *)(h->d_mp + o_hin), (int16_t *const *)(h->d_mp + o_hout),
+                                (const int *)(h->d_mp + o_gain), h->d_mp + o_rows, (const int *)(h->d_mp + o_pof), n_parts, n_echo, n_epochs,
+                                h->cfg.samples_per_epoch, row_max > 65535 ? 1 : 0, out_dev, h->d_iq_sat, st));
+    for (int k = 0; k < n_parts; ++k)
+        if (id[k] >= 0) h->mp_cur[id[k]] ^= 1;
+    HIP_TRY(hipEventRecord(h->ev_mp, st));
+    h->mp_pending = true;
+    return GAL_OK;
+}
+
 // ---- front-end FIR filter (iq_fir.hip) ---------------------------------------------------------------------------------------------
 static constexpr int kFirTableWords = 4 * 33;  // (GE, GO) x 2 pairs per trip, (128 / 2 + 1 + 1) / 2 trips at most
 static constexpr int kFirHist = 128;           // complex samples of history, as iq_fir.hip keeps them
@@ -2471,10 +2683,12 @@ int gal_synth_iq_agc(gal_synth_t *h, const int16_t *in_dev, size_t n_samples, in
     return GAL_OK;
 }
 
-int gal_synth_run_gains(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_epochs, const gal_chan_state_t *state_in,
-                        const uint16_t *gain_q7, int16_t *iq_dev, gal_chan_state_t *state_out)
+// gal_synth_run_gains (n_echo = 0) and gal_synth_run_mpath: the slot groups, one synthesis run per group, then the weighted sum or the
+// echo pass
+static int run_groups(const char *who, gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_epochs, const gal_chan_state_t *state_in,
+                      const uint16_t *gain_q7, const int32_t *slot_of_echo, const gal_iq_echo_t *echo_rows, int32_t n_echo, int16_t *iq_dev,
+                      gal_chan_state_t *state_out)
 {
-    const char *who = "gal_synth_run_gains";
     if (!h || !params || !gain_q7 || !iq_dev || n_epochs < 1) return fail(GAL_E_INVAL, "%s: null argument or n_epochs %d (>= 1)", who, n_epochs);
     if ((uintptr_t)iq_dev & 15) return fail(GAL_E_INVAL, "%s: iq_dev must be 16-byte aligned", who);
     if (h->in_flight) return fail(GAL_E_STATE, "%s while a batch is in flight: call gal_synth_finish first", who);
@@ -2490,16 +2704,20 @@ int gal_synth_run_gains(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t 
     struct Group {
         std::vector<int> slots;
         std::vector<int> g;  // [E]; -1: no slot of the group is active in that epoch
+        bool solo = false;   // the one slot of the group carries an echo: no other slot joins it
     };
     std::vector<Group> groups;
     std::vector<int> group_of(S, -1);
+    // a slot that carries an echo is a group of its own, idle or not: its part is what the echo delays, its line follows the slot
+    std::vector<char> solo(S, 0);
+    for (int r = 0; r < n_echo; ++r) solo[slot_of_echo[r]] = 1;
     for (int s = 0; s < S; ++s) {
-        bool active = false;
+        bool active = solo[s];
         for (int e = 0; e < E && !active; ++e) active = params[(size_t)e * S + s].prn > 0;
         if (!active) continue;
-        size_t k = 0;
+        size_t k = solo[s] ? groups.size() : 0;
         for (; k < groups.size(); ++k) {
-            bool fits = true;
+            bool fits = !groups[k].solo;
             for (int e = 0; e < E && fits; ++e)
                 fits = params[(size_t)e * S + s].prn <= 0 || groups[k].g[e] < 0 || groups[k].g[e] == (int)gain_q7[(size_t)e * S + s];
             if (fits) break;
@@ -2507,6 +2725,7 @@ int gal_synth_run_gains(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t 
         if (k == groups.size()) {
             groups.emplace_back();
             groups[k].g.assign(E, -1);
+            groups[k].solo = solo[s];
         }
         groups[k].slots.push_back(s);
         group_of[s] = (int)k;
@@ -2514,7 +2733,7 @@ int gal_synth_run_gains(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t 
             if (params[(size_t)e * S + s].prn > 0) groups[k].g[e] = gain_q7[(size_t)e * S + s];
     }
     const int n_parts = groups.empty() ? 1 : (int)groups.size();  // (an empty sky: one run of nothing)
-    bool unity = n_parts == 1;  // one part at gain 128 wherever it is not zero: y = x, the run goes straight into iq_dev
+    bool unity = n_parts == 1 && n_echo == 0;  // one part at gain 128 wherever it is not zero: y = x, the run goes straight into iq_dev
     if (!groups.empty())
         for (int e = 0; e < E && unity; ++e) unity = groups[0].g[e] < 0 || groups[0].g[e] == GAL_GAIN_UNITY;
     const size_t bytes = (size_t)E * (size_t)h->cfg.samples_per_epoch * 4;
@@ -2524,6 +2743,11 @@ int gal_synth_run_gains(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t 
         HIP_TRY(hipSetDevice(h->device));
         HIP_TRY(hipEventSynchronize(h->ev_gain));
         h->gain_pending = false;
+    }
+    if (h->mp_pending) {
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(hipEventSynchronize(h->ev_mp));
+        h->mp_pending = false;
     }
     h->gain_runs = 0;
     if (!unity && bytes * (size_t)n_parts > h->own_parts_bytes) {
@@ -2561,11 +2785,39 @@ int gal_synth_run_gains(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t 
         std::vector<uint16_t> gp((size_t)E * n_parts);
         for (int e = 0; e < E; ++e)
             for (int k = 0; k < n_parts; ++k) gp[(size_t)e * n_parts + k] = (uint16_t)(groups[k].g[e] < 0 ? 0 : groups[k].g[e]);
-        const int rc = gal_synth_iq_wsum(h, parts, n_parts, gp.data(), E, iq_dev);
+        int rc;
+        if (n_echo > 0) {
+            std::vector<int32_t> hist_id(n_parts, -1), part_of(n_echo);
+            for (int k = 0; k < n_parts; ++k)
+                if (groups[k].solo) hist_id[k] = groups[k].slots[0];
+            for (int r = 0; r < n_echo; ++r) part_of[r] = group_of[slot_of_echo[r]];
+            rc = gal_synth_iq_mpath(h, parts, n_parts, hist_id.data(), gp.data(), E, part_of.data(), echo_rows, n_echo, iq_dev);
+        } else {
+            rc = gal_synth_iq_wsum(h, parts, n_parts, gp.data(), E, iq_dev);
+        }
         if (rc != GAL_OK) return rc;
     }
     if (state_out) memcpy(state_out, st_all.data(), sizeof(gal_chan_state_t) * S);
     return GAL_OK;
+}
+
+int gal_synth_run_gains(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_epochs, const gal_chan_state_t *state_in,
+                        const uint16_t *gain_q7, int16_t *iq_dev, gal_chan_state_t *state_out)
+{
+    return run_groups("gal_synth_run_gains", h, params, n_epochs, state_in, gain_q7, nullptr, nullptr, 0, iq_dev, state_out);
+}
+
+int gal_synth_run_mpath(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_epochs, const gal_chan_state_t *state_in,
+                        const uint16_t *gain_q7, const int32_t *slot_of_echo, const gal_iq_echo_t *echo_rows, int32_t n_echo, int16_t *iq_dev,
+                        gal_chan_state_t *state_out)
+{
+    const char *who = "gal_synth_run_mpath";
+    if (n_echo == 0) return run_groups(who, h, params, n_epochs, state_in, gain_q7, nullptr, nullptr, 0, iq_dev, state_out);
+    if (!h) return fail(GAL_E_INVAL, "%s: null handle", who);
+    if (h->cfg.n_slots > GAL_ECHO_LINES) return fail(GAL_E_INVAL, "%s: %d slots, more than the %d history lines", who, h->cfg.n_slots, GAL_ECHO_LINES);
+    const int rc = gal_synth_mpath_check(echo_rows, n_echo, n_epochs, slot_of_echo, h->cfg.n_slots);
+    if (rc) return rc;
+    return run_groups(who, h, params, n_epochs, state_in, gain_q7, slot_of_echo, echo_rows, n_echo, iq_dev, state_out);
 }
 
 int gal_synth_gain_runs(const gal_synth_t *h, int32_t *n_runs)

@@ -152,6 +152,33 @@ AGC_FIELDS = ("block_len", "window", "target_q8", "gain_min_q12", "gain_max_q12"
 assert ctypes.sizeof(_Agc) == 32
 
 
+class _Echo(ctypes.Structure):  # gal_iq_echo_t (16 bytes)
+    _fields_ = [
+        ("gain_q7", ctypes.c_uint16),
+        ("delay", ctypes.c_uint16),
+        ("ph0", ctypes.c_uint32),
+        ("dph", ctypes.c_int32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+assert ctypes.sizeof(_Echo) == 16
+# one row of an echo table as numpy sees it: echo_rows are arrays of this type, [n_epochs, n_echo]
+ECHO_DTYPE = np.dtype([("gain_q7", "<u2"), ("delay", "<u2"), ("ph0", "<u4"), ("dph", "<i4"), ("reserved", "<u4")])
+assert ECHO_DTYPE.itemsize == 16
+GAL_ECHO_MAX = 32
+GAL_ECHO_MAX_DELAY = 1024
+GAL_ECHO_LINES = 64
+
+
+class _MpathEcho(ctypes.Structure):  # gal_mpath_echo_t (16 bytes)
+    _fields_ = [("delay", ctypes.c_uint32), ("alpha_q12", ctypes.c_uint32), ("ph0", ctypes.c_uint32), ("dph", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(_MpathEcho) == 16
+MPATH_ECHO_FIELDS = tuple(name for name, _ in _MpathEcho._fields_)
+
+
 class _CorrReq(ctypes.Structure):  # gal_corr_req_t (56 bytes)
     _fields_ = [
         ("prn", ctypes.c_int32),
@@ -210,6 +237,12 @@ EXPORTED_SYMBOLS = (
     "gal_synth_run_gains",
     "gal_synth_gain_runs",
     "gal_synth_gain_q7",
+    "gal_synth_mpath_check",
+    "gal_synth_mpath_reset",
+    "gal_synth_iq_mpath",
+    "gal_synth_run_mpath",
+    "gal_synth_mpath_make",
+    "gal_synth_mpath_row",
     "gal_synth_fir_check",
     "gal_synth_fir_lowpass",
     "gal_synth_fir_set",
@@ -301,6 +334,18 @@ def load_library(hooks=False):
     lib.gal_synth_gain_runs.restype = ctypes.c_int
     lib.gal_synth_gain_q7.argtypes = [ctypes.c_double, ctypes.c_double, vp, ctypes.c_double, ctypes.POINTER(ctypes.c_uint16)]
     lib.gal_synth_gain_q7.restype = ctypes.c_int
+    lib.gal_synth_mpath_check.argtypes = [vp, i32, i32, vp, i32]
+    lib.gal_synth_mpath_check.restype = ctypes.c_int
+    lib.gal_synth_mpath_reset.argtypes = [vp]
+    lib.gal_synth_mpath_reset.restype = ctypes.c_int
+    lib.gal_synth_iq_mpath.argtypes = [vp, ctypes.POINTER(vp), i32, vp, vp, i32, vp, vp, i32, vp]
+    lib.gal_synth_iq_mpath.restype = ctypes.c_int
+    lib.gal_synth_run_mpath.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp]
+    lib.gal_synth_run_mpath.restype = ctypes.c_int
+    lib.gal_synth_mpath_make.argtypes = [ctypes.c_double] * 5 + [ctypes.POINTER(_MpathEcho)]
+    lib.gal_synth_mpath_make.restype = ctypes.c_int
+    lib.gal_synth_mpath_row.argtypes = [ctypes.POINTER(_MpathEcho), ctypes.c_uint16, ctypes.c_uint64, i32, ctypes.POINTER(_Echo)]
+    lib.gal_synth_mpath_row.restype = ctypes.c_int
     lib.gal_synth_fir_check.argtypes = [vp, i32]
     lib.gal_synth_fir_check.restype = ctypes.c_int
     lib.gal_synth_fir_lowpass.argtypes = [ctypes.c_double, ctypes.c_double, i32, vp]
@@ -547,6 +592,60 @@ def agc_blocks(first_sample, n_samples, block_len):
     return int(load_library().gal_synth_agc_blocks(int(first_sample), int(n_samples), int(block_len)))
 
 
+def _echo_table(echo_rows, n_epochs, who):
+    """echo_rows -> a contiguous ECHO_DTYPE array [n_epochs, n_echo] (None or an empty one: no echoes)."""
+    if echo_rows is None:
+        return np.zeros((n_epochs, 0), dtype=ECHO_DTYPE)
+    r = np.ascontiguousarray(echo_rows, dtype=ECHO_DTYPE)
+    if r.ndim != 2 or r.shape[0] != n_epochs:
+        raise ValueError("%s: echo_rows must have shape [n_epochs=%d, n_echo]" % (who, n_epochs))
+    return r
+
+
+def mpath_check(echo_rows, part_of_echo, n_parts):
+    """gal_synth_mpath_check (no GPU needed): raises GalSynthError(GAL_E_INVAL) for an echo table [n_epochs, n_echo] (ECHO_DTYPE) or
+    part indices that the echo pass would refuse."""
+    lib = load_library()
+    r = np.ascontiguousarray(echo_rows, dtype=ECHO_DTYPE)
+    if r.ndim != 2:
+        raise ValueError("mpath_check: echo_rows must have shape [n_epochs, n_echo]")
+    pof = np.ascontiguousarray(part_of_echo, dtype=np.int32)
+    if pof.shape != (r.shape[1],):
+        raise ValueError("mpath_check: part_of_echo must have n_echo = %d entries" % r.shape[1])
+    rc = lib.gal_synth_mpath_check(r.ctypes.data, r.shape[1], r.shape[0], pof.ctypes.data, int(n_parts))
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+
+
+def mpath_make(delay_s, rel_db, phase_deg=0.0, fade_hz=0.0, sample_rate=2.6e6):
+    """gal_synth_mpath_make (no GPU needed): one echo from physical figures as a dict -- delay (samples), alpha_q12 (amplitude relative
+    to the direct signal, 4096 = equal), ph0 and dph (2^-32 cycles, per sample)."""
+    lib = load_library()
+    q = _MpathEcho()
+    rc = lib.gal_synth_mpath_make(float(delay_s), float(rel_db), float(phase_deg), float(fade_hz), float(sample_rate), ctypes.byref(q))
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+    return {k: int(getattr(q, k)) for k in MPATH_ECHO_FIELDS}
+
+
+def mpath_rows(echo, slot_gain_q7, first_epoch, samples_per_epoch):
+    """gal_synth_mpath_row (no GPU needed) for the epochs first_epoch, first_epoch + 1, ... of the whole stream: the column of an echo
+    table (ECHO_DTYPE, one row per entry of slot_gain_q7, the Q7 gains of the direct signal) for the dict `echo` of mpath_make."""
+    lib = load_library()
+    q = _MpathEcho(**{k: int(echo[k]) for k in MPATH_ECHO_FIELDS})
+    gains = np.asarray(slot_gain_q7).ravel()
+    out = np.zeros(gains.size, dtype=ECHO_DTYPE)
+    row = _Echo()
+    for e, g in enumerate(gains):
+        if not 0 <= int(g) <= 65535:
+            raise ValueError("mpath_rows: a gain does not fit a uint16")
+        rc = lib.gal_synth_mpath_row(ctypes.byref(q), int(g), int(first_epoch) + e, int(samples_per_epoch), ctypes.byref(row))
+        if rc != 0:
+            raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+        out[e] = (row.gain_q7, row.delay, row.ph0, row.dph, row.reserved)
+    return out
+
+
 def _corr_struct(req):
     """dict with the fields of gal_corr_req_t (grids default to one prompt cell, max_periods to 1), or a _CorrReq."""
     if isinstance(req, _CorrReq):
@@ -768,6 +867,56 @@ class SynthEngine:
         g = np.ascontiguousarray(g, dtype=np.uint16)
         ptrs = (ctypes.c_void_p * max(1, len(part_ptrs)))(*[int(p) for p in part_ptrs])
         self._check(self._lib.gal_synth_iq_wsum(self._h, ptrs, len(part_ptrs), g.ctypes.data, g.shape[0], ctypes.c_void_p(int(out_ptr))))
+
+    def iq_mpath(self, part_ptrs, gain_q7, out_ptr, part_of_echo=(), echo_rows=None, hist_id=None):
+        """gal_synth_iq_mpath, enqueued on the handle's stream: iq_wsum plus the echoes echo_rows [n_epochs, n_echo] (ECHO_DTYPE) of the
+        parts part_of_echo [n_echo].  hist_id: per part the history line (0 .. 63) that carries its last 1024 samples from call to call,
+        -1 for none; None names line k for part k.  Any cut of a stream into calls of whole epochs gives the same bytes.
+        iq_saturated() is the fence and counts the clamped values."""
+        g = np.asarray(gain_q7)
+        if g.ndim != 2 or g.shape[1] != len(part_ptrs):
+            raise ValueError("iq_mpath: gain_q7 must have shape [n_epochs, n_parts=%d]" % len(part_ptrs))
+        if g.size and (g.min() < 0 or g.max() > 65535):
+            raise ValueError("iq_mpath: a gain does not fit a uint16")
+        g = np.ascontiguousarray(g, dtype=np.uint16)
+        rows = _echo_table(echo_rows, g.shape[0], "iq_mpath")
+        pof = np.ascontiguousarray(part_of_echo, dtype=np.int32).ravel()
+        if pof.size != rows.shape[1]:
+            raise ValueError("iq_mpath: part_of_echo must have n_echo = %d entries" % rows.shape[1])
+        hid = None if hist_id is None else np.ascontiguousarray(hist_id, dtype=np.int32).ravel()
+        if hid is not None and hid.size != len(part_ptrs):
+            raise ValueError("iq_mpath: hist_id must have n_parts = %d entries" % len(part_ptrs))
+        ptrs = (ctypes.c_void_p * max(1, len(part_ptrs)))(*[int(p) for p in part_ptrs])
+        self._check(self._lib.gal_synth_iq_mpath(self._h, ptrs, len(part_ptrs), hid.ctypes.data if hid is not None else None, g.ctypes.data,
+                                                 g.shape[0], pof.ctypes.data if pof.size else None, rows.ctypes.data if rows.size else None,
+                                                 rows.shape[1], ctypes.c_void_p(int(out_ptr))))
+
+    def mpath_reset(self):
+        """gal_synth_mpath_reset: zero every history line of iq_mpath / run_mpath (enqueued): the next call starts its streams."""
+        self._check(self._lib.gal_synth_mpath_reset(self._h))
+
+    def run_mpath(self, params, gain_q7, iq_dev_ptr, slot_of_echo=(), echo_rows=None, state_in=None):
+        """gal_synth_run_mpath: run_gains with the echoes echo_rows [n_epochs, n_echo] (ECHO_DTYPE) of the channel slots slot_of_echo
+        [n_echo] -- every such slot is a synthesis run of its own, and its history follows the slot from batch to batch.  No echoes:
+        run_gains.  The echo pass is ENQUEUED when this returns (iq_saturated() is the fence).  Returns state_out."""
+        p = self._params(params)
+        s = self._state(state_in)
+        g = np.asarray(gain_q7)
+        if g.shape != p.shape:
+            raise ValueError("run_mpath: gain_q7 must have shape [n_epochs, n_slots=%d]" % self.n_slots)
+        if g.size and (g.min() < 0 or g.max() > 65535):
+            raise ValueError("run_mpath: a gain does not fit a uint16")
+        g = np.ascontiguousarray(g, dtype=np.uint16)
+        rows = _echo_table(echo_rows, p.shape[0], "run_mpath")
+        sof = np.ascontiguousarray(slot_of_echo, dtype=np.int32).ravel()
+        if sof.size != rows.shape[1]:
+            raise ValueError("run_mpath: slot_of_echo must have n_echo = %d entries" % rows.shape[1])
+        st = np.zeros(self.n_slots, dtype=CHAN_STATE_DTYPE)
+        self._check(self._lib.gal_synth_run_mpath(self._h, p.ctypes.data, p.shape[0], s.ctypes.data if s is not None else None, g.ctypes.data,
+                                                  sof.ctypes.data if sof.size else None, rows.ctypes.data if rows.size else None, rows.shape[1],
+                                                  ctypes.c_void_p(int(iq_dev_ptr)), st.ctypes.data))
+        self.n_epochs = p.shape[0]
+        return st
 
     def fir_set(self, taps):
         """gal_synth_fir_set: give the handle the front-end filter `taps` (int16 Q14, 1 .. GAL_FIR_MAX_TAPS, sum |h| <= 65535) and start

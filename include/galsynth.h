@@ -682,6 +682,87 @@ int gal_corr_from_epoch(const gal_chan_epoch_t *rec, double sample_rate, int64_t
 int gal_corr_cn0(const int64_t *out_host, const gal_corr_req_t *req, int32_t k_prompt, int32_t k_noise, int32_t d, double sample_rate,
                  double *cn0_dbhz, double *peak_ratio);
 
+/*
+ * Per-satellite multipath (not in the reference): a satellite's signal arrives a second time, later, weaker and
+ * with another carrier phase.  An echo of part p is the part's own STREAM, delayed by a whole number of samples -- code, data symbols
+ * and carrier together, as propagation delays them -- times a slowly rotating complex gain.  The pass takes the place of
+ * gal_synth_iq_wsum; the synthesis sees nothing of it.  A FIXED INTEGER FUNCTION of its inputs (tests/mpath_model.py states it in numpy).
+ *
+ * x_k[n] = complex int16 sample n of part k, g[e][k] its Q7 gain in epoch e, as for gal_synth_iq_wsum; N = samples_per_epoch.  Echo r
+ * (0 <= r < n_echo <= GAL_ECHO_MAX) has a constant part index p_r and, in every epoch e of the call, one row gal_iq_echo_t: gain A
+ * (Q7, 0 .. GAL_GAIN_MAX), delay D (0 .. GAL_ECHO_MAX_DELAY samples), phase ph0 at the epoch's first sample and phase step dph per
+ * sample (2^-32 cycles).  For the output sample n, e = n div N, m = n mod N, with the row of the OUTPUT sample's epoch:
+ *   u     = x_p[n - D]                       (n - D < 0: the part's history, below; the delay may reach back over any number of epochs)
+ *   i     = ((ph0 + m dph) mod 2^32) >> 22;  c = C[i], s = C[(i - 256) & 1023]            (C = gal_tables_cos1024(), Q12)
+ *   rI    = (uI c - uQ s + 2048) >> 12;  rQ = (uI s + uQ c + 2048) >> 12                  (arithmetic shifts; |r| <= 65536)
+ *   wI[n] = sum_k g[e][k] x_k.I[n] + sum_r A_r rI_r                                        (likewise Q)
+ *   y     = clamp((w + 64) >> 7, -32768, 32767)
+ * A value the clamp changes counts once in the handle's saturation counter.  n_echo = 0 is gal_synth_iq_wsum bit for bit.  w is formed
+ * in an int32 where sum_k g + 2 sum_r A <= 65535 in every epoch (|w| + 64 <= 65535 x 32768 + 64 < 2^31 for any int16 input), in 64
+ * bits otherwise: the same bits.
+ *
+ * History: the handle keeps GAL_ECHO_LINES = 64 lines of GAL_ECHO_MAX_DELAY complex samples.  hist_id[k] (NULL: k) names the line of
+ * part k, 0 .. 63, or -1: none.  For a part with a line, the samples in front of the call (n - D < 0) are the last 1024 samples that
+ * earlier calls gave under that id since the last gal_synth_mpath_reset (or the creation of the handle) -- zeros in front of those --,
+ * and after the call the line holds the part's last 1024 samples (a call shorter than that rolls the line).  So ANY CUT OF A STREAM
+ * INTO CALLS OF WHOLE EPOCHS GIVES THE SAME BYTES AS ONE CALL.  A line that no part of a call names stays as it is.
+ */
+#define GAL_ECHO_MAX 32
+#define GAL_ECHO_MAX_DELAY 1024
+#define GAL_ECHO_LINES 64
+typedef struct gal_iq_echo {
+    uint16_t gain_q7;   /* A: 0 .. GAL_GAIN_MAX, 128 = the part at unity                                                       */
+    uint16_t delay;     /* D: 0 .. GAL_ECHO_MAX_DELAY samples                                                                  */
+    uint32_t ph0;       /* phase at the epoch's first sample, 2^-32 cycles                                                     */
+    int32_t  dph;       /* phase step per sample, 2^-32 cycles                                                                 */
+    uint32_t reserved;  /* 0                                                                                                   */
+} gal_iq_echo_t;        /* 16 bytes */
+/* GAL_OK if the echo table is admitted, else GAL_E_INVAL: n_echo outside 0..GAL_ECHO_MAX, n_epochs < 1, n_parts outside
+ * 1..GAL_ENGINE_MAX_CHAN, and with n_echo > 0 a null pointer, a part index outside 0..n_parts-1, a gain above GAL_GAIN_MAX, a delay
+ * above GAL_ECHO_MAX_DELAY, reserved != 0.  echo_rows is [n_epochs][n_echo].  Host only, needs no GPU. */
+int gal_synth_mpath_check(const gal_iq_echo_t *echo_rows, int32_t n_echo, int32_t n_epochs, const int32_t *part_of_echo, int32_t n_parts);
+/* Zero every history line (enqueued on the handle's stream): the next call starts its streams.  GAL_E_INVAL for a null handle. */
+int gal_synth_mpath_reset(gal_synth_t *h);
+/* Enqueue on the handle's stream: y of the definition above into out_dev.  parts_dev, n_parts, gain_q7, n_epochs, out_dev and the
+ * rules are those of gal_synth_iq_wsum: 16-byte alignment, an out_dev that overlaps a part is refused, GAL_E_STATE for a buffer of the
+ * batch in flight, gal_synth_iq_saturated is the fence and the counter.  hist_id (HOST, n_parts entries, or NULL), part_of_echo (HOST,
+ * n_echo entries) and echo_rows (HOST, [n_epochs][n_echo]) are copied before the call returns; with n_echo = 0 the last two are not
+ * looked at.  A handle holds one table: a call waits (on the host) for the kernel of the call before it.  GAL_E_INVAL for what
+ * gal_synth_iq_wsum and gal_synth_mpath_check refuse, a hist_id outside -1..63, one line named by two parts, an echo on a part whose
+ * hist_id is -1; GAL_E_NOMEM if the table or the lines cannot be had. */
+int gal_synth_iq_mpath(gal_synth_t *h, const int16_t *const *parts_dev, int32_t n_parts, const int32_t *hist_id, const uint16_t *gain_q7,
+                       int32_t n_epochs, const int32_t *part_of_echo, const gal_iq_echo_t *echo_rows, int32_t n_echo, int16_t *out_dev);
+/* gal_synth_run_gains with echoes: slot_of_echo[r] (0 .. n_slots-1, n_slots <= GAL_ECHO_LINES) is the channel slot echo r repeats.
+ * Every slot that carries an echo is a group (a synthesis run) of its own, whatever its gains, also where it is idle in the whole
+ * batch, and its history line is its SLOT INDEX: the history follows the slot from batch to batch.  An echo repeats the SLOT's stream and
+ * a line is written only in calls in which its slot carries an echo: where another satellite takes over a slot, the first D delayed
+ * samples are the earlier occupant's if both fall into one call, and the line as it was last written if a call boundary lies between
+ * them, unless the caller calls gal_synth_mpath_reset.  gal_synth_iq_mpath takes the place of
+ * the weighted sum.  n_echo = 0 is gal_synth_run_gains, the single-run unity case included; gal_synth_gain_runs counts the runs.
+ * The refusals are those of gal_synth_run_gains, gal_synth_mpath_check (with the slots as parts) and gal_synth_iq_mpath. */
+int gal_synth_run_mpath(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_epochs, const gal_chan_state_t *state_in,
+                        const uint16_t *gain_q7, const int32_t *slot_of_echo, const gal_iq_echo_t *echo_rows, int32_t n_echo,
+                        int16_t *iq_dev, gal_chan_state_t *state_out);
+/* One echo from physical figures; host only, needs no GPU.  In double, operation for operation:
+ *   delay     = llround(delay_s x sample_rate)                           (samples, 0 .. GAL_ECHO_MAX_DELAY)
+ *   alpha_q12 = llround(4096 x 10^(rel_db / 20))                         (amplitude relative to the direct signal, at most 8192 = +6.02 dB)
+ *   ph0       = llround((phase_deg / 360 - floor(phase_deg / 360)) x 2^32) mod 2^32
+ *   dph       = llround(fade_hz / sample_rate x 2^32)                    (must fit an int32: |fade_hz| < sample_rate / 2)
+ * GAL_E_INVAL for a null `out`, an argument that is not finite, sample_rate <= 0, delay_s < 0 and a result outside the ranges above. */
+typedef struct gal_mpath_echo {
+    uint32_t delay;
+    uint32_t alpha_q12;
+    uint32_t ph0;
+    int32_t  dph;
+} gal_mpath_echo_t; /* 16 bytes */
+int gal_synth_mpath_make(double delay_s, double rel_db, double phase_deg, double fade_hz, double sample_rate, gal_mpath_echo_t *out);
+/* The row of `echo` in the epoch with the index `epoch` of the WHOLE stream, for a direct signal at the gain slot_gain_q7; host only:
+ *   gain_q7 = min(GAL_GAIN_MAX, (slot_gain_q7 x alpha_q12 + 2048) >> 12)
+ *   ph0     = (echo->ph0 + epoch x samples_per_epoch x dph) mod 2^32      (so that ph0[e + 1] = ph0[e] + N dph)
+ * delay and dph as they are, reserved = 0.  GAL_E_INVAL for a null pointer, samples_per_epoch < 1, a slot gain above GAL_GAIN_MAX, an
+ * echo outside the ranges of gal_synth_mpath_make. */
+int gal_synth_mpath_row(const gal_mpath_echo_t *echo, uint16_t slot_gain_q7, uint64_t epoch, int32_t samples_per_epoch, gal_iq_echo_t *row);
+
 /* Signal tables as the engine uses them (for tests and for the oracle to share DATA, not code). */
 const uint32_t *gal_tables_e1b(void);   /* [50][128] */
 const uint32_t *gal_tables_e1c(void);   /* [50][128] */
