@@ -36,6 +36,9 @@ from .synth import (  # noqa: F401
     mpath_make,
     mpath_rows,
     noise_from_cn0,
+    osc_check,
+    osc_lo_step,
+    osc_make,
     pack_page,
     tables,
     unpack_page,

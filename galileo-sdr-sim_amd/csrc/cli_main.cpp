@@ -30,6 +30,9 @@
 // --agc [target_rms], --iq-format i2bit (not in the reference): a block AGC in front of the quantiser, behind everything above, and the
 // 2-bit format it makes possible (gal_synth_iq_agc); --agc-log <file> writes the gain of every block.
 //
+// --lo-offset hz[,drift_hz_per_s], --phase-noise h0 (not in the reference): the receiver's local oscillator -- a carrier offset, a drift and
+// white-FM phase noise common to the whole stream, behind gains, --multipath, --cn0 and --jam and in front of --fir / the decimator, --agc
+// and the format (gal_synth_iq_osc); the file does not depend on -B.
 // --monitor <file> (not in the reference): the built-in receiver check -- every --monitor-every'th epoch (default 10) the first 25 code
 // periods of every active channel are despread, in the buffer as it is written (behind noise and format), with the planned replica
 // (gal_synth_correlate); one CSV line per (epoch, PRN) with the measured C/N0 and where the peak lies.  Read-only: the IQ is the same.
@@ -150,6 +153,14 @@ void usage(const char *prog)
            "                   with neither: a low-pass at 1.17 MHz with 32 M + 1 taps (printed on stderr).  The automatic --iq-shift\n"
            "                   uses the sigma behind the filter, sigma x sqrt(sum h^2) / 16384.  --monitor needs taps whose\n"
            "                   (n_taps - 1) is a multiple of 2 M (a delay of whole output samples).  Default -B: max(8, 128 / M)\n"
+           "  --lo-offset <hz>[,<drift_hz_per_s>] Receiver oscillator: rotate the whole stream -- satellites, echoes, --jam sources and noise --\n"
+           "                   by a carrier offset and a linear drift, behind --cn0 / --jam and in front of --fir / the decimator, --agc and\n"
+           "                   the format (with --oversample at the high rate).  --monitor follows the offset and the drift.  The sample\n"
+           "                   clock stays ideal: the code rate is not scaled by the same ppm (a few 1e-6 of it at a TCXO's offset).\n"
+           "  --phase-noise <h0> the same oscillator with white-FM phase noise of the one-sided fractional-frequency PSD h0 in seconds\n"
+           "                   (1e-21: a good TCXO); the per-sample sigma, the rms phase over 1 and 4 ms and the linewidth are printed\n"
+           "  --osc-seed <N>   with --phase-noise: the seed of the phase noise (unsigned 64-bit, default 1)\n"
+           "  --osc-stream <N> with --phase-noise: its stream (unsigned 32-bit, default 0; --sites gives site i the stream i)\n"
            "  --monitor <file> Despread the output with the planned replicas and write one CSV line per monitored epoch and PRN:\n"
            "                   time, PRN, planned Doppler, measured C/N0 (composite E1B + E1C), peak ratio, strongest of the delays\n"
            "                   -1 / 0 / +1 half chip and of the Doppler offsets -1 / 0 / +1 bin of 250 Hz; a summary per PRN on stderr\n"
@@ -506,7 +517,7 @@ struct Site {
 };
 
 int run_sites(const char *self, const std::vector<std::string> &base_args, const char *sites_file, const char *out_stem,
-              int n_gpus, int per_gpu, int udp_base, const char *fmt_name, double bytes_per_sample, bool noise_on, const char *monitor_file)
+              int n_gpus, int per_gpu, int udp_base, const char *fmt_name, double bytes_per_sample, bool noise_on, bool osc_on, const char *monitor_file)
 {
     std::vector<Site> sites;
     FILE *fp = fopen(sites_file, "r");
@@ -577,6 +588,10 @@ int run_sites(const char *self, const std::vector<std::string> &base_args, const
             args.push_back(std::to_string(udp_base > 0 ? udp_base + (int)next : 0));
             if (noise_on) {  // site i: noise stream i -- two sites never share their noise
                 args.push_back("--noise-stream");
+                args.push_back(std::to_string(next));
+            }
+            if (osc_on) {  // ... nor their oscillator's phase noise
+                args.push_back("--osc-stream");
                 args.push_back(std::to_string(next));
             }
             if (monitor_file) {  // site i: <file>.site<i>
@@ -746,12 +761,13 @@ int main(int argc, char *argv[])
     std::vector<const char *> prn_power_args;
     const char *cn0_arg = nullptr, *noise_seed_arg = nullptr, *noise_stream_arg = nullptr, *signal_gain_arg = nullptr;
     std::vector<const char *> jam_args;
+    const char *lo_offset_arg = nullptr, *phase_noise_arg = nullptr, *osc_seed_arg = nullptr, *osc_stream_arg = nullptr;
     sc.udp_port = GAL_SCEN_UDP_PORT;  // the reference always listens for position updates (src/galileo-sdr.cpp:185)
     sc.udp_loopback = 1;              // ... on every interface; the default listener here takes local datagrams only
 
     enum { OPT_STRICT = 1000, OPT_SITES, OPT_WRITERS, OPT_GPUS, OPT_PER_GPU, OPT_EXACT, OPT_SHIFT_TOE, OPT_REF_T, OPT_IQ_FORMAT, OPT_IQ_SHIFT, OPT_CN0, OPT_NOISE_SEED,
            OPT_NOISE_STREAM, OPT_SIGNAL_GAIN, OPT_MONITOR, OPT_MONITOR_EVERY, OPT_JAM, OPT_POWER_MODEL, OPT_ANTENNA, OPT_PRN_POWER, OPT_FIR, OPT_FIR_LOWPASS, OPT_OVERSAMPLE,
-           OPT_AGC, OPT_AGC_BLOCK, OPT_AGC_WINDOW, OPT_AGC_INIT, OPT_AGC_LOG, OPT_I2BIT_THR, OPT_MULTIPATH };
+           OPT_AGC, OPT_AGC_BLOCK, OPT_AGC_WINDOW, OPT_AGC_INIT, OPT_AGC_LOG, OPT_I2BIT_THR, OPT_MULTIPATH, OPT_LO_OFFSET, OPT_PHASE_NOISE, OPT_OSC_SEED, OPT_OSC_STREAM };
     static const struct option long_opts[] = {{"strict", no_argument, nullptr, OPT_STRICT},
                                               {"exact-replay", no_argument, nullptr, OPT_EXACT},
                                               {"shift-toe", no_argument, nullptr, OPT_SHIFT_TOE},
@@ -782,6 +798,10 @@ int main(int argc, char *argv[])
                                               {"agc-log", required_argument, nullptr, OPT_AGC_LOG},
                                               {"i2bit-threshold", required_argument, nullptr, OPT_I2BIT_THR},
                                               {"multipath", required_argument, nullptr, OPT_MULTIPATH},
+                                              {"lo-offset", required_argument, nullptr, OPT_LO_OFFSET},
+                                              {"phase-noise", required_argument, nullptr, OPT_PHASE_NOISE},
+                                              {"osc-seed", required_argument, nullptr, OPT_OSC_SEED},
+                                              {"osc-stream", required_argument, nullptr, OPT_OSC_STREAM},
                                               {nullptr, 0, nullptr, 0}};
     std::vector<std::string> child_args;  // --sites: everything but -l / -o / --sites / --gpus / --per-gpu / --noise-stream goes to the children
     int opt;
@@ -789,14 +809,15 @@ int main(int argc, char *argv[])
         // `--agc 4096`: getopt takes an optional argument only as --agc=4096; a following word that begins like a number is the target
         if (opt == OPT_AGC && !optarg && optind < argc && ((argv[optind][0] >= '0' && argv[optind][0] <= '9') || argv[optind][0] == '.'))
             optarg = argv[optind++];
-        if (opt != 'l' && opt != 'o' && opt != 'P' && opt != OPT_SITES && opt != OPT_GPUS && opt != OPT_PER_GPU && opt != OPT_NOISE_STREAM && opt != OPT_MONITOR && opt != OPT_AGC_LOG && opt != '?' && opt != ':') {
+        if (opt != 'l' && opt != 'o' && opt != 'P' && opt != OPT_SITES && opt != OPT_GPUS && opt != OPT_PER_GPU && opt != OPT_NOISE_STREAM && opt != OPT_OSC_STREAM && opt != OPT_MONITOR && opt != OPT_AGC_LOG && opt != '?' && opt != ':') {
             if (opt >= 1000) {
                 child_args.push_back(opt == OPT_STRICT ? "--strict" : opt == OPT_EXACT ? "--exact-replay" : opt == OPT_SHIFT_TOE ? "--shift-toe" : opt == OPT_REF_T ? "--ref-T"
                                      : opt == OPT_IQ_FORMAT ? "--iq-format" : opt == OPT_IQ_SHIFT ? "--iq-shift" : opt == OPT_CN0 ? "--cn0"
                                      : opt == OPT_NOISE_SEED ? "--noise-seed" : opt == OPT_SIGNAL_GAIN ? "--signal-gain" : opt == OPT_MONITOR_EVERY ? "--monitor-every" : opt == OPT_JAM ? "--jam" : opt == OPT_POWER_MODEL ? "--power-model"
                                      : opt == OPT_ANTENNA ? "--antenna" : opt == OPT_PRN_POWER ? "--prn-power" : opt == OPT_FIR ? "--fir" : opt == OPT_FIR_LOWPASS ? "--fir-lowpass" : opt == OPT_OVERSAMPLE ? "--oversample"
                                      : opt == OPT_AGC ? "--agc" : opt == OPT_AGC_BLOCK ? "--agc-block" : opt == OPT_AGC_WINDOW ? "--agc-window" : opt == OPT_AGC_INIT ? "--agc-init-rms"
-                                     : opt == OPT_I2BIT_THR ? "--i2bit-threshold" : opt == OPT_MULTIPATH ? "--multipath" : "--writers");
+                                     : opt == OPT_I2BIT_THR ? "--i2bit-threshold" : opt == OPT_MULTIPATH ? "--multipath" : opt == OPT_LO_OFFSET ? "--lo-offset"
+                                     : opt == OPT_PHASE_NOISE ? "--phase-noise" : opt == OPT_OSC_SEED ? "--osc-seed" : "--writers");
             } else {
                 char name[3] = {'-', (char)opt, 0};
                 child_args.push_back(name);
@@ -853,6 +874,10 @@ int main(int argc, char *argv[])
         case OPT_CN0: cn0_arg = optarg; break;
         case OPT_NOISE_SEED: noise_seed_arg = optarg; break;
         case OPT_NOISE_STREAM: noise_stream_arg = optarg; break;
+        case OPT_LO_OFFSET: lo_offset_arg = optarg; break;
+        case OPT_PHASE_NOISE: phase_noise_arg = optarg; break;
+        case OPT_OSC_SEED: osc_seed_arg = optarg; break;
+        case OPT_OSC_STREAM: osc_stream_arg = optarg; break;
         case OPT_SIGNAL_GAIN: signal_gain_arg = optarg; break;
         case OPT_MONITOR: monitor_arg = optarg; break;
         case OPT_MONITOR_EVERY: monitor_every_arg = optarg; break;
@@ -1377,6 +1402,76 @@ int main(int argc, char *argv[])
             }
         }
     }
+    // receiver oscillator: checked here too, before any device work.  Without --lo-offset / --phase-noise nothing below differs from a
+    // build without them.
+    gal_iq_osc_t osc;
+    memset(&osc, 0, sizeof(osc));
+    const bool osc_on = lo_offset_arg || phase_noise_arg;
+    if (!osc_on && (osc_seed_arg || osc_stream_arg)) {
+        fprintf(stderr, "ERROR: --osc-seed and --osc-stream need --lo-offset or --phase-noise.\n");
+        exit(1);
+    }
+    if (osc_on) {
+        double lo_hz = 0.0, lo_drift = 0.0, lo_h0 = 0.0;
+        if (lo_offset_arg) {
+            char *end = nullptr;
+            lo_hz = strtod(lo_offset_arg, &end);
+            bool ok = *lo_offset_arg && end != lo_offset_arg;
+            if (ok && *end == ',') {
+                const char *d = end + 1;
+                lo_drift = strtod(d, &end);
+                ok = *d && end != d;
+            }
+            if (!ok || *end) {
+                fprintf(stderr, "ERROR: --lo-offset '%s' is not hz[,drift_hz_per_s].\n", lo_offset_arg);
+                exit(1);
+            }
+        }
+        if (phase_noise_arg) {
+            char *end = nullptr;
+            lo_h0 = strtod(phase_noise_arg, &end);
+            if (!*phase_noise_arg || end == phase_noise_arg || *end) {
+                fprintf(stderr, "ERROR: --phase-noise '%s' is not a number (h0 in seconds, e.g. 1e-21).\n", phase_noise_arg);
+                exit(1);
+            }
+        }
+        // the oscillator sits in front of the decimator: with --oversample M it runs at M x 2.6 MS/s
+        if (gal_synth_osc_make(lo_hz, lo_drift, lo_h0, kSampleRate, 1575.42e6, &osc) != GAL_OK) {
+            fprintf(stderr, "ERROR: --lo-offset / --phase-noise: %s\n", gal_synth_last_error());
+            exit(1);
+        }
+        if (osc_seed_arg) {
+            char *end = nullptr;
+            errno = 0;
+            osc.seed = strtoull(osc_seed_arg, &end, 0);
+            if (!*osc_seed_arg || *end || errno || osc_seed_arg[0] == '-') {
+                fprintf(stderr, "ERROR: --osc-seed '%s' is not an unsigned 64-bit integer.\n", osc_seed_arg);
+                exit(1);
+            }
+        }
+        if (osc_stream_arg) {
+            char *end = nullptr;
+            errno = 0;
+            const unsigned long long v = strtoull(osc_stream_arg, &end, 0);
+            if (!*osc_stream_arg || *end || errno || osc_stream_arg[0] == '-' || v > 0xffffffffull) {
+                fprintf(stderr, "ERROR: --osc-stream '%s' is not an unsigned 32-bit integer.\n", osc_stream_arg);
+                exit(1);
+            }
+            osc.stream = (uint32_t)v;
+        }
+        if (!sitesfile[0]) {
+            const double two64 = 18446744073709551616.0, pi = 3.14159265358979323846;
+            const double sig_cyc = 1575.42e6 * sqrt(lo_h0 / (2.0 * kSampleRate)), sig_rad = 2.0 * pi * sig_cyc;
+            fprintf(stderr, "Oscillator: offset %.6f Hz, drift %.6g Hz/s (F = %lld, D = %lld at %g MS/s)", (double)osc.f / two64 * kSampleRate,
+                    (double)osc.d / two64 * kSampleRate * kSampleRate, (long long)osc.f, (long long)osc.d, kSampleRate / 1e6);
+            if (osc.s)
+                fprintf(stderr, "; phase noise h0 %g s: sigma %.4g rad per sample (S = %llu), rms phase %.4g rad over 1 ms, %.4g rad over 4 ms, "
+                                "Lorentzian linewidth %.4g Hz; seed %llu, stream %u",
+                        lo_h0, sig_rad, (unsigned long long)osc.s, sig_rad * sqrt(kSampleRate * 1e-3), sig_rad * sqrt(kSampleRate * 4e-3),
+                        sig_rad * sig_rad * kSampleRate / (2.0 * pi), (unsigned long long)osc.seed, osc.stream);
+            fprintf(stderr, "\n");
+        }
+    }
     // bytes of n samples in the output format: the AGC has its own count (i2bit is a format of the AGC call only)
     const auto out_bytes = [&](size_t n) { return agc_on ? gal_synth_agc_out_bytes(iq_format, n) : gal_synth_iq_bytes(iq_format, n); };
     const double iq_bytes_per_sample = (double)out_bytes(4) / 4.0;
@@ -1388,7 +1483,7 @@ int main(int argc, char *argv[])
         if (n <= 0) snprintf(self, sizeof(self), "%s", argv[0]);
         else self[n] = 0;
         return run_sites(self, child_args, sitesfile, outfile, sites_gpus, sites_per_gpu, udp_given ? sc.udp_port : 0,
-                         kIqNames[iq_format], iq_bytes_per_sample, noise_on, monitor_arg);
+                         kIqNames[iq_format], iq_bytes_per_sample, noise_on, osc_on, monitor_arg);
     }
     if (outfile[0] == 0) {
         printf("[+] File sink not specified. Using galileosim.%s\n", kIqNames[iq_format]);
@@ -1479,6 +1574,10 @@ int main(int argc, char *argv[])
         fprintf(stderr, "ERROR: %s\n", gal_synth_last_error());
         exit(1);
     }
+    if (osc_on && gal_synth_osc_set(eng, &osc, 0) != GAL_OK) {
+        fprintf(stderr, "ERROR: %s\n", gal_synth_last_error());
+        exit(1);
+    }
     if (batch_epochs > total) batch_epochs = total > 0 ? total : 1;
     const size_t batch_bytes = epoch_bytes * batch_epochs;  // in the output format
     // d_iq: the engine's int16 output; d_out: what the copies read -- d_iq itself for ishort (with --cn0: after the noise pass has
@@ -1508,7 +1607,7 @@ int main(int argc, char *argv[])
             fprintf(stderr, "ERROR: buffer allocation failed\n");
             exit(1);
         }
-        if ((iq_format != GAL_IQ_ISHORT || mix_on || power_on || mp_on || fir_on || agc_on) && hipEventCreateWithFlags(&converted[i], hipEventDisableTiming) != hipSuccess) {
+        if ((iq_format != GAL_IQ_ISHORT || mix_on || power_on || mp_on || fir_on || agc_on || osc_on) && hipEventCreateWithFlags(&converted[i], hipEventDisableTiming) != hipSuccess) {
             fprintf(stderr, "ERROR: buffer allocation failed\n");
             exit(1);
         }
@@ -1525,6 +1624,9 @@ int main(int argc, char *argv[])
     mon_shape.dopp_step = (int32_t)llround(kMonBinHz / kOutRate * 4294967296.0);
     mon_shape.dopp0 = -mon_shape.dopp_step;
     mon_shape.n_dopp = 3;
+    // gal_corr_cn0 reads the period length off the shape: the nominal code step (a request's own differs by its code Doppler, a few
+    // 1e-6: 1e-5 dB).  Left at 0 it made every C/N0 of the CSV "nan"
+    mon_shape.code_dph = (uint64_t)llround(2.0 * 1.023e6 / kOutRate * 4294967296.0);
     const size_t mon_epochs_max = (size_t)(batch_epochs + monitor_every - 1) / monitor_every + 1;
     const size_t mon_bytes = mon_epochs_max * sc.n_slots * (kMonNear + kMonFar) * sizeof(long long);
     if (monitor_fp)
@@ -1716,6 +1818,16 @@ int main(int argc, char *argv[])
                     if (rec.prn <= 0) continue;
                     gal_corr_req_t q = mon_shape;
                     if (gal_corr_from_epoch(&rec, kOutRate, skip - fir_delay, &q) != GAL_OK) continue;  // (a record the monitor cannot follow)
+                    if (osc_on) {
+                        // the replica follows the oscillator's offset and drift: its step at the window's first sample -- counted at the
+                        // rate the oscillator runs at, and where the filters' delay puts that sample -- times the M samples of that rate
+                        // in one of the output (the drift inside the window of 0.1 s is not followed: 0.2 Hz at 2 Hz/s)
+                        const int64_t off = ((int64_t)skip - fir_delay) * osr;
+                        const uint64_t n_lo = (uint64_t)(emitted + e) * (uint64_t)cfg.samples_per_epoch + (uint64_t)(off > 0 ? off : 0);
+                        int32_t lo_step = 0;
+                        gal_synth_osc_lo_step(&osc, n_lo, &lo_step);
+                        q.carr_dph = (int32_t)((uint32_t)q.carr_dph + (uint32_t)osr * (uint32_t)lo_step);
+                    }
                     MonEntry me;
                     me.t = (emitted + e) * 0.1;
                     me.f_carr = rec.f_carr;
@@ -1820,6 +1932,7 @@ int main(int argc, char *argv[])
             if (mix_on)
                 crc = gal_synth_iq_convert_interf(eng, d_iq[cur], n_samples, (uint64_t)emitted * (uint64_t)cfg.samples_per_epoch, &noise, interf, n_jam,
                                                   GAL_IQ_ISHORT, 0, d_iq[cur]);
+            if (crc == GAL_OK && osc_on) crc = gal_synth_iq_osc(eng, d_iq[cur], n_samples, d_iq[cur]);  // the mixer: in front of the filter, in place
             if (crc == GAL_OK && dec_on) {
                 size_t got = 0;
                 crc = gal_synth_iq_firdec(eng, d_iq[cur], n_samples, d_fir[cur], &got);
@@ -1846,7 +1959,24 @@ int main(int argc, char *argv[])
             if (mix_on)
                 crc = gal_synth_iq_convert_interf(eng, d_iq[cur], n_samples, (uint64_t)emitted * (uint64_t)cfg.samples_per_epoch, &noise, interf, n_jam,
                                                   GAL_IQ_ISHORT, 0, d_iq[cur]);
+            if (crc == GAL_OK && osc_on) crc = gal_synth_iq_osc(eng, d_iq[cur], n_samples, d_iq[cur]);
             if (crc == GAL_OK) crc = gal_synth_iq_agc(eng, d_iq[cur], n_samples, iq_format, agc_param, d_out[cur], agc_log[cur].dev, &agc_log[cur].n);
+            if (crc != GAL_OK) {
+                fprintf(stderr, "\nERROR: %s\n", gal_synth_last_error());
+                rc = 1;
+                break;
+            }
+        } else if (osc_on) {
+            // the oscillator needs the int16 stream between the noise pass and the format: noise / interference into the int16 batch in
+            // place (as with --fir), the oscillator in place behind it, the plain format conversion from there (ishort: the copies read
+            // d_iq[cur] itself); its phase runs on from batch to batch inside the handle
+            const size_t n_samples = (size_t)n * cfg.samples_per_epoch;
+            int crc = GAL_OK;
+            if (mix_on)
+                crc = gal_synth_iq_convert_interf(eng, d_iq[cur], n_samples, (uint64_t)emitted * (uint64_t)cfg.samples_per_epoch, &noise, interf, n_jam,
+                                                  GAL_IQ_ISHORT, 0, d_iq[cur]);
+            if (crc == GAL_OK) crc = gal_synth_iq_osc(eng, d_iq[cur], n_samples, d_iq[cur]);
+            if (crc == GAL_OK && iq_format != GAL_IQ_ISHORT) crc = gal_synth_iq_convert(eng, d_iq[cur], n_samples, iq_format, iq_shift, d_out[cur]);
             if (crc != GAL_OK) {
                 fprintf(stderr, "\nERROR: %s\n", gal_synth_last_error());
                 rc = 1;
@@ -1874,7 +2004,7 @@ int main(int argc, char *argv[])
             }
             agc_log[cur].pending = true;
         }
-        if (iq_format != GAL_IQ_ISHORT || mix_on || power_on || mp_on || fir_on || agc_on) {  // what the copies read is enqueued on the engine's stream: they wait for it
+        if (iq_format != GAL_IQ_ISHORT || mix_on || power_on || mp_on || fir_on || agc_on || osc_on) {  // what the copies read is enqueued on the engine's stream: they wait for it
             if (hipEventRecord(converted[cur], stream) != hipSuccess || hipStreamWaitEvent(copy_stream[0], converted[cur], 0) != hipSuccess ||
                 hipStreamWaitEvent(copy_stream[1], converted[cur], 0) != hipSuccess) {
                 fprintf(stderr, "\nERROR: event after the IQ conversion failed\n");
@@ -2001,7 +2131,7 @@ int main(int argc, char *argv[])
                 fprintf(stderr, "  PRN %2d: gain %5d .. %5d  (%+.2f .. %+.2f dB)\n", prn, prn_gain_lo[prn], prn_gain_hi[prn],
                         prn_gain_lo[prn] > 0 ? 20.0 * log10(prn_gain_lo[prn] / 128.0) : -INFINITY, prn_gain_hi[prn] > 0 ? 20.0 * log10(prn_gain_hi[prn] / 128.0) : -INFINITY);
     }
-    if (iq_format == GAL_IQ_IBYTE || mix_on || power_on || mp_on || fir_on || agc_on) {
+    if (iq_format == GAL_IQ_IBYTE || mix_on || power_on || mp_on || fir_on || agc_on || osc_on) {
         // (stderr: with -o - the data go to stdout)
         uint64_t n_sat = 0;
         const double n_val = (double)emitted * cfg.samples_per_epoch * 2;

@@ -103,6 +103,9 @@ hipError_t galk_launch_iq_agc(const int16_t *in, uint64_t n, uint32_t off0, int 
                               const unsigned long long *state_in, unsigned long long *state_out, void *scratch, void *out, uint32_t *gains_out,
                               unsigned long long *sat, hipStream_t st);
 uint64_t galk_agc_scratch_bytes(uint64_t n, uint32_t off0, uint32_t block_len);
+hipError_t galk_launch_iq_osc(const int16_t *in, int16_t *out, uint64_t n, uint64_t first_sample, uint64_t n0, const gal_iq_osc_t *p,
+                              const long long *state_in, long long *state_out, void *scratch, unsigned long long *sat, hipStream_t st);
+uint64_t galk_osc_scratch_bytes(uint64_t n);
 hipError_t galk_launch_iq_echo(const int16_t *const *parts_dev, const int16_t *const *hist_in_dev, int16_t *const *hist_out_dev, const int *gain_dev,
                                const void *rows_dev, const int *part_of_dev, int n_parts, int n_echo, int n_epochs, int samples_per_epoch, int wide,
                                int16_t *out, unsigned long long *sat, hipStream_t st);
@@ -386,6 +389,18 @@ struct gal_synth {
     int agc_cur = 0;
     hipEvent_t ev_agc = nullptr;
     bool agc_pending = false;
+    // gal_synth_osc_set / gal_synth_iq_osc (iq_osc.hip): d_osc = the two 64-bit words of the running sum Z (a call with s > 0 reads
+    // osc_cur and writes the other); d_osc_scr = the tile sums and their scan of the last call, grown on demand; osc_n0 = N0, osc_pos =
+    // the global index of the next sample; ev_osc = the last oscillator kernel of the handle is done
+    long long *d_osc = nullptr;
+    void *d_osc_scr = nullptr;
+    size_t osc_scr_bytes = 0;
+    gal_iq_osc_t osc = {};
+    bool osc_on = false;
+    uint64_t osc_n0 = 0, osc_pos = 0;
+    int osc_cur = 0;
+    hipEvent_t ev_osc = nullptr;
+    bool osc_pending = false;
 };
 
 // The stream the handle works on: the caller's (gal_synth_set_stream), or one of its own, made at first need.
@@ -632,6 +647,9 @@ int gal_synth_destroy(gal_synth_t *h)
     if (h->h_agc) hipHostFree(h->h_agc);
     if (h->d_agc_scr) hipFree(h->d_agc_scr);
     if (h->ev_agc) hipEventDestroy(h->ev_agc);
+    if (h->d_osc) hipFree(h->d_osc);
+    if (h->d_osc_scr) hipFree(h->d_osc_scr);
+    if (h->ev_osc) hipEventDestroy(h->ev_osc);
     if (h->d_lut) hipFree(h->d_lut);
     if (h->d_str) hipFree(h->d_str);
     if (h->h_up) hipHostFree(h->h_up);
@@ -2680,6 +2698,166 @@ int gal_synth_iq_agc(gal_synth_t *h, const int16_t *in_dev, size_t n_samples, in
     HIP_TRY(hipEventRecord(h->ev_agc, st));
     h->agc_pending = true;
     if (n_gains) *n_gains = (size_t)ng;
+    return GAL_OK;
+}
+
+// ---- receiver oscillator (iq_osc.hip) ----------------------------------------------------------------------------------------------
+static constexpr uint64_t kOscMaxS = 1ull << 48;
+
+int gal_synth_osc_check(const gal_iq_osc_t *o)
+{
+    const char *who = "gal_synth_osc_check";
+    if (!o) return fail(GAL_E_INVAL, "%s: null argument", who);
+    if (o->reserved != 0) return fail(GAL_E_INVAL, "%s: reserved %u (0)", who, o->reserved);
+    if (o->s > kOscMaxS) return fail(GAL_E_INVAL, "%s: s %llu is more than 2^48", who, (unsigned long long)o->s);
+    return GAL_OK;
+}
+
+// M2 = the sum of mag(w)^2 over the 2^31 words w of the Gauss table's input (exact: below 2^31 x 2^30): per octave the 13 bits under
+// the leading one choose the cell and the fraction, every (cell, fraction) 2^(low - 13) times where the octave has low >= 13 bits
+// under its leading one, else only those whose missing low bits are 0, once
+static uint64_t gauss_m2()
+{
+    const int32_t(*T)[32][2] = (const int32_t(*)[32][2])gal_tables_gauss();
+    uint64_t m2 = 0;
+    for (int o = 0; o < 31; ++o) {
+        const int low = 30 - o, step = low >= 13 ? 1 : 1 << (13 - low);
+        uint64_t acc = 0;
+        for (int sf = 0; sf < 8192; sf += step) {
+            const int64_t a = T[o][sf >> 8][0], b = T[o][sf >> 8][1], mag = a - (((a - b) * (sf & 255) + 128) >> 8);
+            acc += (uint64_t)(mag * mag);
+        }
+        m2 += low >= 13 ? acc << (low - 13) : acc;
+    }
+    const int64_t m0 = T[31][0][0];  // w = 0
+    return m2 + (uint64_t)(m0 * m0);
+}
+
+int gal_synth_osc_make(double f_hz, double drift_hz_s, double h0, double sample_rate, double carrier_hz, gal_iq_osc_t *out)
+{
+    const char *who = "gal_synth_osc_make";
+    if (!out) return fail(GAL_E_INVAL, "%s: null argument", who);
+    if (!std::isfinite(f_hz) || !std::isfinite(drift_hz_s) || !std::isfinite(h0) || !std::isfinite(sample_rate) || !std::isfinite(carrier_hz))
+        return fail(GAL_E_INVAL, "%s: an argument is not finite", who);
+    if (!(sample_rate > 0.0) || carrier_hz < 0.0 || h0 < 0.0)
+        return fail(GAL_E_INVAL, "%s: sample rate %g (> 0), carrier %g Hz (>= 0), h0 %g s (>= 0)", who, sample_rate, carrier_hz, h0);
+    if (!(fabs(f_hz) < sample_rate / 2)) return fail(GAL_E_INVAL, "%s: offset %g Hz must lie inside +-sample_rate / 2 = %g Hz", who, f_hz, sample_rate / 2);
+    const double two64 = 18446744073709551616.0, two63 = 9223372036854775808.0;
+    const double fv = f_hz / sample_rate * two64, dv = drift_hz_s / sample_rate / sample_rate * two64;
+    if (!(fabs(fv) < two63)) return fail(GAL_E_INVAL, "%s: offset %g Hz must lie inside +-sample_rate / 2 = %g Hz", who, f_hz, sample_rate / 2);
+    if (!(fabs(dv) < two63))
+        return fail(GAL_E_INVAL, "%s: drift %g Hz/s does not fit (|drift| < sample_rate^2 / 2 = %g Hz/s)", who, drift_hz_s, sample_rate * sample_rate / 2);
+    const double v = (double)gauss_m2() / 36028797018963968.0;  // 2^55 = 2^31 words x 4096^2
+    const double sigma_cycles = carrier_hz * sqrt(h0 / (2.0 * sample_rate));
+    const double sv = sigma_cycles / sqrt(v) * 4503599627370496.0;  // 2^52
+    if (!(sv <= (double)kOscMaxS)) return fail(GAL_E_INVAL, "%s: the phase noise of h0 %g s needs s = %g, more than 2^48", who, h0, sv);
+    gal_iq_osc_t o;
+    memset(&o, 0, sizeof(o));
+    o.seed = 1;
+    o.f = (int64_t)llround(fv);
+    o.d = (int64_t)llround(dv);
+    o.s = (uint64_t)llround(sv);
+    *out = o;
+    return GAL_OK;
+}
+
+int gal_synth_osc_lo_step(const gal_iq_osc_t *osc, uint64_t N, int32_t *carr_dph)
+{
+    if (!osc || !carr_dph) return fail(GAL_E_INVAL, "gal_synth_osc_lo_step: null argument");
+    *carr_dph = (int32_t)(uint32_t)(((uint64_t)osc->f + N * (uint64_t)osc->d) >> 32);
+    return GAL_OK;
+}
+
+int gal_synth_osc_set(gal_synth_t *h, const gal_iq_osc_t *osc, uint64_t first_sample)
+{
+    const char *who = "gal_synth_osc_set";
+    if (!h) return fail(GAL_E_INVAL, "null handle");
+    gal_iq_osc_t o;
+    if (osc) {
+        o = *osc;  // the caller's struct is not looked at again
+        const int rc = gal_synth_osc_check(&o);
+        if (rc) return rc;
+        if (first_sample >> 62) return fail(GAL_E_INVAL, "%s: first_sample must be below 2^62", who);
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->osc_pending) {  // the state and the scratch belong to the kernels in flight
+        HIP_TRY(hipEventSynchronize(h->ev_osc));
+        h->osc_pending = false;
+    }
+    if (!osc) {
+        if (h->d_osc) hipFree(h->d_osc);
+        if (h->d_osc_scr) hipFree(h->d_osc_scr);
+        h->d_osc = nullptr;
+        h->d_osc_scr = nullptr;
+        h->osc_scr_bytes = 0;
+        h->osc_on = false;
+        return GAL_OK;
+    }
+    hipStream_t st = handle_stream(h);
+    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
+    if (!h->ev_osc) HIP_TRY(hipEventCreateWithFlags(&h->ev_osc, hipEventDisableTiming));
+    if (!h->d_osc && hipMalloc((void **)&h->d_osc, 2 * sizeof(long long)) != hipSuccess) {
+        h->d_osc = nullptr;
+        (void)hipGetLastError();
+        return fail(GAL_E_NOMEM, "%s: the state of 16 bytes could not be allocated", who);
+    }
+    // from here on the oscillator in force is gone: a failure leaves the handle without one
+    h->osc_on = false;
+    HIP_TRY(hipMemsetAsync(h->d_osc, 0, 2 * sizeof(long long), st));
+    HIP_TRY(hipEventRecord(h->ev_osc, st));
+    h->osc_pending = true;
+    h->osc = o;
+    h->osc_n0 = h->osc_pos = first_sample;
+    h->osc_cur = 0;
+    h->osc_on = true;
+    return GAL_OK;
+}
+
+int gal_synth_iq_osc(gal_synth_t *h, const int16_t *in_dev, size_t n_samples, int16_t *out_dev)
+{
+    const char *who = "gal_synth_iq_osc";
+    if (!h) return fail(GAL_E_INVAL, "null handle");
+    if (!in_dev || !out_dev || ((uintptr_t)in_dev & 15) || ((uintptr_t)out_dev & 15))
+        return fail(GAL_E_INVAL, "%s: device pointers must be non-null and 16-byte aligned", who);
+    if ((uint64_t)n_samples >> 41) return fail(GAL_E_INVAL, "%s: n_samples must be below 2^41", who);
+    if (!h->osc_on) return fail(GAL_E_STATE, "%s: no oscillator set (call gal_synth_osc_set first)", who);
+    if (n_samples == 0) return GAL_OK;
+    const size_t bytes = 4 * n_samples;
+    const char *x = (const char *)in_dev, *o = (const char *)out_dev;
+    if (x != o && x < o + bytes && o < x + bytes) return fail(GAL_E_INVAL, "%s: input and output overlap (only exactly in place may)", who);
+    if (hits_batch_in_flight(h, in_dev, bytes)) return fail(GAL_E_STATE, "%s: input of the batch in flight (call gal_synth_finish first)", who);
+    if (hits_batch_in_flight(h, out_dev, bytes)) return fail(GAL_E_STATE, "%s: output of the batch in flight (call gal_synth_finish first)", who);
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = handle_stream(h);
+    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
+    const int rc = ensure_sat_counter(h, st);
+    if (rc) return rc;
+    const bool noise = h->osc.s != 0;
+    // the scratch of this call: one per handle, grown when a call is longer than any before it (only then the host waits for the
+    // kernels of the call before)
+    const uint64_t need = noise ? galk_osc_scratch_bytes((uint64_t)n_samples) : 0;
+    if (need > h->osc_scr_bytes) {
+        if (h->osc_pending) {
+            HIP_TRY(hipEventSynchronize(h->ev_osc));
+            h->osc_pending = false;
+        }
+        if (h->d_osc_scr) hipFree(h->d_osc_scr);
+        h->d_osc_scr = nullptr;
+        h->osc_scr_bytes = 0;
+        const uint64_t cap = need + need / 4 + 256;
+        if (cap != (uint64_t)(size_t)cap || hipMalloc(&h->d_osc_scr, (size_t)cap) != hipSuccess) {
+            h->d_osc_scr = nullptr;
+            (void)hipGetLastError();
+            return fail(GAL_E_NOMEM, "%s: the scratch of %llu bytes (12 per tile of 1024 samples) could not be allocated", who, (unsigned long long)cap);
+        }
+        h->osc_scr_bytes = (size_t)cap;
+    }
+    HIP_TRY(galk_launch_iq_osc(in_dev, out_dev, (uint64_t)n_samples, h->osc_pos, h->osc_n0, &h->osc, h->d_osc + h->osc_cur, h->d_osc + (h->osc_cur ^ 1),
+                               h->d_osc_scr, h->d_iq_sat, st));
+    if (noise) h->osc_cur ^= 1;
+    h->osc_pos += (uint64_t)n_samples;
+    HIP_TRY(hipEventRecord(h->ev_osc, st));
+    h->osc_pending = true;
     return GAL_OK;
 }
 

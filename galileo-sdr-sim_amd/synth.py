@@ -152,6 +152,23 @@ AGC_FIELDS = ("block_len", "window", "target_q8", "gain_min_q12", "gain_max_q12"
 assert ctypes.sizeof(_Agc) == 32
 
 
+class _Osc(ctypes.Structure):  # gal_iq_osc_t (48 bytes)
+    _fields_ = [
+        ("seed", ctypes.c_uint64),
+        ("stream", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("p0", ctypes.c_uint64),
+        ("f", ctypes.c_int64),
+        ("d", ctypes.c_int64),
+        ("s", ctypes.c_uint64),
+    ]
+
+
+OSC_FIELDS = ("seed", "stream", "p0", "f", "d", "s")
+assert ctypes.sizeof(_Osc) == 48
+GAL_OSC_MAX_S = 1 << 48
+
+
 class _Echo(ctypes.Structure):  # gal_iq_echo_t (16 bytes)
     _fields_ = [
         ("gain_q7", ctypes.c_uint16),
@@ -258,6 +275,11 @@ EXPORTED_SYMBOLS = (
     "gal_synth_agc_from_rms",
     "gal_synth_agc_set",
     "gal_synth_iq_agc",
+    "gal_synth_osc_check",
+    "gal_synth_osc_make",
+    "gal_synth_osc_set",
+    "gal_synth_iq_osc",
+    "gal_synth_osc_lo_step",
     "gal_synth_corr_out_bytes",
     "gal_synth_correlate",
     "gal_tables_e1b",
@@ -376,6 +398,16 @@ def load_library(hooks=False):
     lib.gal_synth_agc_set.restype = ctypes.c_int
     lib.gal_synth_iq_agc.argtypes = [vp, vp, ctypes.c_size_t, i32, i32, vp, vp, ctypes.POINTER(ctypes.c_size_t)]
     lib.gal_synth_iq_agc.restype = ctypes.c_int
+    lib.gal_synth_osc_check.argtypes = [ctypes.POINTER(_Osc)]
+    lib.gal_synth_osc_check.restype = ctypes.c_int
+    lib.gal_synth_osc_make.argtypes = [ctypes.c_double] * 5 + [ctypes.POINTER(_Osc)]
+    lib.gal_synth_osc_make.restype = ctypes.c_int
+    lib.gal_synth_osc_set.argtypes = [vp, ctypes.POINTER(_Osc), ctypes.c_uint64]
+    lib.gal_synth_osc_set.restype = ctypes.c_int
+    lib.gal_synth_iq_osc.argtypes = [vp, vp, ctypes.c_size_t, vp]
+    lib.gal_synth_iq_osc.restype = ctypes.c_int
+    lib.gal_synth_osc_lo_step.argtypes = [ctypes.POINTER(_Osc), ctypes.c_uint64, ctypes.POINTER(i32)]
+    lib.gal_synth_osc_lo_step.restype = ctypes.c_int
     lib.gal_synth_corr_out_bytes.argtypes = [ctypes.POINTER(_CorrReq)]
     lib.gal_synth_corr_out_bytes.restype = ctypes.c_size_t
     lib.gal_synth_correlate.argtypes = [vp, vp, i32, ctypes.c_size_t, ctypes.POINTER(_CorrReq), i32, vp]
@@ -590,6 +622,55 @@ def agc_blocks(first_sample, n_samples, block_len):
     """gal_synth_agc_blocks (no GPU needed): the blocks whose first sample lies in a call of n_samples that begins at the global index
     first_sample -- the number of b with first_sample <= b block_len < first_sample + n_samples."""
     return int(load_library().gal_synth_agc_blocks(int(first_sample), int(n_samples), int(block_len)))
+
+
+def _osc_struct(osc):
+    """dict with the fields of gal_iq_osc_t but `reserved` (all optional: seed defaults to 1, the others to 0), or an _Osc."""
+    if isinstance(osc, _Osc):
+        return osc
+    unknown = set(osc) - set(OSC_FIELDS)
+    if unknown:
+        raise ValueError("osc: unknown keys %s" % sorted(unknown))
+    d = {"seed": 1, "stream": 0, "p0": 0, "f": 0, "d": 0, "s": 0}
+    d.update(osc)
+    for k in OSC_FIELDS:
+        lo, hi = (-(1 << 63), 1 << 63) if k in ("f", "d") else (0, 1 << 32) if k == "stream" else (0, 1 << 64)
+        if not lo <= int(d[k]) < hi:
+            raise ValueError("osc: %s = %r does not fit its field" % (k, d[k]))
+    return _Osc(int(d["seed"]), int(d["stream"]), 0, int(d["p0"]), int(d["f"]), int(d["d"]), int(d["s"]))
+
+
+def osc_check(osc):
+    """gal_synth_osc_check (no GPU needed): raises GalSynthError unless the oscillator parameters are admitted (s <= 2^48)."""
+    lib = load_library()
+    o = _osc_struct(osc)
+    rc = lib.gal_synth_osc_check(ctypes.byref(o))
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+
+
+def osc_make(f_hz=0.0, drift_hz_s=0.0, h0=0.0, sample_rate=2.6e6, carrier_hz=1575.42e6):
+    """gal_synth_osc_make (no GPU needed): the `osc` dict of SynthEngine.osc_set for a carrier offset f_hz, a drift in Hz/s and white-FM
+    phase noise of the one-sided fractional-frequency PSD h0 (s) at carrier_hz -- f = llround(f_hz / fs 2^64), d = llround(drift / fs^2
+    2^64), s = llround(carrier_hz sqrt(h0 / (2 fs)) / sqrt(var z) 2^52); seed 1, stream 0, p0 0."""
+    lib = load_library()
+    o = _Osc()
+    rc = lib.gal_synth_osc_make(float(f_hz), float(drift_hz_s), float(h0), float(sample_rate), float(carrier_hz), ctypes.byref(o))
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+    return {k: int(getattr(o, k)) for k in OSC_FIELDS}
+
+
+def osc_lo_step(osc, n):
+    """gal_synth_osc_lo_step (no GPU needed): the oscillator's deterministic phase step at the global sample n in the correlator's
+    units, (F + n D) mod 2^64 >> 32 as an int32 -- add it to a request's carr_dph."""
+    lib = load_library()
+    o = _osc_struct(osc)
+    out = ctypes.c_int32(0)
+    rc = lib.gal_synth_osc_lo_step(ctypes.byref(o), int(n), ctypes.byref(out))
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+    return int(out.value)
 
 
 def _echo_table(echo_rows, n_epochs, who):
@@ -968,6 +1049,22 @@ class SynthEngine:
                                                ctypes.c_void_p(int(out_ptr)), ctypes.c_void_p(int(gains_ptr)) if gains_ptr else None,
                                                ctypes.byref(n_gains)))
         return int(n_gains.value)
+
+    def osc_set(self, osc, first_sample=0):
+        """gal_synth_osc_set: give the handle the receiver oscillator `osc` (a dict with the fields of gal_iq_osc_t; osc_make makes one)
+        and start a stream whose next sample has the global index first_sample (the phase-noise sum Z is 0 there); None switches it
+        off.  Independent of fir_set, firdec_set and agc_set."""
+        if osc is None:
+            self._check(self._lib.gal_synth_osc_set(self._h, None, 0))
+            return
+        o = _osc_struct(osc)
+        self._check(self._lib.gal_synth_osc_set(self._h, ctypes.byref(o), int(first_sample)))
+
+    def iq_osc(self, in_ptr, n_samples, out_ptr):
+        """gal_synth_iq_osc, enqueued on the handle's stream: rotate the next n_samples complex int16 samples of the stream by the
+        oscillator's phase, device address in_ptr -> out_ptr (both 16-byte aligned; the same address or disjoint).  Any cut of a stream
+        into calls gives the same bytes.  iq_saturated() is the fence and counts the clamped samples."""
+        self._check(self._lib.gal_synth_iq_osc(self._h, ctypes.c_void_p(int(in_ptr)), int(n_samples), ctypes.c_void_p(int(out_ptr))))
 
     def run_gains(self, params, gain_q7, iq_dev_ptr, state_in=None):
         """gal_synth_run_gains: the batch with per-slot, per-epoch Q7 gains gain_q7 [n_epochs, n_slots] (128 = unity) into the device

@@ -763,6 +763,68 @@ int gal_synth_mpath_make(double delay_s, double rel_db, double phase_deg, double
  * echo outside the ranges of gal_synth_mpath_make. */
 int gal_synth_mpath_row(const gal_mpath_echo_t *echo, uint16_t slot_gain_q7, uint64_t epoch, int32_t samples_per_epoch, gal_iq_echo_t *row);
 
+/*
+ * Receiver oscillator (not in the reference, whose receiver has a perfect clock): a carrier offset, a linear
+ * drift and white-FM phase noise of the local oscillator, i.e. ONE rotation common to everything that enters the mixer -- all
+ * satellites, their echoes, the interference sources, the noise floor.  A FIXED INTEGER FUNCTION of (parameters, index of the sample
+ * in the whole stream, int16 input): the same bytes on any machine and for any cut of the stream into calls (tests/osc_model.py states
+ * it in numpy).
+ *
+ * x[n] = the complex int16 sample with the global index N = first_sample + n.  All phase arithmetic is modulo 2^64, in units of 2^-64
+ * cycles (wrapping uint64 arithmetic is exact):
+ *   Phi(N) = P0 + N F + T(N) D + S Z(N),   T(N) = N (N - 1) / 2  (halve the even factor first: exact mod 2^64)
+ *   Z(N)   = sum of z(j) for N0 < j <= N,  N0 = the first_sample given to the set call below;  Z(N0) = 0
+ *   z(j)   = the Q12 Gaussian of the noise floor above (same table T, same steps) of word j & 3 of Philox4x32-10 with the counter
+ *            (B & 0xffffffff, B >> 32, stream, 1), B = j >> 2, key = (seed & 0xffffffff, seed >> 32).  Counter word 3 = 1 keeps it
+ *            disjoint from the noise floor, which uses 0
+ *   theta  = Phi >> 32  (uint32, 2^-32 cycles);  t = (theta + 2^21) mod 2^32
+ *   i      = t >> 22  (0 .. 1023);  e = ((t >> 10) & 4095) - 2048  (the residual, 2^-22 cycles, -2048 .. 2047)
+ *   c0 = C[i], s0 = C[(i - 256) & 1023]                                       (C = gal_tables_cos1024(), Q12)
+ *   c  = c0 - ((s0 e 101 + 2^25) >> 26);  s = s0 + ((c0 e 101 + 2^25) >> 26)  (first-order correction; 101 = round(2 pi 2^4);
+ *                                                                               arithmetic shifts)
+ *   yI = clamp((xI c - xQ s + 2048) >> 12, -32768, 32767);  yQ = clamp((xI s + xQ c + 2048) >> 12, -32768, 32767)    (y = x e^{+j theta})
+ * A complex sample counts ONCE as saturated if either clamp changed it.  |s0 e 101| <= 4096 x 2048 x 101 < 2^30, so |c|, |s| <= 4096
+ * + 13 and every product and sum fits an int32 for any int16 input.  F = D = S = P0 = 0 gives c = 4096, s = 0 and y = x bit for bit.
+ * The frequency resolution is sample_rate x 2^-64, the drift resolution sample_rate^2 x 2^-64 (4e-7 Hz/s at 2.6 MS/s); the 12-bit
+ * residual keeps the table's 0.35 degree steps out of the result.  The sample clock stays ideal: the code rate is not scaled.
+ */
+typedef struct gal_iq_osc {
+    uint64_t seed;      /* Philox key of the phase noise                                                                     */
+    uint32_t stream;    /* Philox counter word 2 (the CLI: the site index of --sites)                                         */
+    uint32_t reserved;  /* 0                                                                                                 */
+    uint64_t p0;        /* P0: phase at N = 0, 2^-64 cycles                                                                   */
+    int64_t  f;         /* F: phase step per sample, 2^-64 cycles (the carrier offset / sample_rate x 2^64)                   */
+    int64_t  d;         /* D: change of the step per sample (the drift / sample_rate^2 x 2^64)                                */
+    uint64_t s;         /* S <= 2^48: the phase-noise increment of a sample is S z 2^-64 cycles, sigma = S 2^-52 sqrt(var z) */
+} gal_iq_osc_t;         /* 48 bytes */
+/* GAL_OK if the parameters are admitted, else GAL_E_INVAL: a null pointer, reserved != 0, s > 2^48.  Host only, needs no GPU. */
+int gal_synth_osc_check(const gal_iq_osc_t *osc);
+/* Parameters from physical figures; host only, needs no GPU.  In double, operation for operation, rounding to nearest (llround):
+ *   f = llround(f_hz / sample_rate x 2^64);   d = llround(drift_hz_s / sample_rate / sample_rate x 2^64)
+ *   sigma_cycles = carrier_hz x sqrt(h0 / (2 sample_rate)): white-FM phase noise with the one-sided fractional-frequency PSD h0 (in
+ *        seconds) gives the per-sample phase increment the variance (2 pi carrier_hz)^2 h0 / (2 sample_rate) rad^2
+ *   s = llround(sigma_cycles / sqrt(v) x 2^52), v = the variance of z / 4096^2 taken from the table itself: v = M2 / 2^55 with the
+ *        integer M2 = the sum of z(u)^2 over all 2^32 words u, halved (0.99999...: not assumed to be 1)
+ * seed = 1, stream = 0, p0 = 0, reserved = 0.  GAL_E_INVAL for a null `out`, an argument that is not finite, sample_rate <= 0,
+ * carrier_hz < 0, |f_hz| >= sample_rate / 2, a drift whose d does not fit an int64, h0 < 0, an s above 2^48. */
+int gal_synth_osc_make(double f_hz, double drift_hz_s, double h0, double sample_rate, double carrier_hz, gal_iq_osc_t *out);
+/* Give the handle the oscillator *osc (copied) and start a stream: N0 = first_sample (< 2^62) = the global index of the next sample,
+ * and the running sum Z on the device is zeroed (enqueued on the handle's stream).  osc == NULL switches the oscillator off.
+ * GAL_E_INVAL for a null handle, what the check refuses, first_sample >= 2^62; GAL_E_NOMEM if the state cannot be had. */
+int gal_synth_osc_set(gal_synth_t *h, const gal_iq_osc_t *osc, uint64_t first_sample);
+/* Enqueue on the handle's stream: the next n_samples complex int16 samples of the stream, in_dev -> out_dev (DEVICE memory, 16-byte
+ * aligned, 4 n_samples bytes each).  It may run exactly IN PLACE (out_dev == in_dev); any other overlap is refused.  Calls continue
+ * the stream where the last one ended: ANY CUT OF A STREAM INTO CALLS GIVES THE SAME BYTES AS ONE CALL.  With s > 0 a call is three
+ * launches (tile sums, a scan of them, the rotation) ordered by the stream alone, and the handle keeps a scratch of 12 bytes per 1024
+ * samples of its longest call.  gal_synth_iq_saturated is the fence and the counter.  GAL_E_INVAL for a null handle or pointer, a
+ * misaligned pointer, n_samples >= 2^41, a partial overlap; GAL_E_STATE for a buffer of the batch in flight and where no oscillator is
+ * set; GAL_E_NOMEM if the scratch cannot be had. */
+int gal_synth_iq_osc(gal_synth_t *h, const int16_t *in_dev, size_t n_samples, int16_t *out_dev);
+/* The deterministic step of the oscillator at sample N in the correlator's units, so that a replica can follow it: *carr_dph =
+ * (int32)((F + N D) mod 2^64 >> 32) (2^-32 cycles per sample; add it to gal_corr_req_t.carr_dph).  Host only, needs no GPU.
+ * GAL_E_INVAL for a null pointer. */
+int gal_synth_osc_lo_step(const gal_iq_osc_t *osc, uint64_t N, int32_t *carr_dph);
+
 /* Signal tables as the engine uses them (for tests and for the oracle to share DATA, not code). */
 const uint32_t *gal_tables_e1b(void);   /* [50][128] */
 const uint32_t *gal_tables_e1c(void);   /* [50][128] */
