@@ -20,8 +20,10 @@
 
 #if defined(__HIPCC__)
 #define GAL_HD __host__ __device__ __forceinline__
+#define GAL_HDM __host__ __device__ __forceinline__
 #else
 #define GAL_HD static inline
+#define GAL_HDM inline
 #endif
 
 namespace galnco {
@@ -154,8 +156,16 @@ GAL_HD bool tie_step(double d)
 // (|p| grows towards the wrap), 2^-30 <= |d| -- with everything that depends only on d hoisted out of the
 // loop; other states (a phase still running against a step that changed sign, degenerate steps) take the
 // general nco_batch.  Same results as stepping sample by sample, bit for bit (tests/test_walker_cpu.py).
-template <class Emit>
-GAL_HD WalkOut carr_walk_track(double p, double d, double inv_ad, int N, int R, int cp0, Emit emit)
+// `probe(loop, flags, trips)` is called once per iteration -- loop: 0 general / 1 lean; flags: WALK_PROBE_*; trips: checkpoints the
+// closed form emitted inside the batch.  The product passes none (WalkNoProbe: nothing is generated); the host build counts with it
+// what the lanes of a wave would do side by side (walk_host.cpp: galwalk_lane_profile, tools/walker_lane_profile.py).
+enum { WALK_PROBE_CP_START = 1, WALK_PROBE_NO_BATCH = 2, WALK_PROBE_STEP = 4, WALK_PROBE_WRAP = 8, WALK_PROBE_TIE = 16 };
+struct WalkNoProbe {
+    GAL_HDM void operator()(int, int, int) const {}
+};
+
+template <class Emit, class Probe = WalkNoProbe>
+GAL_HD WalkOut carr_walk_track(double p, double d, double inv_ad, int N, int R, int cp0, Emit emit, Probe probe = Probe())
 {
     // cp0: local index of the first checkpoint (checkpoints at cp0, cp0+R, ...); pass cp0 >= N for none
     int i = 0;
@@ -180,7 +190,9 @@ GAL_HD WalkOut carr_walk_track(double p, double d, double inv_ad, int N, int R, 
         const double q_ = p + d;                                                                     \
         const double t_ = __builtin_trunc(q_);                                                       \
         const bool wrapped_ = t_ != 0.0;                                                             \
+        pf_ |= WALK_PROBE_STEP | (wrapped_ ? WALK_PROBE_WRAP : 0);                                   \
         if (tieprone && wrapped_ && o.tdir == 0) { /* rare: only steps that are multiples of 2^-53 */ \
+            pf_ |= WALK_PROBE_TIE;                                                                   \
             const double bv_ = q_ - p; /* TwoSum: err = (p + d) - q exactly */                       \
             const double err_ = (p - (q_ - bv_)) + (d - bv_);                                        \
             if (err_ == 1.1102230246251565e-16) o.tdir = -1; /* exact sum above q: rounded down */   \
@@ -197,10 +209,12 @@ GAL_HD WalkOut carr_walk_track(double p, double d, double inv_ad, int N, int R, 
     while (i < N) {
         const uint64_t pb = d2u(p);
         if (lean_d && (((uint32_t)(pb >> 63) == dsign) || (pb & ~kSign) == 0)) break;
+        int pf_ = 0, pt_ = 0;  // (probe only)
         if (next_cp == i) {
             emit(c, p);
             ++c;
             next_cp += R;
+            pf_ |= WALK_PROBE_CP_START;
         }
         const Batch b = nco_batch(p, d, N - i, 1.0, inv_ad);
         const double a0 = p;
@@ -210,20 +224,25 @@ GAL_HD WalkOut carr_walk_track(double p, double d, double inv_ad, int N, int R, 
             emit(c, fma_exact((double)(next_cp - i), b.inc, a0));
             ++c;
             next_cp += R;
+            ++pt_;
         }
         p = fma_exact((double)b.n, b.inc, p);
         const double m = binade_margin(a0, p);
         mg = m < mg ? m : mg;
         i += b.n;
+        pf_ |= b.n == 0 ? WALK_PROBE_NO_BATCH : 0;
         if (i < N) GAL_GENUINE_STEP()
+        probe(0, pf_, pt_);
     }
     // ---- lean iterations: |p| only grows until the wrap, which keeps the sign -- the regime is permanent
     const double sd = dsign ? -1.0 : 1.0;
     while (i < N) {
+        int pf_ = 0, pt_ = 0;  // (probe only)
         if (next_cp == i) {
             emit(c, p);
             ++c;
             next_cp += R;
+            pf_ |= WALK_PROBE_CP_START;
         }
         const uint64_t pa = d2u(p) & ~kSign;
         const uint32_t ea = (uint32_t)(pa >> 52);
@@ -254,10 +273,13 @@ GAL_HD WalkOut carr_walk_track(double p, double d, double inv_ad, int N, int R, 
             emit(c, fma_exact((double)(next_cp - i) * sd, dk, p));
             ++c;
             next_cp += R;
+            ++pt_;
         }
         p = fma_exact(nd * sd, dk, p);
         i += n;
+        pf_ |= n == 0 ? WALK_PROBE_NO_BATCH : 0;
         if (i < N) GAL_GENUINE_STEP()
+        probe(1, pf_, pt_);
     }
 #undef GAL_GENUINE_STEP
     const double m = binade_margin(p, p);  // the state handed over

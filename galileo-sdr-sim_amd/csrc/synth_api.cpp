@@ -81,10 +81,12 @@ void galk_launch_repair_g(const DevPlan *P, uint32_t *iq, int e0, hipStream_t st
 void galk_touch(hipStream_t st);
 void galk_launch_walk_code(const DevPlan *P, hipStream_t st);
 void galk_launch_walk_carr(const DevPlan *P, int first, hipStream_t st);
+#ifdef GAL_TEST_HOOKS
+void galk_test_poke(const DevPlan *P, int what, long long idx, unsigned bits, unsigned long long *old_dev, int restore, hipStream_t st);
+#endif
 void galk_launch_carr_scan(const DevPlan *P, uint32_t tag, hipStream_t st);
 size_t galk_scanm_status_bytes(int S, int legs);
-void galk_launch_verify_carr(const DevPlan *P, hipStream_t st);
-void galk_launch_verify_code(const DevPlan *P, hipStream_t st);
+void galk_launch_verify(const DevPlan *P, hipStream_t st);
 void galk_launch_pages(const DevPlan *P, hipStream_t st);
 void galk_launch_publish(const DevPlan *P, int *h_ctr, void *h_state, uint32_t *h_flag, uint32_t seq, hipStream_t st);
 int galk_scanm_blocks(int legs);
@@ -164,7 +166,7 @@ constexpr int kGroupChunk = 1024;   // k_synth_g: samples per wave iteration = c
 constexpr int kGroupSyms = 64;      // ... symbol masks per channel and epoch (SG_SYMS)
 constexpr int kGroupListMin = 1 << 16;  // ... least capacity of the undecided-group list (a 120 s batch lists ~2000 of 19.5 M groups);
                                         // a plan's list holds 0.5 % of its groups + this
-constexpr int kVerifyRotation = 8;  // GAL_CFG_VERIFY_SAMPLED: k_verify_carr / k_verify_code re-walk every eighth leg position per batch (default:
+constexpr int kVerifyRotation = 8;  // GAL_CFG_VERIFY_SAMPLED: k_verify re-walks, of both chains, every eighth leg position per batch (default:
                                     // all of them).  Same box, M-SYN12, pipelined step / one handle / k_synth_g beside it, carrier legs only
                                     // (profiles/r05f_verify_ab.log): none 0.974 / 1.230 / 0.842 ms; every leg 1.010 / 1.297 / 0.890; every 4th
                                     // 0.985 / 1.258 / 0.865; 8th 0.979 / 1.238 / 0.846; 16th 0.976 / 1.234 / 0.845
@@ -272,10 +274,7 @@ struct gal_synth {
     // are first in line then, instead of queueing behind the pending synthesis workgroups of other handles
     hipStream_t walk_stream = nullptr;
     hipEvent_t ev_walk = nullptr;
-    hipEvent_t ev_ver = nullptr;  // k_verify_carr done (k_synth_g batches)
-    hipEvent_t ev_verc = nullptr; // k_verify_code done (k_synth_g batches; second walker stream)
-    hipEvent_t ev_ctr = nullptr;  // the first carrier walk of the batch in flight is done: it resets the batch's counters at its start, and
-                                  // k_verify_code, on the other walker stream, must not count a mismatch in front of that
+    hipEvent_t ev_ver = nullptr;  // k_verify done (k_synth_g batches)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_prep = nullptr, ev_aux = nullptr;
     hipEvent_t ev_upd = nullptr;  // the plan's upload and memsets are complete (what the walkers of its first execute wait for)
@@ -532,8 +531,6 @@ int gal_synth_create(const gal_synth_cfg_t *cfg, gal_synth_t **out)
         hipEventCreateWithFlags(&h->ev_prep, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_upd, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_ver, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_verc, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_ctr, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_aux, hipEventDisableTiming) != hipSuccess)
         return bail(fail(GAL_E_DEVICE, "hipEventCreate failed"));
     // (coherent = fine-grained: k_publish writes both from the device while the host polls the flag behind h_ctr)
@@ -664,8 +661,6 @@ int gal_synth_destroy(gal_synth_t *h)
     if (h->ev_aux) hipEventDestroy(h->ev_aux);
     if (h->ev_walk) hipEventDestroy(h->ev_walk);
     if (h->ev_ver) hipEventDestroy(h->ev_ver);
-    if (h->ev_verc) hipEventDestroy(h->ev_verc);
-    if (h->ev_ctr) hipEventDestroy(h->ev_ctr);
     if (h->walk_stream) hipStreamDestroy(h->walk_stream);
     if (h->aux_stream) hipStreamDestroy(h->aux_stream);
     if (h->own_stream) hipStreamDestroy(h->own_stream);
@@ -1072,7 +1067,7 @@ static int plan_impl(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_e
     // with 8 legs, 0.215 / 0.129 with 32; 128 epochs 0.442 / 0.254 -> 0.295 / 0.182; 256 epochs 0.542 / 0.329 -> 0.400 / 0.300;
     // 512 epochs 0.714 / 0.493 -> 0.622 / 0.477 with 16, 0.626 / 0.512 with 32; 1199 epochs: 16 legs cost the pipelined step
     // 15 % -- profiles/r05s_walk_legs_ab.log, r05c_walk_ab.log).  One-epoch calls (INTEGRATION.md option B): k_walk_carr /
-    // k_verify_carr 124 / 121 -> 38 / 36 us with 32 legs (round 4).
+    // the carrier verifier 124 / 121 -> 38 / 36 us with 32 legs (round 4).
     int legs = E <= 256 ? 32 : E <= 512 ? 16 : 8;
 #ifdef GAL_TEST_HOOKS
     if (const char *env = getenv("GAL_WALK_LEGS")) legs = atoi(env) > 0 ? atoi(env) : legs;
@@ -1348,9 +1343,37 @@ const void *gal_hooks_plan_host_array(const char *name)
     if (!strcmp(name, "form")) return (const void *)(uintptr_t)(1 + P.rw);
     return nullptr;
 }
+
+// Test hook (tests/test_verify_fused.py): after a finished batch, perturb ONE word of the handle's checkpoint arrays (what: 0 cp_p one ulp,
+// 1 cp_x one ulp, 2 cp_ib ^= bits, 3 flip_in ^= 1; idx: element index), run the verifier over every leg of both chains on the batch's
+// own plan, return what it counted, and put the word back.
+extern "C" int gal_synth_test_verify_count(gal_synth *h, int what, long long idx, unsigned bits, int *count)
+{
+    if (!h || !count || !h->executed || h->in_flight) return fail(GAL_E_STATE, "gal_synth_test_verify_count: no finished batch");
+    const long long lim = what == 3 ? (long long)h->P.E * h->P.S : (long long)h->P.E * h->P.S * h->P.CP1;
+    if (what < 0 || what > 3 || idx < 0 || idx >= lim) return fail(GAL_E_INVAL, "gal_synth_test_verify_count: index outside the arrays");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = handle_stream(h);
+    unsigned long long *old = nullptr;
+    HIP_TRY(hipMalloc((void **)&old, 8));
+    DevPlan Pv = h->Pw;
+    Pv.ver_mod = 1, Pv.ver_rem = 0;
+    int ctr[CTR_COUNT];
+    HIP_TRY(hipMemsetAsync(Pv.ctr + CTR_MISMATCH, 0, sizeof(int), st));
+    galk_test_poke(&Pv, what, idx, bits, old, 0, st);
+    galk_launch_verify(&Pv, st);
+    HIP_TRY(hipMemcpyAsync(ctr, Pv.ctr, CTR_COUNT * sizeof(int), hipMemcpyDeviceToHost, st));
+    galk_test_poke(&Pv, what, idx, bits, old, 1, st);
+    HIP_TRY(hipMemsetAsync(Pv.ctr + CTR_MISMATCH, 0, sizeof(int), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipFree(old));
+    if (ctr[CTR_UNVERIFIED] != 0) return fail(GAL_E_STATE, "gal_synth_test_verify_count: the chain is not complete");
+    *count = ctr[CTR_MISMATCH];
+    return GAL_OK;
+}
 #endif
 
-// verify_here: k_synth_g does not verify the carrier checkpoints itself (k_synth's exact replay does, on its way); k_verify_carr
+// verify_here: k_synth_g does not verify the checkpoints itself (k_synth's exact replay does, on its way); k_verify
 // does, in front of it on the same stream (repair paths, handles without a walker stream) -- the first launch of a batch runs it
 // on the walker stream instead, beside the synthesis (gal_synth_execute_range)
 static int enqueue_synth(gal_synth *h, uint32_t *iq, bool verify_here)
@@ -1360,8 +1383,7 @@ static int enqueue_synth(gal_synth *h, uint32_t *iq, bool verify_here)
         // nothing to hide it behind, and the repair paths have reason to look at every leg)
         DevPlan Pv = h->Pw;
         if (h->stats.synth_runs > 1) Pv.ver_mod = 1, Pv.ver_rem = 0;
-        galk_launch_verify_carr(&Pv, h->stream);
-        galk_launch_verify_code(&Pv, h->stream);
+        galk_launch_verify(&Pv, h->stream);
     }
     if (h->nact_max == 0) {  // nothing is transmitted in this batch: the reference's loop stores zeros (:536-537)
         HIP_TRY(hipMemsetAsync(iq, 0, (size_t)h->range_ne * (size_t)h->P.N * 4u, h->stream));
@@ -1440,7 +1462,7 @@ int gal_synth_execute_range(gal_synth_t *h, int16_t *iq_dev, int32_t first_epoch
     h->Pw.tr_e0 = first_epoch;
     h->Pw.tr_e1 = first_epoch + n_epochs;
     h->Pw.cp_e0 = first_epoch;
-    // k_verify_carr / k_verify_code (k_synth_g batches): every leg of both chains (default); GAL_CFG_VERIFY_SAMPLED: an eighth of the leg
+    // k_verify (k_synth_g batches): every leg of both chains (default); GAL_CFG_VERIFY_SAMPLED: an eighth of the leg
     // positions per batch, rotating with the handle's batch count, plus the carrier legs whose translation was not overwhelmingly
     // inside its margin (synth_kernels.hip)
     h->Pw.ver_mod = (h->cfg.flags & GAL_CFG_VERIFY_SAMPLED) ? kVerifyRotation : 1;
@@ -1490,7 +1512,6 @@ int gal_synth_execute_range(gal_synth_t *h, int16_t *iq_dev, int32_t first_epoch
     }
     for (int pass = 0; pass < n_passes; ++pass) {
         galk_launch_walk_carr(P, pass == 0, ws);  // (the first one also resets the batch's counters)
-        if (pass == 0 && ws != st) HIP_TRY(hipEventRecord(h->ev_ctr, ws));
         galk_launch_carr_scan(P, ++h->scan_tag, ws);
     }
     // the code chain (restarts every epoch, no speculation) and the page resolution do not depend on the carrier chain:
@@ -1502,11 +1523,18 @@ int gal_synth_execute_range(gal_synth_t *h, int16_t *iq_dev, int32_t first_epoch
         galk_launch_pages(P, h->aux_stream);
         HIP_TRY(hipEventRecord(h->ev_aux, h->aux_stream));
     }
-    // k_synth_g batches: the carrier checkpoints are verified by a kernel of their own (k_verify_carr), on the walker stream
-    // behind the chain and beside the synthesis; the completion record waits for both
+    // k_synth_g batches: the checkpoints of both chains are verified by a kernel of their own (k_verify), ONE launch on the walker
+    // stream behind the carrier chain and beside the synthesis; the completion record waits for it.  What its place guarantees:
+    //  - it counts into CTR_MISMATCH, which the FIRST carrier walk of the batch resets: behind the whole carrier chain on the same
+    //    stream no mismatch can be counted in front of that reset, nor in front of the last stitch's completion (the stitch may
+    //    still translate checkpoints);
+    //  - the code checkpoints come from the second walker stream: the walker stream waits for ev_aux in front of the launch -- behind
+    //    ev_walk, so the synthesis does not inherit that wait through ev_walk (it has its own on ev_aux);
+    //  - a chain that is not complete (CTR_UNVERIFIED != 0) makes the kernel leave at once, both parts: gal_synth_finish then iterates
+    //    from the host, clears CTR_MISMATCH and launches k_verify again in front of the repeated synthesis (enqueue_synth).
     bool verify_beside = h->P.fam == 1 && ws != st && h->nact_max != 0;
 #ifdef GAL_TEST_HOOKS
-    const bool no_verify = getenv("GAL_G_NOVERIFY") != nullptr;  // timing experiments only: what k_verify_carr costs the pipeline
+    const bool no_verify = getenv("GAL_G_NOVERIFY") != nullptr;  // timing experiments only: what k_verify costs the pipeline
     if (no_verify) verify_beside = false;
 #else
     const bool no_verify = false;
@@ -1515,14 +1543,19 @@ int gal_synth_execute_range(gal_synth_t *h, int16_t *iq_dev, int32_t first_epoch
         HIP_TRY(hipEventRecord(h->ev_walk, ws));
         HIP_TRY(hipStreamWaitEvent(st, h->ev_walk, 0));
         if (verify_beside) {
-            galk_launch_verify_carr(P, ws);
+            HIP_TRY(hipStreamWaitEvent(ws, h->ev_aux, 0));
+#ifdef GAL_TEST_HOOKS
+            if (const char *env = getenv("GAL_VERIFY_POKE")) {  // "what,idx,bits": one checkpoint word perturbed between the stitch and the verifier
+                int what = -1;
+                long long idx = -1;
+                unsigned bits = 0;
+                if (sscanf(env, "%d,%lld,%u", &what, &idx, &bits) == 3 && what >= 0 && what <= 3 && idx >= 0 &&
+                    idx < (what == 3 ? (long long)h->P.E * h->P.S : (long long)h->P.E * h->P.S * h->P.CP1))
+                    galk_test_poke(P, what, idx, bits, nullptr, 0, ws);
+            }
+#endif
+            galk_launch_verify(P, ws);
             HIP_TRY(hipEventRecord(h->ev_ver, ws));
-            // ... and the code checkpoints, on the second walker stream behind the code walk that wrote them (ev_aux is recorded):
-            // it does not wait for the carrier chain -- only for the first carrier walk, whose first block resets the counters
-            // this kernel counts its mismatches in
-            HIP_TRY(hipStreamWaitEvent(h->aux_stream, h->ev_ctr, 0));
-            galk_launch_verify_code(P, h->aux_stream);
-            HIP_TRY(hipEventRecord(h->ev_verc, h->aux_stream));
         }
     }
     HIP_TRY(hipStreamWaitEvent(st, h->ev_aux, 0));
@@ -1530,10 +1563,7 @@ int gal_synth_execute_range(gal_synth_t *h, int16_t *iq_dev, int32_t first_epoch
     int rc = enqueue_synth(h, (uint32_t *)iq_dev, !verify_beside && !no_verify);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(h->ev[2], st));
-    if (verify_beside) {
-        HIP_TRY(hipStreamWaitEvent(st, h->ev_ver, 0));
-        HIP_TRY(hipStreamWaitEvent(st, h->ev_verc, 0));
-    }
+    if (verify_beside) HIP_TRY(hipStreamWaitEvent(st, h->ev_ver, 0));
     // counters (walker passes + replay check) and the end-of-batch state, behind the synthesis: nothing in front of
     // k_synth that it does not need (finish()'s repair paths fetch both again)
     h->seq += 1;

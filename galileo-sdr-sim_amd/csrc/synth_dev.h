@@ -68,9 +68,9 @@ struct DevPlan {
     int8_t *tdir;        // rounding direction of the first tie the walk met (WalkOut::tdir), 0 = none
     long long *tpos;     // global sample index right after that tie step
     double *shift;       // pending translation (new anchor residual - walked anchor residual)
-    uint8_t *risk;       // 1: the leg was accepted by a translation that used more than 1/256 of its binade margin: k_verify_carr
+    uint8_t *risk;       // 1: the leg was accepted by a translation that used more than 1/256 of its binade margin: k_verify
                          // re-walks such a leg in every batch, whatever the rotation says
-    int ver_mod, ver_rem;  // k_verify_carr re-walks the legs i = ver_rem (mod ver_mod) of the executed epochs (1, 0: every leg)
+    int ver_mod, ver_rem;  // k_verify re-walks the legs i = ver_rem (mod ver_mod) of the executed epochs (1, 0: every leg)
     void *scanm;         // scratch of the stitch: tickets and look-back records (synth_kernels.hip: ScanM)
     int translate;       // 1 normal; 0: always re-walk (the all-walked fallback); 2: GAL_TEST_HOOKS builds only
     int tr_e0, tr_e1;    // legs of epochs outside [tr_e0, tr_e1) are never translated (gal_synth_execute_range)

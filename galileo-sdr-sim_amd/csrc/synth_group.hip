@@ -27,7 +27,7 @@
 // a matter of the window's contents, not of the sample loop (k_synth: slow groups); the chunk's checkpoints are wave-uniform
 // scalar loads (k_synth: 36 gathers per lane); neighbouring lanes read neighbouring carrier-table entries (4.7 instead of
 // 6.7 LDS cycles per gather at +-3.5 kHz).
-// The carrier checkpoints, which k_synth's exact replay verifies on its way, are verified by k_verify_carr (synth_kernels.hip)
+// The checkpoints of both chains, which k_synth's exact replay verifies on its way, are verified by k_verify (synth_kernels.hip)
 // on the walker stream, beside this kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -835,9 +835,9 @@ __global__ __launch_bounds__(256) void k_repair_g(DevPlan P, SynGeom G, uint32_t
             {
                 // ... and both chains walked on to the END of the chunk: they must arrive at the next checkpoint, bit for bit (the
                 // end-of-epoch state behind the last chunk).  The listed groups are scattered over the batch by the bits of the
-                // phases, so this is a random sample of ~20 000 (chunk, channel) pairs per 120 s batch -- the only check the CODE
-                // checkpoints get on this kernel family (k_synth's replay checks every one), and one more on the carrier's beside
-                // k_verify_carr's rotation.  A mismatch ends the batch in gal_synth_finish's repair path.
+                // phases, so this is a random sample of ~20 000 (chunk, channel) pairs per 120 s batch -- one more check beside
+                // k_verify (synth_kernels.hip), which re-walks every leg of BOTH chains in every batch of this kernel family (an eighth
+                // per batch under GAL_CFG_VERIFY_SAMPLED).  A mismatch ends the batch in gal_synth_finish's repair path.
                 int nR = G.N - c * G.R;
                 nR = nR > G.R ? G.R : nR;
                 const int rem = nR - 16 * g;

@@ -395,7 +395,8 @@ __global__ void k_walk_carr(DevPlan P, int first)
     }
 }
 
-// k_verify_carr: legs of the executed epochs walked once more, genuinely and in closed form, from their own first checkpoint:
+// k_verify, carrier part (verify_carr_thread): legs of the executed epochs walked once more, genuinely and in closed form, from their
+// own first checkpoint:
 // each checkpoint of the leg and the state it hands to the next leg must come out bit for bit (CTR_MISMATCH otherwise, which sends
 // gal_synth_finish into the all-walked fallback).  This is what k_synth's exact replay establishes on its way; k_synth_g
 // (synth_group.hip) never forms the exact phase, so batches that run it get this kernel on the walker stream, beside the synthesis.
@@ -425,54 +426,87 @@ __device__ __forceinline__ void verify_carr_leg(const DevPlan &P, const int s, c
     if (bad) atomicAdd(&P.ctr[CTR_MISMATCH], bad);
 }
 
-__global__ void k_verify_carr(DevPlan P)
+// Which position thread t of k_verify's grid re-walks: THE mapping -- the kernel's two bodies and the host (galk_verify_position, for the
+// tests of the sampled rotation) call this one function.  The first verify_carr_threads() threads (whole blocks, hence whole waves) are
+// the carrier verifier's: the rotation's legs i = ver_rem (mod ver_mod), compact and slot by slot, then (sampled mode) one thread per
+// eight legs for the risk flags; the threads behind them are the code verifier's in k_walk_code's layout.
+#define VERIFY_THREADS 256
+struct VerifyPos {
+    int chain;    // 0: carrier leg k of epoch e; 1: code leg k of epoch e; 2: the risk flags of the eight legs from li = e on; -1: nothing
+    int s, e, k;
+};
+
+__host__ __device__ __forceinline__ int verify_carr_threads(const int legs, const int S, const int ver_mod)
 {
-    if (P.ctr[CTR_UNVERIFIED] != 0) return;  // chain not complete: gal_synth_finish iterates and launches this again
-    const int mod = P.ver_mod > 1 ? P.ver_mod : 1;
-    const int per_slot = (P.LEGS + mod - 1) / mod;
-    const int nsel = per_slot * P.S;
-    int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < nsel) {
-        const int s = t / per_slot;
-        const int i = (t - s * per_slot) * mod + P.ver_rem;
-        if (i < P.LEGS) verify_carr_leg(P, s, i);
+    const int mod = ver_mod > 1 ? ver_mod : 1;
+    const int nsel = (legs + mod - 1) / mod * S;  // the rotation's legs, then (mod > 1) one thread per eight legs for the risky ones
+    const int n = nsel + (mod > 1 ? (legs * S + 7) / 8 : 0);
+    return (n + VERIFY_THREADS - 1) / VERIFY_THREADS * VERIFY_THREADS;
+}
+
+__host__ __device__ __forceinline__ VerifyPos verify_position(int t, const int E, const int S, const int W, const int Wc, const int ver_mod,
+                                                              const int ver_rem)
+{
+    VerifyPos q = {-1, 0, 0, 0};
+    const int legs = E * W, mod = ver_mod > 1 ? ver_mod : 1;
+    const int nc = verify_carr_threads(legs, S, ver_mod);
+    if (t < nc) {
+        const int per_slot = (legs + mod - 1) / mod;
+        const int nsel = per_slot * S;
+        if (t < nsel) {
+            const int s = t / per_slot;
+            const int i = (t - s * per_slot) * mod + ver_rem;
+            if (i < legs) {
+                q.chain = 0; q.s = s; q.e = i / W; q.k = i - q.e * W;
+            }
+            return q;
+        }
+        t -= nsel;
+        if (mod > 1 && t * 8 < legs * S) {
+            q.chain = 2; q.e = t * 8;
+        }
+        return q;
+    }
+    t -= nc;
+    if (t >= E * S * Wc) return q;
+    const int k = t & (Wc - 1), se = t / Wc, s = se / E, e = se - s * E;
+    if (mod > 1 && (e * Wc + k) % mod != ver_rem) return q;
+    q.chain = 1; q.s = s; q.e = e; q.k = k;
+    return q;
+}
+
+__device__ __forceinline__ void verify_carr_thread(const DevPlan &P, const VerifyPos &q)
+{
+    if (q.chain == 0) {
+        verify_carr_leg(P, q.s, q.e * P.W + q.k);
         return;
     }
     // (b), sampled mode only: eight legs' flags per thread; a set one is next to never seen, and EVERY set one is re-walked (round 5
     // re-walked the first of the eight only: ADVICE r5)
-    t -= nsel;
+    const int mod = P.ver_mod > 1 ? P.ver_mod : 1;
     const int total = P.LEGS * P.S;
-    if (mod == 1 || t * 8 >= total) return;
 #pragma unroll 1
-    for (int q = 0; q < 8 && t * 8 + q < total; ++q) {
-        const int li = t * 8 + q;
-        if (!P.risk[li] || li % P.LEGS % mod == P.ver_rem) continue;
+    for (int j = 0; j < 8 && q.e + j < total; ++j) {
+        const int li = q.e + j;
+        if (!P.risk[li] || li % P.LEGS % mod == P.ver_rem) continue;  // (the rotation's own legs are walked by their threads)
         const int s = li / P.LEGS;
         verify_carr_leg(P, s, li - s * P.LEGS);
     }
 }
 
-// k_verify_code: the same for the CODE chain (round 6; ADVICE r5: on the k_synth_g family its checkpoints were only checked where
+// k_verify, code part (verify_code_thread): the same for the CODE chain (round 6; ADVICE r5: on the k_synth_g family its checkpoints were only checked where
 // k_repair_g happened to walk, ~0.5 % of them per batch).  One lane per (slot, epoch, code leg) of the executed epochs -- k_walk_code's
 // layout --, the leg walked once more from its own first checkpoint, genuinely and in closed form (code_walk: no speculation, no
 // translation): every checkpoint of the leg, the state it hands to the next leg (or the end-of-epoch state) and -- leg 0 -- the epoch's
 // host-given start state must come out bit for bit, symbol counter and page-flip flag included.  By induction from the epoch's
 // start every code checkpoint of the batch is then what stepping src/galileo-sdr.cpp:491-507,528 sample by sample produces.
 // Sampled mode (GAL_CFG_VERIFY_SAMPLED): the legs (epoch * Wc + leg) = ver_rem (mod ver_mod).
-__global__ void k_verify_code(DevPlan P)
+__device__ __forceinline__ void verify_code_thread(const DevPlan &P, const VerifyPos &q)
 {
-    const int Wc = P.Wc;
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= P.E * P.S * Wc) return;
-    const int k = t & (Wc - 1);
-    const int se = t / Wc;
-    const int s = se / P.E;
-    const int e = se - s * P.E;
+    const int s = q.s, e = q.e, k = q.k;
     if (e < P.cp_e0) return;  // epochs in front of the executed range carry no checkpoints
     const int idx = e * P.S + s;
     if (P.prn[idx] <= 0) return;
-    const int mod = P.ver_mod > 1 ? P.ver_mod : 1;
-    if (mod > 1 && (e * Wc + k) % mod != P.ver_rem) return;
     const int Lk = P.Lkc;
     const int n0 = k * Lk * P.R;
     if (n0 >= P.N) return;
@@ -493,6 +527,44 @@ __global__ void k_verify_code(DevPlan P)
     if (n1 >= P.N) bad += P.flip_in[idx] != (uint8_t)(end.flipped | fl0);  // what k_pages reads
     if (bad) atomicAdd(&P.ctr[CTR_MISMATCH], bad);
 }
+
+// k_verify: ONE launch for both chains (two kernels -- and, beside the synthesis, two streams with a chain each for gal_synth_finish to
+// wait for -- up to round 6).  The first carr_threads threads of the grid (a multiple of the block, hence of the wave) are the carrier
+// verifier's, the threads behind them the code verifier's in k_walk_code's layout: a wave never mixes the two bodies.  A code leg is
+// 88 dependent closed-form steps against the carrier leg's 484, so the code waves end in the carrier waves' shadow.  Both parts count
+// into CTR_MISMATCH and both leave while the carrier chain is incomplete (gal_synth_finish iterates, clears the counter and launches
+// this kernel again in front of the repeated synthesis: enqueue_synth).
+__global__ void __launch_bounds__(VERIFY_THREADS) k_verify(DevPlan P)
+{
+    if (P.ctr[CTR_UNVERIFIED] != 0) return;  // chain not complete: gal_synth_finish iterates and launches this again
+    // (P.LEGS = P.E * P.W: the walkers' plan is cut to the epochs up to the end of the executed range)
+    const VerifyPos q = verify_position(blockIdx.x * VERIFY_THREADS + threadIdx.x, P.E, P.S, P.W, P.Wc, P.ver_mod, P.ver_rem);
+    if (q.chain == 1) verify_code_thread(P, q);
+    else if (q.chain >= 0) verify_carr_thread(P, q);
+}
+
+#ifdef GAL_TEST_HOOKS
+// what: 0 cp_p[idx] one ulp up, 1 cp_x[idx] one ulp up, 2 cp_ib[idx] ^= bits, 3 flip_in[idx] ^= 1.  Applying it twice with what = 0 / 1 is not
+// an inverse: the tests restore through the saved value (galk_test_poke returns it).
+__global__ void k_test_poke(DevPlan P, int what, long long idx, unsigned bits, unsigned long long *old, int restore)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (what == 0 || what == 1) {
+        uint64_t *w = (uint64_t *)(what == 0 ? P.cp_p : P.cp_x) + idx;
+        if (restore) { *w = *old; return; }
+        if (old) *old = *w;
+        *w = *w + 1ull;
+    } else if (what == 2) {
+        if (restore) { P.cp_ib[idx] = (uint32_t)*old; return; }
+        if (old) *old = P.cp_ib[idx];
+        P.cp_ib[idx] ^= bits;
+    } else if (what == 3) {
+        if (restore) { P.flip_in[idx] = (uint8_t)*old; return; }
+        if (old) *old = P.flip_in[idx];
+        P.flip_in[idx] ^= 1;
+    }
+}
+#endif
 
 // k_scanm stitches the legs of a slot.  Sequential statement (what its three phases compute; walk_host.cpp::galwalk_spec_wrap
 // runs the same statement on the host):
@@ -2269,18 +2341,30 @@ extern "C" void galk_launch_walk_code(const DevPlan *P, hipStream_t st)
     hipLaunchKernelGGL(k_walk_code, dim3((n + 63) / 64), dim3(64), 0, st, *P);
 }
 
-extern "C" void galk_launch_verify_carr(const DevPlan *P, hipStream_t st)
+extern "C" void galk_launch_verify(const DevPlan *P, hipStream_t st)
 {
-    const int mod = P->ver_mod > 1 ? P->ver_mod : 1;
-    const int nsel = (P->LEGS + mod - 1) / mod * P->S;  // the rotation's legs, then (mod > 1) one thread per eight legs for the risky ones
-    const int n = nsel + (mod > 1 ? (P->LEGS * P->S + 7) / 8 : 0);
-    hipLaunchKernelGGL(k_verify_carr, dim3((n + 255) / 256), dim3(256), 0, st, *P);
+    const int nc = verify_carr_threads(P->LEGS, P->S, P->ver_mod);  // carrier legs first, whole blocks of them ...
+    const int n = nc + P->E * P->S * P->Wc;                         // ... then one lane per leg of the code chain
+    hipLaunchKernelGGL(k_verify, dim3((n + VERIFY_THREADS - 1) / VERIFY_THREADS), dim3(VERIFY_THREADS), 0, st, *P);
 }
 
-extern "C" void galk_launch_verify_code(const DevPlan *P, hipStream_t st)
+#ifdef GAL_TEST_HOOKS
+extern "C" void galk_test_poke(const DevPlan *P, int what, long long idx, unsigned bits, unsigned long long *old_dev, int restore, hipStream_t st)
 {
-    const int n = P->E * P->S * P->Wc;
-    hipLaunchKernelGGL(k_verify_code, dim3((n + 63) / 64), dim3(64), 0, st, *P);
+    hipLaunchKernelGGL(k_test_poke, dim3(1), dim3(64), 0, st, *P, what, idx, bits, old_dev, restore);
+}
+#endif
+
+// Which (epoch, leg) position of which chain thread t of k_verify's grid re-walks: verify_position(), the function the kernel calls, for
+// the tests of the sampled rotation (tests/test_verify_fused.py).  Returns 0 and (chain 0 carrier / 1 code, slot, epoch, leg) if the
+// thread walks one, 1 if it has none (padding, an unselected leg, the carrier's risk-flag threads), -1 behind the grid.
+extern "C" int galk_verify_position(int t, int E, int S, int W, int Wc, int ver_mod, int ver_rem, int *chain, int *slot, int *epoch, int *leg)
+{
+    if (t < 0 || t >= verify_carr_threads(E * W, S, ver_mod) + E * S * Wc) return -1;
+    const VerifyPos q = verify_position(t, E, S, W, Wc, ver_mod, ver_rem);
+    if (q.chain != 0 && q.chain != 1) return 1;
+    *chain = q.chain; *slot = q.s; *epoch = q.e; *leg = q.k;
+    return 0;
 }
 
 extern "C" void galk_launch_walk_carr(const DevPlan *P, int first, hipStream_t st)

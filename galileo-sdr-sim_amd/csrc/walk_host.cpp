@@ -446,3 +446,131 @@ int galwalk_spec_wrap(int E, int W, int L, int N, const int *prn, const uint32_t
     return pass;
 }
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------
+// What the 64 lanes of a wave of k_walk_carr (mode 0: first pass, anchors from ideal arithmetic) or of k_verify_carr (mode 1: every
+// leg, from its own first checkpoint) do side by side, counted with the product's own walker (tools/walker_lane_profile.py; DESIGN.md
+// section 5.3).  Thread t of the grid is leg i = t % LEGS of slot s = t / LEGS, a wave is 64 consecutive threads -- the kernels'
+// own mapping.  A wave runs every loop of the kernel as often as its slowest lane: the loops are the kernel's, in program order --
+// (walk only) anchor -> leg start, one carr_walk_track per epoch segment, then the leg's carr_walk_track; each of them a general
+// loop followed by a lean loop.  out[wave * GALWALK_LP_COLS + k], sums over the wave's loop iterations ("wave" = executed by the
+// wave because some lane needs it, "lane" = lanes that need it):
+//   0 active lanes   1 wave iterations   2 lane iterations   3 the longest lane's iterations (all its loops together)
+//   4 / 5 wave / lane iterations whose genuine step WRAPS            6 / 7 ... whose genuine step crosses a binade (no wrap)
+//   8 / 9 ... that emit a checkpoint at their start                  10 / 11 trips of the checkpoint loop inside the batch (max / sum)
+//   12 / 13 ... without a closed-form batch (n == 0)                 14 / 15 ... that enter the tie bookkeeping
+//   16 / 17 wave / lane iterations in the GENERAL loop
+// dstep: [E][S] epoch-major; p_root[S]: the chain's start phase per slot (d == 0 slots are skipped: whole waves that leave at once
+// in the walk, a fixed point in the verifier).
+#define GALWALK_LP_COLS 18
+extern "C" int galwalk_lane_profile(int E, int S, int W, int Lc, int N, int R, const double *dstep, const double *p_root, int mode,
+                                    double *out, int max_waves)
+{
+    const int LEGS = E * W, L = Lc * R;
+    struct It { uint8_t loop, flags; uint16_t trips; };
+    // true phase at every leg start and every wrap-anchored first guess, slot by slot
+    std::vector<double> leg_p((size_t)S * LEGS, 0.0), pg((size_t)S * E, 0.0), gr((size_t)S * E, 0.0);
+    std::vector<long long> gw((size_t)S * E, 0);
+    for (int s = 0; s < S; ++s) {
+        double p = p_root[s], q = p_root[s], lr = p_root[s];
+        long long lw = 0;
+        for (int e = 0; e < E; ++e) {
+            const double d = dstep[(size_t)e * S + s];
+            p = carr_walk_track(p, d, 1.0 / __builtin_fabs(d), N, L, 0, [&](int c, double v) { leg_p[(size_t)s * LEGS + e * W + c] = v; }).p;
+            pg[(size_t)s * E + e] = q; gw[(size_t)s * E + e] = lw; gr[(size_t)s * E + e] = lr;
+            int om; double rr;
+            const double de = eff_step(d);
+            if (ideal_last_wrap(q, de, N, &om, &rr)) { lw = (long long)e * N + om; lr = rr; }
+            q = q + (double)N * de;
+            q = q - __builtin_trunc(q);
+        }
+    }
+    const int T = LEGS * S, nw = (T + 63) / 64;
+    if (nw > max_waves) return -1;
+    std::vector<std::vector<std::vector<It>>> ph(64);  // [lane][loop slot][iteration]
+    for (int wv = 0; wv < nw; ++wv) {
+        double *o = out + (size_t)wv * GALWALK_LP_COLS;
+        for (int k = 0; k < GALWALK_LP_COLS; ++k) o[k] = 0.0;
+        size_t nslots = 0;
+        for (int ln = 0; ln < 64; ++ln) {
+            ph[ln].clear();
+            const int t = wv * 64 + ln;
+            if (t >= T) continue;
+            const int s = t / LEGS, i = t - s * LEGS, e = i / W, w = i - e * W;
+            const double d = dstep[(size_t)e * S + s];
+            if (d == 0.0 && mode == 0) continue;
+            o[0] += 1;
+            auto run = [&](double p, double dd, int n, int Rr, int cp0) {
+                ph[ln].emplace_back(); ph[ln].emplace_back();  // general, lean
+                const size_t b = ph[ln].size() - 2;
+                return carr_walk_track(p, dd, 1.0 / __builtin_fabs(dd), n, Rr, cp0, [](int, double) {},
+                                       [&](int loop, int fl, int tr) { ph[ln][b + loop].push_back(It{(uint8_t)loop, (uint8_t)fl, (uint16_t)tr}); }).p;
+            };
+            int n = N - w * L;
+            n = n > L ? L : n;
+            if (mode == 1) {
+                run(leg_p[(size_t)s * LEGS + i], d, n, R, 0);
+            } else {
+                const long long A = (long long)e * N + (long long)w * L;
+                int om; double rr, p;
+                long long cur;
+                if (ideal_last_wrap(pg[(size_t)s * E + e], eff_step(d), w * L, &om, &rr)) { cur = (long long)e * N + om; p = rr; }
+                else { cur = gw[(size_t)s * E + e]; p = gr[(size_t)s * E + e]; }
+                while (cur < A) {
+                    const int ec = (int)(cur / N);
+                    long long seg_end = (long long)(ec + 1) * N;
+                    seg_end = seg_end > A ? A : seg_end;
+                    const int nn = (int)(seg_end - cur);
+                    const double dd = dstep[(size_t)ec * S + s];
+                    if (dd != 0.0) p = run(p, dd, nn, nn, nn);
+                    cur = seg_end;
+                }
+                // the leg's own loops come last whatever the number of segments in front: align them across lanes at the back
+                const size_t b0 = ph[ln].size();
+                run(p, d, n, R, 0);
+                const std::vector<It> lg = ph[ln][b0], ll = ph[ln][b0 + 1];
+                ph[ln].resize(b0);
+                ph[ln].insert(ph[ln].begin(), ll);  // loop slot 0 = the leg's lean loop, 1 = its general loop, 2.. = the segments' loops
+                ph[ln].insert(ph[ln].begin() + 1, lg);
+            }
+            nslots = std::max(nslots, ph[ln].size());
+        }
+        long longest = 0;
+        for (int ln = 0; ln < 64; ++ln) {
+            long tot = 0;
+            for (auto &v : ph[ln]) tot += (long)v.size();
+            longest = std::max(longest, tot);
+        }
+        o[3] = (double)longest;
+        for (size_t sl = 0; sl < nslots; ++sl) {
+            size_t mx = 0;
+            for (int ln = 0; ln < 64; ++ln)
+                if (sl < ph[ln].size()) mx = std::max(mx, ph[ln][sl].size());
+            for (size_t j = 0; j < mx; ++j) {
+                int act = 0, wr = 0, cr = 0, cs = 0, tmax = 0, tsum = 0, nb = 0, tie = 0, gen = 0;
+                for (int ln = 0; ln < 64; ++ln) {
+                    if (sl >= ph[ln].size() || j >= ph[ln][sl].size()) continue;
+                    const It &it = ph[ln][sl][j];
+                    ++act;
+                    wr += (it.flags & WALK_PROBE_WRAP) ? 1 : 0;
+                    cr += ((it.flags & WALK_PROBE_STEP) && !(it.flags & WALK_PROBE_WRAP)) ? 1 : 0;
+                    cs += (it.flags & WALK_PROBE_CP_START) ? 1 : 0;
+                    tmax = std::max(tmax, (int)it.trips);
+                    tsum += it.trips;
+                    nb += (it.flags & WALK_PROBE_NO_BATCH) ? 1 : 0;
+                    tie += (it.flags & WALK_PROBE_TIE) ? 1 : 0;
+                    gen += it.loop == 0 ? 1 : 0;
+                }
+                o[1] += 1; o[2] += act;
+                o[4] += wr > 0; o[5] += wr;
+                o[6] += cr > 0; o[7] += cr;
+                o[8] += cs > 0; o[9] += cs;
+                o[10] += tmax; o[11] += tsum;
+                o[12] += nb > 0; o[13] += nb;
+                o[14] += tie > 0; o[15] += tie;
+                o[16] += gen > 0; o[17] += gen;
+            }
+        }
+    }
+    return nw;
+}

@@ -105,7 +105,7 @@ typedef struct gal_synth_cfg {
 #define GAL_CFG_VERIFY_SAMPLED 16u /* batches of the default kernel (kernel_family 1), which never forms an exact phase itself.  DEFAULT
                                     (flag clear): every carrier leg and every code leg of the executed epochs is walked once more from
                                     its own first checkpoint, genuinely, in every batch, and every checkpoint must come out bit for
-                                    bit (k_verify_carr, k_verify_code) -- what the exact-replay kernel establishes on its way.
+                                    bit (k_verify) -- what the exact-replay kernel establishes on its way.
                                     Flag set (round 5's default; ~3-5 % less per step): an eighth of the leg positions of both
                                     chains per batch, rotating with the handle's batch count -- every (epoch, leg) position of a
                                     repeated plan is re-walked once per N = 8 batches --, plus every carrier leg whose translation
