@@ -5,7 +5,7 @@
 //   Q[b]  = P[b - W] + ... + P[b - 1]                         (the W blocks BEFORE b: every gain is known before its block begins)
 //   g[b]  = clamp((target_q8 << 12) div max(isqrt((Q[b] << 16) div (2 B W)), 1), gain_min_q12, gain_max_q12)
 //   z     = clamp16((int64(y) g[b] + 2048) >> 12)             (arithmetic shift), b the block of the value's sample
-//   out   z in the format: ishort z; ibyte (z + r) >> s clamped to +-127 (iq_pass.hip's rule); i2bit q = (z > thr) + (z > 0) + (z > -thr) - 2,
+//   out   z in the format: ishort z; ibyte (z + r) >> s clamped to +-127 (iq_dev.h: f8); i2bit q = (z > thr) + (z > 0) + (z > -thr) - 2,
 //         the code q & 3, four codes per byte with value 4k in bits 7..6, unused low bits of the last byte 0
 //
 // A value counts once as saturated if the int16 clamp or ibyte's +-127 clamp changed it.  Everything is integer arithmetic
@@ -29,16 +29,13 @@
 //                 trip, the samples behind the last whole trip in one lane.  A lane finds the block of its first run with one 32-bit
 //                 division, steps the position sample by sample inside a run, and jumps to its next run with the host's (jump div B,
 //                 jump mod B) and one conditional correction.  Saturated values: per lane, per wave, per block, one atomic per block.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
 #include "../../include/galsynth.h"
+#include "iq_dev.h"
 
 namespace {
 
-// tests/agc_model.py repeats kThreads, kMaxBlocks, kPowChunk and the formats' runs (4 x kVec) as THREADS, MAX_BLOCKS, POWER_CHUNK and RUN:
+// tests/agc_model.py repeats kThreads (iq_dev.h), kMaxBlocks, kPowChunk and the formats' runs (4 x kVec) as THREADS, MAX_BLOCKS, POWER_CHUNK and RUN:
 // the GPU tests place their sizes at these edges.  Change them there too, or the edge sizes go stale without a failure.
-constexpr int kThreads = 256;
 constexpr int kMaxBlocks = 2048;  // 8 blocks of 4 waves per CU, the rest by the grid-stride loop
 constexpr int kHistMax = GAL_AGC_MAX_WINDOW;  // a state buffer: [0 .. W-1] the powers of the last W complete blocks, oldest first; [kHistMax] the open block's partial sum
 
@@ -48,9 +45,6 @@ constexpr int kPowTrip = kThreads * kPowRun;               // 4096 samples
 constexpr int kPowChunk = kPowTrip * kPowTrips;            // 16384 samples per workgroup
 constexpr int kPowSlots = kPowChunk / GAL_AGC_MIN_BLOCK + 2;  // blocks a chunk can touch: (B - 1 + 16383) div B + 1 <= 1025 at B = 16
 static_assert(kPowRun <= GAL_AGC_MIN_BLOCK, "a run of k_agc_power crosses at most one block edge");
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef short v2s __attribute__((ext_vector_type(2)));
 
 // I^2 + Q^2 of one complex sample: at most 2^31, exact as an unsigned 32-bit number
 __device__ __forceinline__ uint32_t power(uint32_t w)
@@ -169,25 +163,10 @@ __global__ __launch_bounds__(kThreads) void k_agc_gains(const unsigned long long
 }
 
 // ---- apply and format ----------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int clamp16(int v) { return min(max(v, -32768), 32767); }
-
 // (y g + 2048) >> 12 BEFORE the clamp to int16: |y g| <= 2^39, the result fits an int
 __device__ __forceinline__ int scaled(int y, uint32_t g) { return (int)(((long long)y * (long long)(int)g + 2048) >> 12); }
 
-__device__ __forceinline__ uint32_t f16(int v, uint32_t &sat)
-{
-    const int z = clamp16(v);
-    sat += (uint32_t)(z != v);
-    return (uint32_t)z & 0xffffu;
-}
-
-__device__ __forceinline__ uint32_t f8(int v, int s, int r, uint32_t &sat)
-{
-    const int z = clamp16(v), q = (z + r) >> s;
-    sat += (uint32_t)((z != v) | (q < -127) | (q > 127));
-    return (uint32_t)(min(max(q, -127), 127)) & 0xffu;
-}
-
+// f16 and f8 of a scaled value before the clamp to int16: iq_dev.h
 // the 2-bit code: the magnitude saturates by design and is not counted
 __device__ __forceinline__ uint32_t f2(int v, int thr, uint32_t &sat)
 {
@@ -256,23 +235,6 @@ struct Fmt2Bit {
     }
 };
 
-// per-lane counts -> one atomicAdd per block, only where the block saw a saturated value (iq_pass.hip: add_block_count)
-__device__ __forceinline__ void add_block_count(uint32_t cnt, unsigned long long *sat)
-{
-    __shared__ unsigned long long part[kThreads / 64];
-    unsigned long long c = cnt;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long s = 0;
-#pragma unroll
-        for (int w = 0; w < kThreads / 64; ++w) s += part[w];
-        if (s) atomicAdd(sat, s);
-    }
-}
-
 // where a lane stands in the stream: block q of the call, `rem` samples into it, g = gains[q]
 struct Pos {
     uint64_t q;
@@ -339,7 +301,7 @@ __global__ __launch_bounds__(kThreads) void k_iq_agc(const int16_t *__restrict__
             step(ps, B, gains);
         }
     }
-    add_block_count(cnt, sat);
+    add_block_count<kThreads>(cnt, sat);
 }
 
 template <class Fmt>
@@ -366,7 +328,7 @@ extern "C" uint64_t galk_agc_scratch_bytes(uint64_t n, uint32_t off0, uint32_t b
 
 // n >= 1 samples (< 2^41) that begin off0 < block_len samples into a block; format GAL_IQ_ISHORT, GAL_IQ_IBYTE or GAL_IQ_I2BIT; state_in /
 // state_out: GAL_AGC_MAX_WINDOW + 1 words each; scratch: galk_agc_scratch_bytes, 8-byte aligned; gains_out may be null.  Arguments are
-// checked by the caller (synth_api.cpp: gal_synth_iq_agc).
+// checked by the caller (iq_api.cpp: gal_synth_iq_agc).
 extern "C" hipError_t galk_launch_iq_agc(const int16_t *in, uint64_t n, uint32_t off0, int format, int param, const gal_iq_agc_t *p,
                                          const unsigned long long *state_in, unsigned long long *state_out, void *scratch, void *out,
                                          uint32_t *gains_out, unsigned long long *sat, hipStream_t st)

@@ -20,12 +20,10 @@
 //   5. code_dph <= 2^32 (one half chip per sample) keeps a tile of 2048 samples inside 2048 half chips < one period: a tile sees at
 //      most ONE period boundary, at a block-uniform sample jb; every lane keeps two sets of sums, the period in front of jb and the
 //      one behind it, and walks [.., jb) and [jb, ..) separately -- exact, with uniform control flow.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "iq_dev.h"
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kTile = 2048;  // samples per block: 32 KB of LDS
 constexpr int kSub = 128;    // samples per int32 accumulation (see 4. above)
 constexpr int kHalfChips = 8184;
@@ -173,7 +171,7 @@ __global__ __launch_bounds__(kThreads) void k_corr(const void *__restrict__ buf,
 
 }  // namespace
 
-// One request.  Arguments are checked by the caller (synth_api.cpp: gal_synth_correlate): code_dph <= 2^32, 1 <= n_delay <= 8184,
+// One request.  Arguments are checked by the caller (iq_api.cpp: gal_synth_correlate): code_dph <= 2^32, 1 <= n_delay <= 8184,
 // 1 <= n_dopp <= 64, 1 <= max_periods <= 1024, `out` zeroed and large enough, n_eff <= n_samples of the buffer.
 extern "C" hipError_t galk_launch_corr(int format, const void *buf, uint64_t n_eff, uint64_t code_ph0, uint64_t code_dph, uint32_t carr_ph0,
                                        uint32_t carr_step0, uint32_t dopp_step, int delay0, int delay_step, int n_delay, int n_dopp,

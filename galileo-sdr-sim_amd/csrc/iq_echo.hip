@@ -23,23 +23,18 @@
 // line is 256 vectors, the call begins on a vector), and q + 1 never lies behind the lane's own vector, so nothing is read that the
 // undelayed load of some lane does not read too: the delayed reads hit lines that are in the cache already.  The cosine table (2 KB)
 // is copied to LDS by every block.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
 #include <type_traits>
 
 #include "../../include/galsynth.h"
+
 #define GAL_INTERF_DEVICE_TABLE
-#include "interf_table.inc"
+#include "iq_dev.h"
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kMaxBlocks = 2048;  // as k_iq_wsum: 8 blocks of 4 waves per CU, the rest by the grid-stride loops
 constexpr int kHist = GAL_ECHO_MAX_DELAY;      // complex samples of one history line
 constexpr int kHistVec = GAL_ECHO_MAX_DELAY / 4;
-
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 // one echo of one epoch as the kernel reads it (gal_iq_echo_t, 16 bytes: one scalar load)
 struct EchoRow {
@@ -49,33 +44,6 @@ struct EchoRow {
     uint32_t reserved;
 };
 static_assert(sizeof(EchoRow) == sizeof(gal_iq_echo_t), "the kernel reads gal_iq_echo_t rows");
-
-template <class T>
-__device__ __forceinline__ const __attribute__((address_space(1))) T *as_global(const int16_t *p)
-{
-    return (const __attribute__((address_space(1))) T *)p;
-}
-
-// (w + 64) >> 7 clamped to int16; `sat` counts the values the clamp changes
-template <class acc_t>
-__device__ __forceinline__ uint32_t q7(acc_t w, uint32_t &sat)
-{
-    const acc_t v = (w + 64) >> 7;
-    const acc_t y = v < -32768 ? (acc_t)-32768 : v > 32767 ? (acc_t)32767 : v;
-    sat += (uint32_t)(y != v);
-    return (uint32_t)y & 0xffffu;
-}
-
-// the four complex samples of vector `a` times g, added to w[0..7] (I0, Q0, I1, Q1, ...)
-template <class acc_t>
-__device__ __forceinline__ void mac8(acc_t (&w)[8], v4i a, int g)
-{
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        w[2 * m] += (acc_t)g * (acc_t)(int16_t)a[m];
-        w[2 * m + 1] += (acc_t)g * (acc_t)(a[m] >> 16);
-    }
-}
 
 // the complex sample u (I in the low half) turned by the table phase `ph` and scaled by A, added to (wI, wQ)
 template <class acc_t>
@@ -89,23 +57,6 @@ __device__ __forceinline__ void mac_echo(acc_t &wI, acc_t &wQ, int u, uint32_t p
     wQ += (acc_t)A * (acc_t)rQ;
 }
 
-// per-lane counts -> one atomicAdd per block, only where the block saw a saturated value (iq_gain.hip: add_block_count)
-__device__ __forceinline__ void add_block_count(uint32_t cnt, unsigned long long *sat)
-{
-    __shared__ unsigned long long part[kThreads / 64];
-    unsigned long long c = cnt;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long s = 0;
-#pragma unroll
-        for (int w = 0; w < kThreads / 64; ++w) s += part[w];
-        if (s) atomicAdd(sat, s);
-    }
-}
-
 // parts[k]: n_epochs * N complex samples, 16-byte aligned, none overlapping `out`; hist[k]: the kHist samples in front of part k (null
 // for a part without a line: no echo reads it); gain[e * n_parts + k]: 0 .. 32767; rows[e * n_echo + r]; part_of[r]: 0 .. n_parts - 1
 template <bool kWide>
@@ -115,10 +66,7 @@ __global__ __launch_bounds__(kThreads) void k_iq_echo(const int16_t *const *__re
                                                       int16_t *__restrict__ out, unsigned long long *sat)
 {
     typedef std::conditional_t<kWide, long long, int> acc_t;
-    __shared__ uint32_t cw[512];
-    for (int k = threadIdx.x; k < 512; k += kThreads) cw[k] = kInterfCosPairs[k];
-    __syncthreads();
-    const int16_t *cosl = (const int16_t *)cw;
+    const int16_t *cosl = load_cos_table();
     uint32_t cnt = 0;
     for (int e = blockIdx.y; e < n_epochs; e += gridDim.y) {
         const int *__restrict__ g = gain + (size_t)e * n_parts;
@@ -197,7 +145,7 @@ __global__ __launch_bounds__(kThreads) void k_iq_echo(const int16_t *const *__re
             }
         }
     }
-    add_block_count(cnt, sat);
+    add_block_count<kThreads>(cnt, sat);
 }
 
 // Block k: the new history line of part k = the last kHist samples of (old line, the call's n samples of the part).  hist_in[k] is
@@ -219,7 +167,7 @@ __global__ __launch_bounds__(kThreads) void k_echo_hist(const int16_t *const *__
 
 // tab_dev: the call's device table -- n_parts part pointers, hist_in and hist_out pointers at [GAL_ENGINE_MAX_CHAN] each (in that
 // order), then the gains [n_epochs][n_parts] int32, the echo rows [n_epochs][n_echo] and part_of_echo [n_echo] at the given pointers.
-// wide != 0: the int64 instance.  Arguments are checked by the caller (synth_api.cpp: gal_synth_iq_mpath).
+// wide != 0: the int64 instance.  Arguments are checked by the caller (iq_api.cpp: gal_synth_iq_mpath).
 extern "C" hipError_t galk_launch_iq_echo(const int16_t *const *parts_dev, const int16_t *const *hist_in_dev, int16_t *const *hist_out_dev,
                                           const int *gain_dev, const void *rows_dev, const int *part_of_dev, int n_parts, int n_echo,
                                           int n_epochs, int samples_per_epoch, int wide, int16_t *out, unsigned long long *sat, hipStream_t st)

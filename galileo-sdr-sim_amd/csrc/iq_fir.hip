@@ -33,15 +33,12 @@
 // conflict); one trip of the loop takes one such read per rail and 16 dot products.  The tap pairs are the host's table
 // (GE[2i], GO[2i], GE[2i + 1], GO[2i + 1]) per trip i, padded with zeros to whole trips, read through a uniform address: scalar
 // loads, the taps sit in SGPRs.  64-bit sample indices throughout.  Saturated values are counted per lane, per wave, per block, one
-// atomic per block that saw one (iq_pass.hip: add_block_count).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
+// atomic per block that saw one (iq_dev.h: add_block_count).
 #include "../../include/galsynth.h"
+#include "iq_dev.h"
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kTile = 4 * kThreads;  // complex samples per block
 constexpr int kHist = 128;           // history the handle keeps: the last 128 input samples (>= GAL_FIR_MAX_TAPS - 1, whole vectors)
 constexpr int kMaxTrips = 33;        // Hs / 2 + 1 <= 65 tap pairs, two per trip
@@ -50,39 +47,6 @@ constexpr int kMaxTrips = 33;        // Hs / 2 + 1 <= 65 tap pairs, two per trip
 constexpr int kStage = 2 * (2 * (kThreads - 1) + 2 * kMaxTrips + 2);
 static_assert(kStage >= kHist + kTile, "the stage holds the largest halo and the tile");
 static_assert(GAL_FIR_MAX_TAPS - 1 <= kHist && kHist % 4 == 0, "the history holds the longest halo in whole vectors");
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef short v2s __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int dot2(uint32_t w, uint32_t g, int acc)
-{
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s, w), __builtin_bit_cast(v2s, g), acc, false);
-}
-
-// (a + 8192) >> 14 is what `v` holds (the accumulators start at 8192); `sat` counts the values the clamp changes
-__device__ __forceinline__ uint32_t q14(int v, uint32_t &sat)
-{
-    const int r = v >> 14, y = min(max(r, -32768), 32767);
-    sat += (uint32_t)(y != r);
-    return (uint32_t)y & 0xffffu;
-}
-
-// per-lane counts -> one atomicAdd per block, only where the block saw a saturated value (iq_pass.hip: add_block_count)
-__device__ __forceinline__ void add_block_count(uint32_t cnt, unsigned long long *sat)
-{
-    __shared__ unsigned long long part[kThreads / 64];
-    unsigned long long c = cnt;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long s = 0;
-#pragma unroll
-        for (int w = 0; w < kThreads / 64; ++w) s += part[w];
-        if (s) atomicAdd(sat, s);
-    }
-}
 
 // in, out: n complex samples each, 16-byte aligned, not overlapping; taps: n_trips uint4 (see above); hs = the halo, a multiple of 4
 // in 0 .. 128; hist_in / hist_out: kHist complex samples each, the handle's two history buffers
@@ -164,7 +128,7 @@ __global__ __launch_bounds__(kThreads) void k_iq_fir(const uint32_t *__restrict_
                 if (o + m < n) out[o + m] = q14(aI[m], cnt) | (q14(aQ[m], cnt) << 16);
         }
     }
-    add_block_count(cnt, sat);
+    add_block_count<kThreads>(cnt, sat);
 }
 
 }  // namespace
@@ -189,7 +153,7 @@ extern "C" void galk_fir_table(const int16_t *h, int n_taps, uint32_t *table, in
     *hs = Hs;
 }
 
-// n >= 1 complex samples; arguments are checked by the caller (synth_api.cpp: gal_synth_iq_fir), which also keeps n below 2^41
+// n >= 1 complex samples; arguments are checked by the caller (iq_api.cpp: gal_synth_iq_fir), which also keeps n below 2^41
 extern "C" hipError_t galk_launch_iq_fir(const int16_t *in, int16_t *out, uint64_t n, const uint32_t *table_dev, int n_trips, int hs,
                                          const uint32_t *hist_in, uint32_t *hist_out, unsigned long long *sat, hipStream_t st)
 {

@@ -39,53 +39,17 @@
 // The stream across calls: the handle keeps the last kHist = 512 input samples (zeros in front of the stream's start) in one of two
 // device buffers; a call reads the one the call before it wrote and block 0 writes the other.  A call that keeps no output still
 // runs one block for this.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
 #include "../../include/galsynth.h"
+#include "iq_dev.h"
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kTileIn = 4096;  // input samples per block at most: a block filters (kTileIn / M) & ~3 outputs, M times that many inputs
 constexpr int kHist = 512;     // history the handle keeps: the last 512 input samples (>= GAL_FIRDEC_MAX_TAPS - 1, whole vectors)
 // staged elements per rail, all planes: M (OB + 4 trips) <= kTileIn + M (U + 5) <= kTileIn + 511 + 5 x 16 (galk_firdec_table checks it)
 constexpr int kStage = kTileIn + 640;
 static_assert(GAL_FIRDEC_MAX_TAPS - 1 <= kHist && kHist % 4 == 0, "the history holds the longest halo in whole vectors");
 static_assert(kTileIn + (GAL_FIRDEC_MAX_TAPS - 1) + 5 * GAL_FIRDEC_MAX_DECIM <= kStage && kStage % 8 == 0, "the stage holds every shape");
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef short v2s __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int dot2(uint32_t w, uint32_t g, int acc)
-{
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s, w), __builtin_bit_cast(v2s, g), acc, false);
-}
-
-// (a + 8192) >> 14 is what `v` holds (the accumulators start at 8192); `sat` counts the values the clamp changes
-__device__ __forceinline__ uint32_t q14(int v, uint32_t &sat)
-{
-    const int r = v >> 14, y = min(max(r, -32768), 32767);
-    sat += (uint32_t)(y != r);
-    return (uint32_t)y & 0xffffu;
-}
-
-// per-lane counts -> one atomicAdd per block, only where the block saw a saturated value (iq_pass.hip: add_block_count)
-__device__ __forceinline__ void add_block_count(uint32_t cnt, unsigned long long *sat)
-{
-    __shared__ unsigned long long part[kThreads / 64];
-    unsigned long long c = cnt;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long s = 0;
-#pragma unroll
-        for (int w = 0; w < kThreads / 64; ++w) s += part[w];
-        if (s) atomicAdd(sat, s);
-    }
-}
 
 struct Shape {
     int M;         // the decimation
@@ -189,7 +153,7 @@ __global__ __launch_bounds__(kThreads) void k_iq_firdec(const uint32_t *__restri
             }
         }
     }
-    add_block_count(cnt, sat);
+    add_block_count<kThreads>(cnt, sat);
 }
 
 Shape shape_of(int n_taps, int decim)
@@ -236,7 +200,7 @@ extern "C" int galk_firdec_table(const int16_t *h, int n_taps, int decim, uint32
 // The input samples one block filters at this decimation: (4096 / decim) & ~3 outputs.  Host only.
 extern "C" int galk_firdec_tile_inputs(int decim) { return ((kTileIn / decim) & ~3) * decim; }
 
-// n >= 1 input samples, n_out outputs from local index i0 on; arguments are checked by the caller (synth_api.cpp: gal_synth_iq_firdec),
+// n >= 1 input samples, n_out outputs from local index i0 on; arguments are checked by the caller (iq_api.cpp: gal_synth_iq_firdec),
 // which also keeps n below 2^41
 extern "C" hipError_t galk_launch_iq_firdec(const int16_t *in, int16_t *out, uint64_t n, uint64_t n_out, int i0, int n_taps, int decim,
                                             const uint32_t *table_dev, const uint32_t *hist_in, uint32_t *hist_out,

@@ -14,70 +14,20 @@
 //
 // Shape: a memory-bound stream of (n_parts + 1) x 4 bytes per complex sample, nothing reused -- as k_iq_pass (iq_pass.hip): 16-byte
 // loads and stores, 64-bit indices, plain loads (the parts have just been written by the synthesis: non-temporal loads lost there,
-// DESIGN.md section 10), the per-lane / per-wave / per-block saturation count of that file.  Nothing is divided per sample: the grid
+// DESIGN.md section 10), the per-lane / per-wave / per-block saturation count of iq_dev.h.  Nothing is divided per sample: the grid
 // is two-dimensional, blockIdx.y strides over the epochs and blockIdx.x over the 16-byte vectors that lie wholly inside the epoch, so
 // the epoch's gain row and the part pointers are uniform for the block (read through uniform addresses: scalar loads).  Four parts'
 // loads are issued before the first is used.  An epoch boundary need not be 16-byte aligned (gal_synth_create accepts any
 // samples_per_epoch >= 4): the up to three complex samples in front of an epoch's first whole vector and the up to three behind its
 // last one are taken one per lane by the epoch's first block, with 4-byte accesses.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
 #include <type_traits>
 
 #include "../../include/galsynth.h"
+#include "iq_dev.h"
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kMaxBlocks = 2048;  // 8 blocks of 4 waves per CU, the rest by the grid-stride loops
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-// a part's pointer comes out of a device table: say that it points to global memory (global_load instead of flat_load)
-template <class T>
-__device__ __forceinline__ const __attribute__((address_space(1))) T *as_global(const int16_t *p)
-{
-    return (const __attribute__((address_space(1))) T *)p;
-}
-
-// (w + 64) >> 7 clamped to int16; `sat` counts the values the clamp changes
-template <class acc_t>
-__device__ __forceinline__ uint32_t q7(acc_t w, uint32_t &sat)
-{
-    const acc_t v = (w + 64) >> 7;
-    const acc_t y = v < -32768 ? (acc_t)-32768 : v > 32767 ? (acc_t)32767 : v;
-    sat += (uint32_t)(y != v);
-    return (uint32_t)y & 0xffffu;
-}
-
-// the four complex samples of vector `a` times g, added to w[0..7] (I0, Q0, I1, Q1, ...)
-template <class acc_t>
-__device__ __forceinline__ void mac8(acc_t (&w)[8], v4i a, int g)
-{
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        w[2 * m] += (acc_t)g * (acc_t)(int16_t)a[m];
-        w[2 * m + 1] += (acc_t)g * (acc_t)(a[m] >> 16);
-    }
-}
-
-// per-lane counts -> one atomicAdd per block, only where the block saw a saturated value (iq_pass.hip: add_block_count)
-__device__ __forceinline__ void add_block_count(uint32_t cnt, unsigned long long *sat)
-{
-    __shared__ unsigned long long part[kThreads / 64];
-    unsigned long long c = cnt;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long s = 0;
-#pragma unroll
-        for (int w = 0; w < kThreads / 64; ++w) s += part[w];
-        if (s) atomicAdd(sat, s);
-    }
-}
 
 // parts[k]: n_epochs * N complex samples, 16-byte aligned, none overlapping `out`; gain[e * n_parts + k]: 0 .. 32767
 template <bool kWide>
@@ -123,13 +73,13 @@ __global__ __launch_bounds__(kThreads) void k_iq_wsum(const int16_t *const *__re
             }
         }
     }
-    add_block_count(cnt, sat);
+    add_block_count<kThreads>(cnt, sat);
 }
 
 }  // namespace
 
 // parts_dev: n_parts device pointers (a device table); gain_dev: [n_epochs][n_parts] int32 on the device; wide != 0: the int64 instance.
-// Arguments are checked by the caller (synth_api.cpp: gal_synth_iq_wsum).
+// Arguments are checked by the caller (iq_api.cpp: gal_synth_iq_wsum).
 extern "C" hipError_t galk_launch_iq_wsum(const int16_t *const *parts_dev, const int *gain_dev, int n_parts, int n_epochs, int samples_per_epoch,
                                           int wide, int16_t *out, unsigned long long *sat, hipStream_t st)
 {

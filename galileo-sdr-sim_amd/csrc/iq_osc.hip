@@ -3,7 +3,7 @@
 // sample with the global index N = first_sample + n; all phase arithmetic modulo 2^64, in units of 2^-64 cycles:
 //
 //   Phi(N) = P0 + N F + T(N) D + S Z(N),  T(N) = N (N - 1) / 2 (the even factor halved first),  Z(N) = sum of z(j) for N0 < j <= N
-//   z(j)   = the Q12 Gaussian of iq_pass.hip of word j & 3 of Philox4x32-10(counter = (B lo, B hi, stream, 1), key = seed), B = j >> 2
+//   z(j)   = the Q12 Gaussian of iq_dev.h of word j & 3 of Philox4x32-10(counter = (B lo, B hi, stream, 1), key = seed), B = j >> 2
 //   theta  = Phi >> 32;  t = theta + 2^21 (mod 2^32);  i = t >> 22;  e = ((t >> 10) & 4095) - 2048
 //   c0 = C[i], s0 = C[(i - 256) & 1023];  c = c0 - ((s0 e 101 + 2^25) >> 26);  s = s0 + ((c0 e 101 + 2^25) >> 26)
 //   yI = clamp16((xI c - xQ s + 2048) >> 12);  yQ = clamp16((xI s + xQ c + 2048) >> 12)
@@ -26,25 +26,19 @@
 //
 // The deterministic part costs no 64 x 64 multiply per sample: per tile (uniform, scalar unit) A = P0 + Nt F + T(Nt) D and the step
 // W = F + Nt D at the tile's first sample Nt; a lane at k = 4 lane starts from A + k W + T(k) D and steps Phi += w, w += D.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
 #include "../../include/galsynth.h"
+
 #define GAL_GAUSS_DEVICE_TABLE
-#include "gauss_table.inc"
 #define GAL_INTERF_DEVICE_TABLE
-#include "interf_table.inc"
+#include "iq_dev.h"
 
 namespace {
 
-// tests/osc_model.py repeats kTile and kMaxBlocks as TILE and MAX_BLOCKS: the GPU tests place their lengths at these edges
-constexpr int kThreads = 256;
+// tests/osc_model.py repeats kTile (4 x iq_dev.h's kThreads) and kMaxBlocks as TILE and MAX_BLOCKS: the GPU tests place their lengths at these edges
 constexpr int kTile = 4 * kThreads;
 constexpr int kMaxBlocks = 2048;  // 8 blocks of 4 waves per CU, the rest by the grid-stride loop over the tiles
 constexpr int kScanThreads = 1024;
 static_assert((long long)kTile * 25960 * 7 < (1ll << 31), "a tile's sum of z stays far inside an int32");
-
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 struct OscArgs {
     uint64_t n1;  // the global index of the call's first sample
@@ -53,59 +47,18 @@ struct OscArgs {
     uint32_t k0, k1, stream;
 };
 
-// Philox4x32-10 (Salmon et al., Random123) of the counter (b lo, b hi, stream, 1): iq_pass.hip's, with counter word 3 = 1
-__device__ __forceinline__ void philox(uint64_t b, const OscArgs &p, uint32_t (&o)[4])
-{
-    uint32_t c0 = (uint32_t)b, c1 = (uint32_t)(b >> 32), c2 = p.stream, c3 = 1, k0 = p.k0, k1 = p.k1;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1;
-        c3 = (uint32_t)p0;
-        c0 = n0;
-        c2 = n2;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    o[0] = c0;
-    o[1] = c1;
-    o[2] = c2;
-    o[3] = c3;
-}
-
-// uniform word -> z in Q12; tab = the packed table in LDS (iq_pass.hip: gauss_q12)
-__device__ __forceinline__ int gauss_q12(uint32_t u, const uint32_t *tab)
-{
-    const uint32_t w = u & 0x7fffffffu;
-    const int o = w ? __builtin_clz(w) - 1 : 31;
-    const uint32_t wn = w << o;
-    const uint32_t cell = tab[(o << 5) | ((wn >> 25) & 31u)];
-    const int a = (int)(cell & 0xffffu), d = (int)(cell >> 16), f = (int)((wn >> 17) & 255u);
-    const int mag = a - ((d * f + 128) >> 8);
-    return (u >> 31) ? -mag : mag;
-}
-
-__device__ __forceinline__ const uint32_t *load_gauss_table()
-{
-    __shared__ uint32_t tab[1024];
-    for (int k = threadIdx.x; k < 1024; k += kThreads) tab[k] = kGaussPacked[k];
-    __syncthreads();
-    return tab;
-}
-
 // the z of the samples 4 v .. 4 v + 3 of a call of n samples; 0 for a sample behind the call's end and for the sample N0
 __device__ __forceinline__ void lane_z(const OscArgs &p, uint64_t v, uint64_t n, const uint32_t *gt, int (&z)[4])
 {
     const uint64_t j0 = p.n1 + 4 * v;
     const uint32_t ph = (uint32_t)p.n1 & 3u;  // (uniform) where in its Philox block the lane's first sample lies
     uint32_t a[4], u[4];
-    philox(j0 >> 2, p, a);
+    philox(j0 >> 2, p.k0, p.k1, p.stream, 1u, a);
     if (ph == 0) {
         u[0] = a[0], u[1] = a[1], u[2] = a[2], u[3] = a[3];
     } else {
         uint32_t b[4];
-        philox((j0 >> 2) + 1, p, b);
+        philox((j0 >> 2) + 1, p.k0, p.k1, p.stream, 1u, b);
         if (ph == 1) {
             u[0] = a[1], u[1] = a[2], u[2] = a[3], u[3] = b[0];
         } else if (ph == 2) {
@@ -164,8 +117,6 @@ __global__ __launch_bounds__(kScanThreads) void k_osc_scan(const int *__restrict
     if (threadIdx.x == kScanThreads - 1) *st_out = run;  // (the last lane's tiles end at nt, or it has none: everything in front of it)
 }
 
-__device__ __forceinline__ int clamp16(int v) { return min(max(v, -32768), 32767); }
-
 // the complex sample x (I in the low half) turned by the phase Phi; `sat` counts the samples a clamp changes
 __device__ __forceinline__ uint32_t rotate(int x, uint64_t Phi, const int16_t *cosl, uint32_t &sat)
 {
@@ -184,34 +135,14 @@ __device__ __forceinline__ uint32_t rotate(int x, uint64_t Phi, const int16_t *c
 // N (N - 1) / 2 mod 2^64
 __device__ __forceinline__ uint64_t tri64(uint64_t N) { return (N & 1u) ? N * ((N - 1) >> 1) : (N >> 1) * (N - 1); }
 
-// per-lane counts -> one atomicAdd per block, only where the block saw a saturated sample (iq_pass.hip: add_block_count)
-__device__ __forceinline__ void add_block_count(uint32_t cnt, unsigned long long *sat)
-{
-    __shared__ unsigned long long part[kThreads / 64];
-    unsigned long long c = cnt;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long s = 0;
-#pragma unroll
-        for (int w = 0; w < kThreads / 64; ++w) s += part[w];
-        if (s) atomicAdd(sat, s);
-    }
-}
-
 // n >= 1 complex samples at `in` -> `out`, both 16-byte aligned, the same buffer or disjoint (a lane reads its vector before it writes
 // it and no other lane touches it); pre: k_osc_scan's word per tile (kNoise only)
 template <bool kNoise>
 __global__ __launch_bounds__(kThreads) void k_iq_osc(const int16_t *in, int16_t *out, uint64_t n, OscArgs p, const long long *__restrict__ pre,
                                                      unsigned long long *sat)
 {
-    __shared__ uint32_t cw[512];
+    const int16_t *cosl = load_cos_table();
     __shared__ int wtot[2][kThreads / 64];
-    for (int k = threadIdx.x; k < 512; k += kThreads) cw[k] = kInterfCosPairs[k];
-    __syncthreads();
-    const int16_t *cosl = (const int16_t *)cw;
     const uint32_t *gt = nullptr;
     if constexpr (kNoise) gt = load_gauss_table();
     const uint64_t nt = (n + kTile - 1) / kTile, nfull = n >> 2;
@@ -274,7 +205,7 @@ __global__ __launch_bounds__(kThreads) void k_iq_osc(const int16_t *in, int16_t 
             }
         }
     }
-    add_block_count(cnt, sat);
+    add_block_count<kThreads>(cnt, sat);
 }
 
 }  // namespace
@@ -288,7 +219,7 @@ extern "C" uint64_t galk_osc_scratch_bytes(uint64_t n)
 
 // n >= 1 samples (< 2^41) whose first has the global index first_sample; n0 = N0 of the definition; state_in / state_out: one 64-bit
 // word each, scratch: galk_osc_scratch_bytes, 8-byte aligned -- none of the three is touched where p->s == 0.  Arguments are checked
-// by the caller (synth_api.cpp: gal_synth_iq_osc).
+// by the caller (iq_api.cpp: gal_synth_iq_osc).
 extern "C" hipError_t galk_launch_iq_osc(const int16_t *in, int16_t *out, uint64_t n, uint64_t first_sample, uint64_t n0, const gal_iq_osc_t *p,
                                          const long long *state_in, long long *state_out, void *scratch, unsigned long long *sat, hipStream_t st)
 {

@@ -45,8 +45,6 @@
 //
 // This is a separate launch behind gal_synth_finish, never fused into the synthesis kernels: k_repair_g and the accumulating
 // exact-replay launches rewrite int16 output after k_synth_g has run, and gal_synth_finish may synthesise the batch again.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <string.h>
 
 #include <type_traits>
@@ -54,16 +52,12 @@
 #include "../../include/galsynth.h"
 
 #define GAL_GAUSS_DEVICE_TABLE
-#include "gauss_table.inc"
 #define GAL_INTERF_DEVICE_TABLE
-#include "interf_table.inc"
+#include "iq_dev.h"
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kMaxBlocks = 2048;  // 8 blocks of 4 waves per CU, the rest by the grid-stride loop
-
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 struct NoiseArgs {
     uint64_t j0;      // 2 first_sample: the global index of the call's first value
@@ -93,47 +87,6 @@ struct Lane {  // one source as one lane sees it, at the sample the lane handles
 };
 
 // ---- noise ---------------------------------------------------------------------------------------------------------------------
-// Philox4x32-10 (Salmon et al., Random123) of the counter (b lo, b hi, stream, 0)
-__device__ __forceinline__ void philox(uint64_t b, const NoiseArgs &p, uint32_t (&o)[4])
-{
-    uint32_t c0 = (uint32_t)b, c1 = (uint32_t)(b >> 32), c2 = p.stream, c3 = 0, k0 = p.k0, k1 = p.k1;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1;
-        c3 = (uint32_t)p0;
-        c0 = n0;
-        c2 = n2;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    o[0] = c0;
-    o[1] = c1;
-    o[2] = c2;
-    o[3] = c3;
-}
-
-// uniform word -> z in Q12; tab = the packed table in LDS
-__device__ __forceinline__ int gauss_q12(uint32_t u, const uint32_t *tab)
-{
-    const uint32_t w = u & 0x7fffffffu;
-    const int o = w ? __builtin_clz(w) - 1 : 31;  // leading zeros of w as a 31-bit number
-    const uint32_t wn = w << o;
-    const uint32_t cell = tab[(o << 5) | ((wn >> 25) & 31u)];
-    const int a = (int)(cell & 0xffffu), d = (int)(cell >> 16), f = (int)((wn >> 17) & 255u);
-    const int mag = a - ((d * f + 128) >> 8);
-    return (u >> 31) ? -mag : mag;
-}
-
-__device__ __forceinline__ const uint32_t *load_gauss_table()
-{
-    __shared__ uint32_t tab[1024];
-    for (int k = threadIdx.x; k < 1024; k += kThreads) tab[k] = kGaussPacked[k];
-    __syncthreads();
-    return tab;
-}
-
 // ---- sources -------------------------------------------------------------------------------------------------------------------
 // m (m - 1) / 2 mod 2^32 (the product is even and below 2^64: halve the even factor first)
 __device__ __forceinline__ uint32_t tri(uint32_t m) { return (m & 1u) ? m * ((m - 1u) >> 1) : (m >> 1) * (m - 1u); }
@@ -212,14 +165,6 @@ __device__ __forceinline__ void sources(const InterfArgs &p, Lane (&L)[GAL_INTER
         }
 }
 
-__device__ __forceinline__ const int16_t *load_cos_table()
-{
-    __shared__ uint32_t cw[512];
-    for (int k = threadIdx.x; k < 512; k += kThreads) cw[k] = kInterfCosPairs[k];
-    __syncthreads();
-    return (const int16_t *)cw;
-}
-
 // ---- the mix -------------------------------------------------------------------------------------------------------------------
 // what every mix of one kernel instance needs; ip and L are empty without sources, gt / ct unset where the instance has no table
 template <bool kSrc>
@@ -261,11 +206,11 @@ __device__ __forceinline__ void mix8(v4i a, uint64_t i, Mixer<kSrc> &m, int (&v)
     if constexpr (kMode != 0) {
         const uint64_t b = (m.np.j0 >> 2) + 2 * i;  // the block of the vector's first value (mode 2: from its word 2 on)
         uint32_t b0[4], b1[4];
-        philox(b, m.np, b0);
-        philox(b + 1, m.np, b1);
+        philox(b, m.np.k0, m.np.k1, m.np.stream, 0u, b0);
+        philox(b + 1, m.np.k0, m.np.k1, m.np.stream, 0u, b1);
         if constexpr (kMode == 2) {
             uint32_t b2[4];
-            philox(b + 2, m.np, b2);
+            philox(b + 2, m.np.k0, m.np.k1, m.np.stream, 0u, b2);
             u[0] = b0[2], u[1] = b0[3], u[2] = b1[0], u[3] = b1[1], u[4] = b1[2], u[5] = b1[3], u[6] = b2[0], u[7] = b2[1];
         } else {
             u[0] = b0[0], u[1] = b0[1], u[2] = b0[2], u[3] = b0[3], u[4] = b1[0], u[5] = b1[1], u[6] = b1[2], u[7] = b1[3];
@@ -281,29 +226,13 @@ __device__ __forceinline__ void mix2(int xI, int xQ, uint64_t j, Mixer<kSrc> &m,
 {
     uint32_t o[4] = {};
     const uint64_t J = m.np.j0 + j;
-    if constexpr (kMode != 0) philox(J >> 2, m.np, o);
+    if constexpr (kMode != 0) philox(J >> 2, m.np.k0, m.np.k1, m.np.stream, 0u, o);
     const bool hi = (J & 2) != 0;
     mix<kMode, kSrc>(xI, xQ, hi ? o[2] : o[0], hi ? o[3] : o[1], m, vI, vQ);
 }
 
 // ---- formats -------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int clamp16(int v) { return min(max(v, -32768), 32767); }
-
-// v = a mixed value before the clamp to int16; `sat` counts the values either clamp changes
-__device__ __forceinline__ uint32_t f16(int v, uint32_t &sat)
-{
-    const int y = clamp16(v);
-    sat += (uint32_t)(y != v);
-    return (uint32_t)y & 0xffffu;
-}
-
-__device__ __forceinline__ uint32_t f8(int v, int s, int r, uint32_t &sat)
-{
-    const int y = clamp16(v), q = (y + r) >> s;
-    sat += (uint32_t)((y != v) | (q < -127) | (q > 127));
-    return (uint32_t)(min(max(q, -127), 127)) & 0xffu;
-}
-
+// f16 and f8 of a mixed value before the clamp to int16: iq_dev.h
 __device__ __forceinline__ uint32_t f1(int v, uint32_t &sat)
 {
     sat += (uint32_t)((v < -32768) | (v > 32767));
@@ -380,23 +309,6 @@ struct FmtBit {
     }
 };
 
-// per-lane counts -> one atomicAdd per block (only where the block saw a saturated value)
-__device__ __forceinline__ void add_block_count(uint32_t cnt, unsigned long long *sat)
-{
-    __shared__ unsigned long long part[kThreads / 64];
-    unsigned long long c = cnt;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long s = 0;
-#pragma unroll
-        for (int w = 0; w < kThreads / 64; ++w) s += part[w];
-        if (s) atomicAdd(sat, s);
-    }
-}
-
 // n_val (even) int16 values at `in` -> the same number of values in the format at `out`, both 16-byte aligned; s = the ibyte shift
 template <class Fmt, int kMode, bool kSrc>
 __global__ __launch_bounds__(kThreads) void k_iq_pass(typename Fmt::in_t in, typename Fmt::out_t out, uint64_t n_val, int s, NoiseArgs np,
@@ -437,7 +349,7 @@ __global__ __launch_bounds__(kThreads) void k_iq_pass(typename Fmt::in_t in, typ
             Fmt::tail(out, j, n_val, vI, vQ, s, r, cnt, acc);
         }
     }
-    if constexpr (kMixed || Fmt::kPlainCounts) add_block_count(cnt, sat);
+    if constexpr (kMixed || Fmt::kPlainCounts) add_block_count<kThreads>(cnt, sat);
 }
 
 struct PassCall {
@@ -477,7 +389,7 @@ extern "C" const int16_t *gal_tables_cos1024(void) { return kInterfCos; }
 
 // format 0 (ishort), 1 (ibyte) or 2 (ibit) of n_val int16 values with the noise floor (noise may be null: none) and n_src sources
 // mixed in; with neither it is the plain conversion (not of format 0: that is a copy).  Arguments are checked by the caller
-// (synth_api.cpp: iq_pass).
+// (iq_api.cpp: iq_pass).
 extern "C" hipError_t galk_launch_iq_pass(int format, const int16_t *in, uint64_t n_val, uint64_t first_sample, const gal_iq_noise_t *noise,
                                           const gal_iq_interf_t *src, int n_src, int shift, void *out, unsigned long long *sat, hipStream_t st)
 {

@@ -1,4 +1,5 @@
-// synth_api.cpp -- C ABI (include/galsynth.h) over the gfx950 kernels in synth_kernels.hip.
+// synth_api.cpp -- C ABI (include/galsynth.h) over the gfx950 kernels in synth_kernels.hip and synth_group.hip: the handle, plan,
+// execute and finish (the passes over the finished stream are iq_api.cpp's; both share synth_handle.h).
 // Host-side plumbing only: validation, HBM arena, kernel sequencing.  There is deliberately no CPU
 // implementation behind these entry points: without a usable GPU they fail with GAL_E_DEVICE.
 #include <hip/hip_runtime.h>
@@ -17,11 +18,9 @@
 #include <time.h>
 #include <vector>
 
-#define GAL_SYNTH_NO_SIZED_MACROS 1
 #include "nco_walk.h"
-#include "synth_dev.h"
+#include "synth_handle.h"
 #include "e1_tables.inc"
-#include "gain_q7.h"
 
 // Smallest distance between two of the 15 thresholds T_u = 1 - frac(u s) of the 16-sample hold pattern (k_synth,
 // rw_phase_a): the kernel's bin table (128 bins of the group-start fraction) decides a lane only if its bin holds ONE
@@ -93,34 +92,9 @@ int galk_scanm_blocks(int legs);
 size_t galk_scanm_bytes(int S, int legs);
 int galk_launch_synth(const DevPlan *P, const DevPlan *Pd, int nch, int accumulate, const uint8_t *act,
                       const int *nact, uint32_t *iq, int e0, int ne, hipStream_t st);
-hipError_t galk_launch_iq_pass(int format, const int16_t *in, uint64_t n_val, uint64_t first_sample, const gal_iq_noise_t *noise,
-                               const gal_iq_interf_t *src, int n_src, int shift, void *out, unsigned long long *sat, hipStream_t st);
-hipError_t galk_launch_iq_fir(const int16_t *in, int16_t *out, uint64_t n, const uint32_t *table_dev, int n_trips, int hs, const uint32_t *hist_in,
-                              uint32_t *hist_out, unsigned long long *sat, hipStream_t st);
-void galk_fir_table(const int16_t *h, int n_taps, uint32_t *table, int *n_trips, int *hs);
-hipError_t galk_launch_iq_firdec(const int16_t *in, int16_t *out, uint64_t n, uint64_t n_out, int i0, int n_taps, int decim,
-                                 const uint32_t *table_dev, const uint32_t *hist_in, uint32_t *hist_out, unsigned long long *sat, hipStream_t st);
-int galk_firdec_table(const int16_t *h, int n_taps, int decim, uint32_t *table, int *trips);
-hipError_t galk_launch_iq_agc(const int16_t *in, uint64_t n, uint32_t off0, int format, int param, const gal_iq_agc_t *p,
-                              const unsigned long long *state_in, unsigned long long *state_out, void *scratch, void *out, uint32_t *gains_out,
-                              unsigned long long *sat, hipStream_t st);
-uint64_t galk_agc_scratch_bytes(uint64_t n, uint32_t off0, uint32_t block_len);
-hipError_t galk_launch_iq_osc(const int16_t *in, int16_t *out, uint64_t n, uint64_t first_sample, uint64_t n0, const gal_iq_osc_t *p,
-                              const long long *state_in, long long *state_out, void *scratch, unsigned long long *sat, hipStream_t st);
-uint64_t galk_osc_scratch_bytes(uint64_t n);
-hipError_t galk_launch_iq_echo(const int16_t *const *parts_dev, const int16_t *const *hist_in_dev, int16_t *const *hist_out_dev, const int *gain_dev,
-                               const void *rows_dev, const int *part_of_dev, int n_parts, int n_echo, int n_epochs, int samples_per_epoch, int wide,
-                               int16_t *out, unsigned long long *sat, hipStream_t st);
-hipError_t galk_launch_iq_wsum(const int16_t *const *parts_dev, const int *gain_dev, int n_parts, int n_epochs, int samples_per_epoch, int wide,
-                               int16_t *out, unsigned long long *sat, hipStream_t st);
-hipError_t galk_launch_corr(int format, const void *buf, uint64_t n_eff, uint64_t code_ph0, uint64_t code_dph, uint32_t carr_ph0,
-                            uint32_t carr_step0, uint32_t dopp_step, int delay0, int delay_step, int n_delay, int n_dopp, int max_periods,
-                            const uint32_t *lut_dev, const uint32_t *code_dev, long long *out, hipStream_t st);
 }
 
-namespace {
-
-thread_local char g_err[512] = "";
+static thread_local char g_err[512] = "";  // gal_synth_last_error
 
 int fail(int code, const char *fmt, ...)
 {
@@ -131,13 +105,7 @@ int fail(int code, const char *fmt, ...)
     return code;
 }
 
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t err__ = (expr);                                                                 \
-        if (err__ != hipSuccess)                                                                   \
-            return fail(GAL_E_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(err__),   \
-                        __FILE__, __LINE__);                                                       \
-    } while (0)
+namespace {
 
 int16_t g_cos[512], g_sin[512];
 bool g_tables_ready = false;
@@ -171,13 +139,6 @@ constexpr int kVerifyRotation = 8;  // GAL_CFG_VERIFY_SAMPLED: k_verify re-walks
                                     // (profiles/r05f_verify_ab.log): none 0.974 / 1.230 / 0.842 ms; every leg 1.010 / 1.297 / 0.890; every 4th
                                     // 0.985 / 1.258 / 0.865; 8th 0.979 / 1.238 / 0.846; 16th 0.976 / 1.234 / 0.845
 constexpr int kSmallPlanEpochs = 32;  // plans up to here are latency-bound calls (see commit_staged: enqueued passes)
-constexpr int kDefaultPasses = 3;   // carrier passes enqueued up front for a NEW plan: walk + stitch (which translates on the spot), two spare --
-                                    // no-op launches in front of k_synth when the chain is complete after one, as it is for four fresh
-                                    // scenarios in five (tools/fresh_plan_probe.py, 32 seeds of M-SYN12: 26 x 1 pass, 4 x 2, 2 x 3; a batch that
-                                    // needs more than were enqueued pays gal_synth_finish's iteration and a SECOND synthesis, 3.4 ms
-                                    // instead of 1.9).  A plan that is executed again enqueues what its last execute needed (the chain
-                                    // is deterministic); rounds 3-5 kept that count per HANDLE, right for a bench that re-executes one
-                                    // resident plan and wrong for a caller with new parameters every batch
 }  // namespace
 
 // First guesses of the speculative carrier walk (synth_kernels.hip: k_walk_carr, first pass): per slot and epoch the IDEAL-arithmetic
@@ -245,172 +206,6 @@ struct GuessChain {
     }
 };
 
-// What a plan produces on the host.  gal_synth_plan[_async] fills one of these (and the pinned staging buffer) WITHOUT touching what
-// the batch in flight still needs; commit_staged() makes it the handle's plan and enqueues its upload -- at once if nothing is in
-// flight, else at the next gal_synth_execute (behind the gal_synth_finish of the batch in flight): plan(k+1) under execute(k) on ONE
-// handle (round 6).  Until the commit the device pointers of P are OFFSETS into the arena.
-struct StagedPlan {
-    DevPlan P{};
-    int n_groups = 0, all_first = 0, all_count = 0, n_exact_records = 0, nact_max = 0;
-    std::vector<int> group_nch, group_kind;
-    std::vector<int64_t> act_prefix;
-    size_t o_plan = 0, o_act = 0, o_nact = 0, up_bytes = 0, total = 0;
-    size_t o_cpx = 0, o_ancw = 0, zero_end = 0, o_clmw = 0, clmw_bytes = 0, o_scanm = 0, scanm_clear = 0;
-    int R = 0, nchunks = 0;
-    float ms_plan = 0.0f;
-};
-
-struct gal_synth {
-    StagedPlan staged;            // the plan made while a batch was in flight (or being committed)
-    bool staged_pending = false;  // ... waits for its commit
-    gal_synth_cfg_t cfg{};
-    int device = 0;
-    int n_cu = 256;  // compute units of the device (MI355X: 256)
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    hipStream_t aux_stream = nullptr;  // code-chain walk + page resolution run beside the carrier passes
-    // the walker chain runs on the handle's own HIGH-PRIORITY stream: k_synth fills every SIMD's register file,
-    // so walker workgroups of the next batch only get on when a synthesis wave retires -- with priority they
-    // are first in line then, instead of queueing behind the pending synthesis workgroups of other handles
-    hipStream_t walk_stream = nullptr;
-    hipEvent_t ev_walk = nullptr;
-    hipEvent_t ev_ver = nullptr;  // k_verify done (k_synth_g batches)
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_prep = nullptr, ev_aux = nullptr;
-    hipEvent_t ev_upd = nullptr;  // the plan's upload and memsets are complete (what the walkers of its first execute wait for)
-
-    // tables in HBM
-    int *d_lut = nullptr;
-    uint32_t *d_str = nullptr;   // [50][512] half-chip streams (2 bits per BOC half chip)
-    DevPlan *d_plan = nullptr;   // device copy of P, inside the arena (the hot kernel reads rarely used fields through it)
-    char *h_up = nullptr;        // pinned staging buffer of plan(): the arena's upload region, byte for byte
-    size_t h_up_bytes = 0;
-
-    // arena for the planned batch
-    void *arena = nullptr;
-    size_t arena_bytes = 0;
-    DevPlan P{};   // the planned batch
-    DevPlan Pw{};  // what the walker kernels of the batch in flight see: P cut to the epochs [0, end of the executed range)
-    bool planned = false;
-    bool executed = false;
-    bool in_flight = false;  // execute() enqueued, finish() not yet called
-    int n_groups = 0;  // channel groups (each <= kKernelMaxChan) -> synth launches per execute
-    std::vector<int> group_nch;
-    std::vector<int> group_kind;     // 1: k_synth_g, 0: k_synth (k_synth_g batches: the records that are not fit for it, accumulating)
-    int all_first = 0, all_count = 0;  // k_synth_g batches with records of kind 0: the groups that hold ALL records (list-overflow path)
-    int n_exact_records = 0;         // records of the batch that take the exact-replay launch behind k_synth_g
-    uint8_t *d_act = nullptr;  // [groups][E][kActRow]
-    int *d_nact = nullptr;     // [groups][E]
-    int nact_max = 0;
-    uint32_t *last_iq = nullptr;
-    int range_e0 = 0, range_ne = 0;  // epoch range of the last execute
-    void *own_iq = nullptr;
-    size_t own_iq_bytes = 0;
-    void *own_pin = nullptr;  // gal_synth_run_host, small batches: pinned landing buffer of the device->host copy
-    size_t own_pin_bytes = 0;
-    int *h_ctr = nullptr;  // pinned: [CTR_COUNT] counters, [CTR_COUNT] spare, then the completion flag (k_publish)
-    uint32_t *h_flag = nullptr;  // = (uint32_t *)(h_ctr + 2 * CTR_COUNT): sequence number of the last batch whose record is complete
-    uint32_t seq = 0;            // sequence number of the batch in flight
-    uint32_t scan_tag = 0;       // tag of the last stitch launched (k_scanm's look-back records carry it)
-    size_t scanm_off = ~(size_t)0, scanm_clear = 0;  // where the stitch's records lie in the arena, as last cleared
-    int64_t legs_walked = 0, legs_translated = 0, n_fallbacks = 0;  // last finish(): carrier legs walked / translated
-    std::vector<int64_t> act_prefix;  // [E + 1] active records in the epochs before e (a first walker pass walks W legs of each)
-    int64_t first_pass_legs = 0;      // legs walked by the first passes of the batch in flight (every active leg; not counted on the device)
-    gal_chan_state_t *h_state = nullptr;  // pinned [S]
-    bool state_fetched = false;           // h_state holds the state of the batch in flight
-    gal_synth_stats_t stats{};
-    int enq_passes = kDefaultPasses;  // carrier passes the next execute enqueues (see kDefaultPasses)
-    int small_need = 2;               // ... what the handle's last plan of <= kSmallPlanEpochs epochs needed (its first: one spare)
-    // k_synth's resampled-window body: per slot the last code step whose hold-pattern thresholds were examined and
-    // their smallest distance (rw_threshold_gap) -- reused only for the identical step
-    std::vector<double> rw_s0, rw_g0, rw_e0;
-    // ... and, since round 6, for every step within rw_rad of it: the thresholds T_u = 1 - frac(u s) move by u |ds| <= 15 |ds| and no
-    // u s crosses an integer while 15 |ds| stays below the distance of every T_u to 0 and 1 (rw_e0), so inside
-    // |ds| < min((e0 - min) / 15, (g0 - min) / 14) both gates keep their verdict.  A Doppler moves the step of the reference geometry by
-    // 2e-6 of itself, the radius is 6e-4: one evaluation per slot instead of one per record (14 388 x 0.3 us of a 1199-epoch plan)
-    std::vector<double> rw_rad;
-    bool host_only = false;       // GAL_TEST_HOOKS, gal_hooks_plan_host_ms: gal_synth_plan's host work without a device (timing on CPU)
-    hipEvent_t ev_up0 = nullptr, ev_up1 = nullptr;  // around the upload of the last plan (timed: stats.ms_h2d)
-    bool upload_pending = false;  // gal_synth_plan_async: the upload is enqueued, nobody has waited for it yet
-    bool upload_timed = false;
-    bool upload_unordered = false;  // ... and no execute has put its walkers behind it yet
-    float ms_plan = 0.0f;         // host time of the last gal_synth_plan (validation, lists, staging; without the wait for the upload)
-    double prev_wait_us = 0.0;  // how long the last gal_synth_finish waited for its batch (paces the next one's naps)
-    int g_holdoff = 0;  // batches for which k_synth_g is not used although it could be: its last batch listed too many groups
-    unsigned long long *d_iq_sat = nullptr;  // gal_synth_iq_convert: saturated ibyte values (device; made at the first conversion)
-    uint32_t *d_corr_tab = nullptr;  // gal_synth_correlate: [512] carrier table + [50][512] replica bits (device; made at the first call)
-    // gal_synth_iq_wsum: the part pointers ([GAL_ENGINE_MAX_CHAN]) and the gains ([n_epochs][n_parts] int32) of the last call, pinned
-    // on the host and on the device; ev_gain = that call's kernel is done (both are free again)
-    char *h_gain = nullptr;
-    char *d_gain = nullptr;
-    size_t gain_bytes = 0;
-    hipEvent_t ev_gain = nullptr;
-    bool gain_pending = false;
-    void *own_parts = nullptr;  // gal_synth_run_gains: the streams of the slot groups, one behind the other
-    int gain_runs = 0;          // ... synthesis runs its last call took (gal_synth_gain_runs)
-    size_t own_parts_bytes = 0;
-    // gal_synth_iq_mpath (iq_echo.hip): d_mp_hist = GAL_ECHO_LINES history lines x 2 buffers of GAL_ECHO_MAX_DELAY complex samples (a call
-    // reads buffer mp_cur[id] of a line it names and writes the other); h_mp / d_mp = the table of the last call (part, history-in and
-    // history-out pointers, gains, echo rows, part indices), pinned on the host and on the device; ev_mp = that call's kernels are done
-    uint32_t *d_mp_hist = nullptr;
-    uint8_t mp_cur[GAL_ECHO_LINES] = {};
-    char *h_mp = nullptr;
-    char *d_mp = nullptr;
-    size_t mp_bytes = 0;
-    hipEvent_t ev_mp = nullptr;
-    bool mp_pending = false;
-    // gal_synth_fir_set / gal_synth_iq_fir (iq_fir.hip): the tap-pair table and the two history buffers of kFirHist complex samples, one
-    // device block; h_fir = the pinned copy of the table the upload reads; ev_fir = the last filter kernel of the handle is done
-    uint32_t *d_fir = nullptr;
-    uint32_t *h_fir = nullptr;
-    int fir_taps = 0, fir_trips = 0, fir_hs = 0;  // fir_taps 0: no filter set
-    int fir_cur = 0;                              // the history buffer the next call reads (it writes the other)
-    hipEvent_t ev_fir = nullptr;
-    bool fir_pending = false;
-    // gal_synth_firdec_set / gal_synth_iq_firdec (iq_firdec.hip): the same for the decimator, a slot of its own; fd_phase = the
-    // global index of the next input sample modulo fd_decim
-    uint32_t *d_fd = nullptr;
-    uint32_t *h_fd = nullptr;
-    int fd_taps = 0, fd_decim = 0, fd_phase = 0;  // fd_taps 0: no decimator set
-    int fd_cur = 0;
-    hipEvent_t ev_fd = nullptr;
-    bool fd_pending = false;
-    // gal_synth_agc_set / gal_synth_iq_agc (iq_agc.hip): d_agc = the two state buffers of kAgcState words (a call reads agc_cur and
-    // writes the other); h_agc = the pinned copy of the first state the upload reads; d_agc_scr = the block sums and gains of the last
-    // call, grown on demand; agc_pos = the global index of the next sample; ev_agc = the last AGC kernel of the handle is done
-    unsigned long long *d_agc = nullptr;
-    unsigned long long *h_agc = nullptr;
-    void *d_agc_scr = nullptr;
-    size_t agc_scr_bytes = 0;
-    gal_iq_agc_t agc = {};
-    bool agc_on = false;
-    uint64_t agc_pos = 0;
-    int agc_cur = 0;
-    hipEvent_t ev_agc = nullptr;
-    bool agc_pending = false;
-    // gal_synth_osc_set / gal_synth_iq_osc (iq_osc.hip): d_osc = the two 64-bit words of the running sum Z (a call with s > 0 reads
-    // osc_cur and writes the other); d_osc_scr = the tile sums and their scan of the last call, grown on demand; osc_n0 = N0, osc_pos =
-    // the global index of the next sample; ev_osc = the last oscillator kernel of the handle is done
-    long long *d_osc = nullptr;
-    void *d_osc_scr = nullptr;
-    size_t osc_scr_bytes = 0;
-    gal_iq_osc_t osc = {};
-    bool osc_on = false;
-    uint64_t osc_n0 = 0, osc_pos = 0;
-    int osc_cur = 0;
-    hipEvent_t ev_osc = nullptr;
-    bool osc_pending = false;
-};
-
-// The stream the handle works on: the caller's (gal_synth_set_stream), or one of its own, made at first need.
-static hipStream_t handle_stream(gal_synth *h)
-{
-    if (!h->stream) {
-        if (!h->own_stream && hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) return nullptr;
-        h->stream = h->own_stream;
-    }
-    return h->stream;
-}
 
 extern "C" {
 
@@ -627,26 +422,12 @@ int gal_synth_destroy(gal_synth_t *h)
     if (h->d_iq_sat) hipFree(h->d_iq_sat);
     if (h->d_corr_tab) hipFree(h->d_corr_tab);
     if (h->own_parts) hipFree(h->own_parts);
-    if (h->d_gain) hipFree(h->d_gain);
-    if (h->h_gain) hipHostFree(h->h_gain);
-    if (h->ev_gain) hipEventDestroy(h->ev_gain);
-    if (h->d_mp_hist) hipFree(h->d_mp_hist);
-    if (h->d_mp) hipFree(h->d_mp);
-    if (h->h_mp) hipHostFree(h->h_mp);
-    if (h->ev_mp) hipEventDestroy(h->ev_mp);
-    if (h->d_fir) hipFree(h->d_fir);
-    if (h->h_fir) hipHostFree(h->h_fir);
-    if (h->ev_fir) hipEventDestroy(h->ev_fir);
-    if (h->d_fd) hipFree(h->d_fd);
-    if (h->h_fd) hipHostFree(h->h_fd);
-    if (h->ev_fd) hipEventDestroy(h->ev_fd);
-    if (h->d_agc) hipFree(h->d_agc);
-    if (h->h_agc) hipHostFree(h->h_agc);
-    if (h->d_agc_scr) hipFree(h->d_agc_scr);
-    if (h->ev_agc) hipEventDestroy(h->ev_agc);
-    if (h->d_osc) hipFree(h->d_osc);
-    if (h->d_osc_scr) hipFree(h->d_osc_scr);
-    if (h->ev_osc) hipEventDestroy(h->ev_osc);
+    h->gain.release();
+    h->mp.release();
+    h->fir.release();
+    h->fd.release();
+    h->agc.release();
+    h->osc.release();
     if (h->d_lut) hipFree(h->d_lut);
     if (h->d_str) hipFree(h->d_str);
     if (h->h_up) hipHostFree(h->h_up);
@@ -683,7 +464,6 @@ size_t gal_synth_output_bytes(const gal_synth_t *h)
     return (size_t)h->P.E * (size_t)h->P.N * 4u;
 }
 
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // The staged plan becomes the handle's: arena (grown if need be), device pointers, the ONE host->device copy out of the pinned
 // staging buffer, the memsets of what must start clean.  Everything the device needs is laid out in the staging buffer exactly as
@@ -1839,1353 +1619,6 @@ int gal_synth_run_host_n(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t
     if (h->stats.synth_runs != 1) HIP_TRY(hipMemcpyAsync(h->own_pin, h->own_iq, bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     memcpy(iq_host, h->own_pin, bytes);
-    return GAL_OK;
-}
-
-// ---- output formats, noise floor, interference sources (iq_pass.hip) ---------------------------------------------------------------
-size_t gal_synth_iq_bytes(int32_t format, size_t n_samples)
-{
-    switch (format) {
-    case GAL_IQ_ISHORT: return 4 * n_samples;
-    case GAL_IQ_IBYTE: return 2 * n_samples;
-    case GAL_IQ_IBIT: return (n_samples + 3) / 4;
-    default: return 0;
-    }
-}
-
-// the handle's saturation counter, made (and zeroed on `st`) at the first pass that may count
-static int ensure_sat_counter(gal_synth *h, hipStream_t st)
-{
-    if (h->d_iq_sat) return GAL_OK;
-    unsigned long long *c = nullptr;
-    HIP_TRY(hipMalloc((void **)&c, sizeof(unsigned long long)));
-    const hipError_t err = hipMemsetAsync(c, 0, sizeof(unsigned long long), st);
-    if (err != hipSuccess) {  // (never keep a counter that was not zeroed)
-        hipFree(c);
-        return fail(GAL_E_DEVICE, "hipMemsetAsync of the saturation counter failed: %s", hipGetErrorString(err));
-    }
-    h->d_iq_sat = c;
-    return GAL_OK;
-}
-
-// The one check path of the three conversions below, `who` in the messages.  in_place: ishort may run with out_dev == iq_dev (every
-// lane rewrites the vector it has read); otherwise any overlap would race (ibyte: lane i writes where lane i / 2 reads), and the
-// kernels take both as __restrict__.
-static int iq_pass(const char *who, bool in_place, gal_synth_t *h, const int16_t *iq_dev, size_t n_samples, uint64_t first_sample,
-                   const gal_iq_noise_t *noise, const gal_iq_interf_t *interf, int32_t n_interf, int32_t format, int32_t shift, void *out_dev)
-{
-    if (!h) return fail(GAL_E_INVAL, "null handle");
-    gal_iq_interf_t src[GAL_INTERF_MAX];  // the caller's array is not looked at again
-    if (n_interf > 0) {
-        if (!interf) return fail(GAL_E_INVAL, "%s: null interf with n_interf %d", who, n_interf);
-        memcpy(src, interf, (size_t)n_interf * sizeof(gal_iq_interf_t));
-    }
-    for (int k = 0; k < n_interf; ++k) {
-        const gal_iq_interf_t &c = src[k];
-        if (c.amp_q4 > (1u << 20) || (c.sweep_len == 0 && c.df != 0) || c.pulse_on > c.pulse_period || c.reserved != 0)
-            return fail(GAL_E_INVAL, "%s: source %d: amp_q4 %u (0..2^20), df %d with sweep_len %u (0 without a sweep), "
-                        "pulse_on %u of pulse_period %u, reserved %u (0)", who, k, c.amp_q4, c.df, c.sweep_len, c.pulse_on, c.pulse_period, c.reserved);
-    }
-    if (format != GAL_IQ_ISHORT && format != GAL_IQ_IBYTE && format != GAL_IQ_IBIT)
-        return fail(GAL_E_INVAL, "%s: unknown format %d (GAL_IQ_ISHORT 0, GAL_IQ_IBYTE 1, GAL_IQ_IBIT 2)", who, format);
-    if (format == GAL_IQ_IBYTE ? (shift < 0 || shift > 15) : shift != 0)
-        return fail(GAL_E_INVAL, "%s: shift %d (0..15 for GAL_IQ_IBYTE, 0 otherwise)", who, shift);
-    if (noise && (noise->gain_q16 > (1u << 20) || noise->sigma_q4 > (1u << 20) || noise->reserved != 0))
-        return fail(GAL_E_INVAL, "%s: gain_q16 %u, sigma_q4 %u (both 0..2^20), reserved %u (0)", who, noise->gain_q16, noise->sigma_q4,
-                    noise->reserved);
-    if (first_sample >> 62) return fail(GAL_E_INVAL, "%s: first_sample must be below 2^62", who);
-    if (!iq_dev || !out_dev || ((uintptr_t)iq_dev & 15) || ((uintptr_t)out_dev & 15))
-        return fail(GAL_E_INVAL, "%s: device pointers must be non-null and 16-byte aligned", who);
-    if (n_samples == 0) return GAL_OK;
-    const char *x = (const char *)iq_dev, *y = x + 4 * n_samples;
-    if (!(in_place && format == GAL_IQ_ISHORT && (const void *)iq_dev == out_dev)) {
-        const char *o = (const char *)out_dev, *e = o + gal_synth_iq_bytes(format, n_samples);
-        if (x < e && o < y)
-            return fail(GAL_E_INVAL, "%s: input and output overlap%s", who, in_place ? " (only ishort exactly in place may)" : "");
-    }
-    if (h->in_flight && h->last_iq) {  // the batch in flight may still be synthesised again by gal_synth_finish
-        const char *a = (const char *)h->last_iq, *b = a + (size_t)h->range_ne * (size_t)h->P.N * 4;
-        if (x < b && a < y) return fail(GAL_E_STATE, "%s: input of the batch in flight (call gal_synth_finish first)", who);
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = handle_stream(h);
-    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
-    if (format == GAL_IQ_ISHORT && !noise && n_interf == 0) {  // nothing to mix: a copy
-        HIP_TRY(hipMemcpyAsync(out_dev, iq_dev, 4 * n_samples, hipMemcpyDeviceToDevice, st));
-        return GAL_OK;
-    }
-    const int rc = ensure_sat_counter(h, st);
-    if (rc) return rc;
-    HIP_TRY(galk_launch_iq_pass(format, iq_dev, 2 * (uint64_t)n_samples, first_sample, noise, src, n_interf, shift, out_dev, h->d_iq_sat, st));
-    return GAL_OK;
-}
-
-int gal_synth_iq_convert(gal_synth_t *h, const int16_t *iq_dev, size_t n_samples, int32_t format, int32_t shift, void *out_dev)
-{
-    return iq_pass("gal_synth_iq_convert", false, h, iq_dev, n_samples, 0, nullptr, nullptr, 0, format, shift, out_dev);
-}
-
-// ---- noise floor ---------------------------------------------------------------------------------------------------------------
-int gal_synth_iq_convert_noise(gal_synth_t *h, const int16_t *iq_dev, size_t n_samples, uint64_t first_sample, const gal_iq_noise_t *noise,
-                               int32_t format, int32_t shift, void *out_dev)
-{
-    if (!noise) return gal_synth_iq_convert(h, iq_dev, n_samples, format, shift, out_dev);
-    return iq_pass("gal_synth_iq_convert_noise", true, h, iq_dev, n_samples, first_sample, noise, nullptr, 0, format, shift, out_dev);
-}
-
-int gal_synth_noise_from_cn0(double cn0_dbhz, double sample_rate, double gain, gal_iq_noise_t *out)
-{
-    if (!out) return fail(GAL_E_INVAL, "gal_synth_noise_from_cn0: null argument");
-    if (!std::isfinite(cn0_dbhz) || !std::isfinite(sample_rate) || !std::isfinite(gain) || sample_rate <= 0.0 || gain < 0.0 || gain > 16.0)
-        return fail(GAL_E_INVAL, "gal_synth_noise_from_cn0: C/N0 %g dB-Hz, sample rate %g Hz (> 0), gain %g (0..16)", cn0_dbhz, sample_rate, gain);
-    // sigma of one rail in int16 LSB for a composite E1B + E1C signal of amplitude 250 per component (include/galsynth.h)
-    const double sigma_q4 = 16.0 * 250.0 * gain * sqrt(sample_rate / pow(10.0, cn0_dbhz / 10.0));
-    if (!(sigma_q4 <= 1048576.0))
-        return fail(GAL_E_INVAL, "gal_synth_noise_from_cn0: sigma %g LSB at %g dB-Hz is beyond the 65536 LSB sigma_q4 holds", sigma_q4 / 16.0, cn0_dbhz);
-    memset(out, 0, sizeof(*out));
-    out->gain_q16 = (uint32_t)llround(gain * 65536.0);
-    out->sigma_q4 = (uint32_t)llround(sigma_q4);
-    return GAL_OK;
-}
-
-// ---- interference sources ------------------------------------------------------------------------------------------------------
-int gal_synth_iq_convert_interf(gal_synth_t *h, const int16_t *iq_dev, size_t n_samples, uint64_t first_sample, const gal_iq_noise_t *noise,
-                                const gal_iq_interf_t *interf, int32_t n_interf, int32_t format, int32_t shift, void *out_dev)
-{
-    if (n_interf < 0 || n_interf > GAL_INTERF_MAX)
-        return fail(GAL_E_INVAL, "gal_synth_iq_convert_interf: n_interf %d (0..%d)", n_interf, GAL_INTERF_MAX);
-    if (n_interf == 0) return gal_synth_iq_convert_noise(h, iq_dev, n_samples, first_sample, noise, format, shift, out_dev);
-    return iq_pass("gal_synth_iq_convert_interf", true, h, iq_dev, n_samples, first_sample, noise, interf, n_interf, format, shift, out_dev);
-}
-
-int gal_synth_interf_make(double js_db, double gain, double sample_rate, double f_lo_hz, double f_hi_hz, double sweep_s, double pulse_period_s,
-                          double pulse_on_s, gal_iq_interf_t *out)
-{
-    if (!out) return fail(GAL_E_INVAL, "gal_synth_interf_make: null argument");
-    if (!std::isfinite(js_db) || !std::isfinite(gain) || !std::isfinite(sample_rate) || !std::isfinite(f_lo_hz) || !std::isfinite(sweep_s) ||
-        !std::isfinite(pulse_period_s) || !std::isfinite(pulse_on_s) || (sweep_s != 0.0 && !std::isfinite(f_hi_hz)))
-        return fail(GAL_E_INVAL, "gal_synth_interf_make: an argument is not finite");
-    if (sample_rate <= 0.0 || gain < 0.0 || sweep_s < 0.0 || pulse_period_s < 0.0 || pulse_on_s < 0.0)
-        return fail(GAL_E_INVAL, "gal_synth_interf_make: sample rate %g Hz (> 0), gain %g, sweep %g s, pulse %g of %g s (all >= 0)", sample_rate, gain,
-                    sweep_s, pulse_on_s, pulse_period_s);
-    // a tone A e^(j theta) has the power A^2, the composite signal of one satellite 2 (250 gain)^2 (include/galsynth.h)
-    const double amp_q4 = 16.0 * 250.0 * sqrt(2.0) * gain * pow(10.0, js_db / 20.0);
-    if (!(amp_q4 <= 1048576.0))
-        return fail(GAL_E_INVAL, "gal_synth_interf_make: amplitude %g LSB at J/S %g dB is beyond the 65536 LSB amp_q4 holds", amp_q4 / 16.0, js_db);
-    const double half = sample_rate / 2.0;
-    if (!(fabs(f_lo_hz) < half) || (sweep_s != 0.0 && !(fabs(f_hi_hz) < half)))
-        return fail(GAL_E_INVAL, "gal_synth_interf_make: frequencies %g, %g Hz must lie inside +-%g Hz", f_lo_hz, f_hi_hz, half);
-    const double len = sweep_s * sample_rate, period = pulse_period_s * sample_rate, on = pulse_on_s * sample_rate;
-    if (!(len < 4294967295.5) || !(period < 4294967295.5) || !(on < 4294967295.5))
-        return fail(GAL_E_INVAL, "gal_synth_interf_make: sweep %g, pulse period %g, pulse on %g samples do not fit 32 bits", len, period, on);
-    gal_iq_interf_t c;
-    memset(&c, 0, sizeof(c));
-    c.amp_q4 = (uint32_t)llround(amp_q4);
-    const long long f0 = llround(f_lo_hz / sample_rate * 4294967296.0);
-    long long df = 0;
-    if (sweep_s != 0.0) {
-        c.sweep_len = (uint32_t)llround(len);
-        if (c.sweep_len < 1) return fail(GAL_E_INVAL, "gal_synth_interf_make: a sweep of %g s is less than one sample", sweep_s);
-        df = llround((f_hi_hz - f_lo_hz) / sample_rate * 4294967296.0 / (double)c.sweep_len);
-    }
-    if (f0 < INT32_MIN || f0 > INT32_MAX || df < INT32_MIN || df > INT32_MAX)  // (a frequency that rounds to sample_rate / 2 itself)
-        return fail(GAL_E_INVAL, "gal_synth_interf_make: phase step %lld, increment %lld per sample do not fit 32 bits", f0, df);
-    c.f0 = (int32_t)f0;
-    c.df = (int32_t)df;
-    c.pulse_period = (uint32_t)llround(period);
-    c.pulse_on = (uint32_t)llround(on);
-    if (c.pulse_on > c.pulse_period)
-        return fail(GAL_E_INVAL, "gal_synth_interf_make: pulse on %u of a period of %u samples", c.pulse_on, c.pulse_period);
-    *out = c;
-    return GAL_OK;
-}
-
-int gal_synth_iq_saturated(gal_synth_t *h, uint64_t *n_saturated, int32_t reset)
-{
-    if (!h || !n_saturated) return fail(GAL_E_INVAL, "gal_synth_iq_saturated: null argument");
-    *n_saturated = 0;
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = handle_stream(h);
-    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
-    if (!h->d_iq_sat) {  // no ibyte conversion yet (the counter is made by the first): still the fence for ibit / ishort conversions
-        HIP_TRY(hipStreamSynchronize(st));
-        return GAL_OK;
-    }
-    unsigned long long v = 0;
-    HIP_TRY(hipMemcpyAsync(&v, h->d_iq_sat, sizeof(v), hipMemcpyDeviceToHost, st));
-    if (reset) HIP_TRY(hipMemsetAsync(h->d_iq_sat, 0, sizeof(v), st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *n_saturated = (uint64_t)v;
-    return GAL_OK;
-}
-
-
-// ---- per-satellite signal power (iq_gain.hip) --------------------------------------------------------------------------------------
-int gal_synth_gain_q7(double d_m, double elev_rad, const double *pattern_db, double offset_db, uint16_t *out)
-{
-    if (!out) return fail(GAL_E_INVAL, "gal_synth_gain_q7: null argument");
-    bool ok = std::isfinite(d_m) && d_m > 0.0 && std::isfinite(elev_rad) && std::isfinite(offset_db);
-    for (int i = 0; pattern_db && ok && i < GAL_GAIN_PATTERN_LEN; ++i) ok = std::isfinite(pattern_db[i]);
-    if (!ok)
-        return fail(GAL_E_INVAL, "gal_synth_gain_q7: distance %g m (> 0), elevation %g rad, offset %g dB and the pattern must be finite", d_m,
-                    elev_rad, offset_db);
-    *out = (uint16_t)gal_gain_q7_eval(d_m, elev_rad, pattern_db, offset_db);
-    return GAL_OK;
-}
-
-// [x, x + bytes) against the int16 output of the batch in flight (gal_synth_finish may still synthesise it again)
-static bool hits_batch_in_flight(const gal_synth *h, const void *p, size_t bytes)
-{
-    if (!h->in_flight || !h->last_iq) return false;
-    const char *x = (const char *)p, *y = x + bytes;
-    const char *a = (const char *)h->last_iq, *b = a + (size_t)h->range_ne * (size_t)h->P.N * 4;
-    return x < b && a < y;
-}
-
-int gal_synth_iq_wsum(gal_synth_t *h, const int16_t *const *parts_dev, int32_t n_parts, const uint16_t *gain_q7, int32_t n_epochs,
-                      int16_t *out_dev)
-{
-    const char *who = "gal_synth_iq_wsum";
-    if (!h) return fail(GAL_E_INVAL, "null handle");
-    if (!parts_dev || !gain_q7 || n_parts < 1 || n_parts > GAL_ENGINE_MAX_CHAN || n_epochs < 1)
-        return fail(GAL_E_INVAL, "%s: null argument, n_parts %d (1..%d) or n_epochs %d (>= 1)", who, n_parts, GAL_ENGINE_MAX_CHAN, n_epochs);
-    if (!out_dev || ((uintptr_t)out_dev & 15)) return fail(GAL_E_INVAL, "%s: device pointers must be non-null and 16-byte aligned", who);
-    const size_t bytes = (size_t)n_epochs * (size_t)h->cfg.samples_per_epoch * 4;
-    const char *o = (const char *)out_dev, *oe = o + bytes;
-    for (int k = 0; k < n_parts; ++k) {
-        const char *x = (const char *)parts_dev[k];
-        if (!x || ((uintptr_t)x & 15)) return fail(GAL_E_INVAL, "%s: device pointers must be non-null and 16-byte aligned (part %d)", who, k);
-        if (x < oe && o < x + bytes) return fail(GAL_E_INVAL, "%s: part %d and the output overlap", who, k);
-        if (hits_batch_in_flight(h, x, bytes)) return fail(GAL_E_STATE, "%s: input of the batch in flight (call gal_synth_finish first)", who);
-    }
-    if (hits_batch_in_flight(h, out_dev, bytes)) return fail(GAL_E_STATE, "%s: output of the batch in flight (call gal_synth_finish first)", who);
-    uint64_t row_max = 0;  // the largest sum of one epoch's gains: what w needs (iq_gain.hip)
-    for (int e = 0; e < n_epochs; ++e) {
-        uint64_t row = 0;
-        for (int k = 0; k < n_parts; ++k) {
-            const uint16_t g = gain_q7[(size_t)e * n_parts + k];
-            if (g > GAL_GAIN_MAX) return fail(GAL_E_INVAL, "%s: gain %u of epoch %d, part %d (0..%d)", who, g, e, k, GAL_GAIN_MAX);
-            row += g;
-        }
-        row_max = std::max(row_max, row);
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = handle_stream(h);
-    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
-    const int rc = ensure_sat_counter(h, st);
-    if (rc) return rc;
-    // the table of this call: pointers, then gains.  One of each per handle: a call waits for the kernel of the call before it
-    if (!h->ev_gain) HIP_TRY(hipEventCreateWithFlags(&h->ev_gain, hipEventDisableTiming));
-    if (h->gain_pending) {
-        HIP_TRY(hipEventSynchronize(h->ev_gain));
-        h->gain_pending = false;
-    }
-    const size_t o_gain = sizeof(void *) * GAL_ENGINE_MAX_CHAN, need = o_gain + (size_t)n_epochs * n_parts * sizeof(int);
-    if (need > h->gain_bytes) {
-        if (h->h_gain) hipHostFree(h->h_gain);
-        if (h->d_gain) hipFree(h->d_gain);
-        h->h_gain = h->d_gain = nullptr;
-        h->gain_bytes = 0;
-        const size_t cap = need + need / 4;
-        if (hipHostMalloc((void **)&h->h_gain, cap, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&h->d_gain, cap) != hipSuccess) {
-            if (h->h_gain) hipHostFree(h->h_gain);
-            h->h_gain = nullptr;
-            return fail(GAL_E_NOMEM, "%s: the gain table of %zu bytes could not be allocated", who, cap);
-        }
-        h->gain_bytes = cap;
-    }
-    memset(h->h_gain, 0, o_gain);
-    memcpy(h->h_gain, parts_dev, sizeof(void *) * (size_t)n_parts);
-    int *const hg = (int *)(h->h_gain + o_gain);
-    for (size_t i = 0; i < (size_t)n_epochs * n_parts; ++i) hg[i] = gain_q7[i];
-    HIP_TRY(hipMemcpyAsync(h->d_gain, h->h_gain, need, hipMemcpyHostToDevice, st));
-    HIP_TRY(galk_launch_iq_wsum((const int16_t *const *)h->d_gain, (const int *)(h->d_gain + o_gain), n_parts, n_epochs, h->cfg.samples_per_epoch,
-                                row_max > 65535 ? 1 : 0, out_dev, h->d_iq_sat, st));
-    HIP_TRY(hipEventRecord(h->ev_gain, st));
-    h->gain_pending = true;
-    return GAL_OK;
-}
-
-// ---- per-satellite multipath (iq_echo.hip) ----------------------------------------------------------------------------------------
-int gal_synth_mpath_check(const gal_iq_echo_t *echo_rows, int32_t n_echo, int32_t n_epochs, const int32_t *part_of_echo, int32_t n_parts)
-{
-    const char *who = "gal_synth_mpath_check";
-    if (n_echo < 0 || n_echo > GAL_ECHO_MAX) return fail(GAL_E_INVAL, "%s: %d echoes (0..%d)", who, n_echo, GAL_ECHO_MAX);
-    if (n_epochs < 1 || n_parts < 1 || n_parts > GAL_ENGINE_MAX_CHAN)
-        return fail(GAL_E_INVAL, "%s: n_epochs %d (>= 1) or n_parts %d (1..%d)", who, n_epochs, n_parts, GAL_ENGINE_MAX_CHAN);
-    if (n_echo == 0) return GAL_OK;
-    if (!echo_rows || !part_of_echo) return fail(GAL_E_INVAL, "%s: null argument", who);
-    for (int r = 0; r < n_echo; ++r)
-        if (part_of_echo[r] < 0 || part_of_echo[r] >= n_parts)
-            return fail(GAL_E_INVAL, "%s: echo %d on part %d (0..%d)", who, r, part_of_echo[r], n_parts - 1);
-    for (int e = 0; e < n_epochs; ++e)
-        for (int r = 0; r < n_echo; ++r) {
-            const gal_iq_echo_t &q = echo_rows[(size_t)e * n_echo + r];
-            if (q.gain_q7 > GAL_GAIN_MAX) return fail(GAL_E_INVAL, "%s: gain %u of epoch %d, echo %d (0..%d)", who, q.gain_q7, e, r, GAL_GAIN_MAX);
-            if (q.delay > GAL_ECHO_MAX_DELAY)
-                return fail(GAL_E_INVAL, "%s: delay %u of epoch %d, echo %d (0..%d samples)", who, q.delay, e, r, GAL_ECHO_MAX_DELAY);
-            if (q.reserved != 0) return fail(GAL_E_INVAL, "%s: reserved = %u in epoch %d, echo %d (must be 0)", who, q.reserved, e, r);
-        }
-    return GAL_OK;
-}
-
-static bool mpath_echo_ok(const gal_mpath_echo_t *q) { return q->delay <= GAL_ECHO_MAX_DELAY && q->alpha_q12 <= 8192; }
-
-int gal_synth_mpath_make(double delay_s, double rel_db, double phase_deg, double fade_hz, double sample_rate, gal_mpath_echo_t *out)
-{
-    const char *who = "gal_synth_mpath_make";
-    if (!out) return fail(GAL_E_INVAL, "%s: null argument", who);
-    if (!std::isfinite(delay_s) || !std::isfinite(rel_db) || !std::isfinite(phase_deg) || !std::isfinite(fade_hz) || !std::isfinite(sample_rate) ||
-        sample_rate <= 0.0 || delay_s < 0.0)
-        return fail(GAL_E_INVAL, "%s: delay %g s (>= 0), %g dB, %g deg, %g Hz and the rate %g Hz (> 0) must be finite", who, delay_s, rel_db,
-                    phase_deg, fade_hz, sample_rate);
-    const double d = delay_s * sample_rate;
-    if (d > GAL_ECHO_MAX_DELAY + 0.5) return fail(GAL_E_INVAL, "%s: a delay of %g samples, more than %d", who, d, GAL_ECHO_MAX_DELAY);
-    const long long delay = llround(d);
-    if (delay > GAL_ECHO_MAX_DELAY) return fail(GAL_E_INVAL, "%s: a delay of %lld samples, more than %d", who, delay, GAL_ECHO_MAX_DELAY);
-    const double a = 4096.0 * pow(10.0, rel_db / 20.0);
-    if (!(a <= 8192.0)) return fail(GAL_E_INVAL, "%s: %g dB is an amplitude of %g, more than 2 (+6.02 dB)", who, rel_db, a / 4096.0);
-    const double turns = phase_deg / 360.0;
-    const long long ph0 = llround((turns - floor(turns)) * 4294967296.0);
-    const double step = fade_hz / sample_rate * 4294967296.0;
-    if (!(fabs(step) < 2147483647.5)) return fail(GAL_E_INVAL, "%s: a fading rate of %g Hz must lie inside +-sample_rate / 2", who, fade_hz);
-    const long long dph = llround(step);
-    if (dph < INT32_MIN || dph > INT32_MAX) return fail(GAL_E_INVAL, "%s: a fading rate of %g Hz must lie inside +-sample_rate / 2", who, fade_hz);
-    out->delay = (uint32_t)delay;
-    out->alpha_q12 = (uint32_t)llround(a);
-    out->ph0 = (uint32_t)(ph0 & 0xffffffffll);
-    out->dph = (int32_t)dph;
-    return GAL_OK;
-}
-
-int gal_synth_mpath_row(const gal_mpath_echo_t *echo, uint16_t slot_gain_q7, uint64_t epoch, int32_t samples_per_epoch, gal_iq_echo_t *row)
-{
-    const char *who = "gal_synth_mpath_row";
-    if (!echo || !row) return fail(GAL_E_INVAL, "%s: null argument", who);
-    if (samples_per_epoch < 1 || slot_gain_q7 > GAL_GAIN_MAX || !mpath_echo_ok(echo))
-        return fail(GAL_E_INVAL, "%s: samples_per_epoch %d (>= 1), gain %u (0..%d), delay %u (0..%d) or alpha_q12 %u (0..8192)", who,
-                    samples_per_epoch, slot_gain_q7, GAL_GAIN_MAX, echo->delay, GAL_ECHO_MAX_DELAY, echo->alpha_q12);
-    const uint32_t A = ((uint32_t)slot_gain_q7 * echo->alpha_q12 + 2048u) >> 12;
-    row->gain_q7 = (uint16_t)std::min<uint32_t>(A, GAL_GAIN_MAX);
-    row->delay = (uint16_t)echo->delay;
-    row->ph0 = echo->ph0 + (uint32_t)epoch * (uint32_t)samples_per_epoch * (uint32_t)echo->dph;  // (exact modulo 2^32)
-    row->dph = echo->dph;
-    row->reserved = 0;
-    return GAL_OK;
-}
-
-static constexpr size_t kMpLineWords = GAL_ECHO_MAX_DELAY;                          // one history line: complex samples = uint32
-static constexpr size_t kMpHistBytes = sizeof(uint32_t) * kMpLineWords * 2 * GAL_ECHO_LINES;  // two buffers per line
-
-static int mpath_wait(gal_synth *h)
-{
-    if (h->mp_pending) {
-        HIP_TRY(hipEventSynchronize(h->ev_mp));
-        h->mp_pending = false;
-    }
-    return GAL_OK;
-}
-
-int gal_synth_mpath_reset(gal_synth_t *h)
-{
-    if (!h) return fail(GAL_E_INVAL, "null handle");
-    if (!h->d_mp_hist) return GAL_OK;  // (the lines are made zeroed)
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = handle_stream(h);
-    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
-    const int rc = mpath_wait(h);  // (whatever stream the last call ran on)
-    if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(h->d_mp_hist, 0, kMpHistBytes, st));
-    return GAL_OK;
-}
-
-int gal_synth_iq_mpath(gal_synth_t *h, const int16_t *const *parts_dev, int32_t n_parts, const int32_t *hist_id, const uint16_t *gain_q7,
-                       int32_t n_epochs, const int32_t *part_of_echo, const gal_iq_echo_t *echo_rows, int32_t n_echo, int16_t *out_dev)
-{
-    const char *who = "gal_synth_iq_mpath";
-    if (!h) return fail(GAL_E_INVAL, "null handle");
-    if (!parts_dev || !gain_q7 || n_parts < 1 || n_parts > GAL_ENGINE_MAX_CHAN || n_epochs < 1)
-        return fail(GAL_E_INVAL, "%s: null argument, n_parts %d (1..%d) or n_epochs %d (>= 1)", who, n_parts, GAL_ENGINE_MAX_CHAN, n_epochs);
-    if (!out_dev || ((uintptr_t)out_dev & 15)) return fail(GAL_E_INVAL, "%s: device pointers must be non-null and 16-byte aligned", who);
-    int rc = gal_synth_mpath_check(echo_rows, n_echo, n_epochs, part_of_echo, n_parts);
-    if (rc) return rc;
-    const size_t bytes = (size_t)n_epochs * (size_t)h->cfg.samples_per_epoch * 4;
-    const char *o = (const char *)out_dev, *oe = o + bytes;
-    for (int k = 0; k < n_parts; ++k) {
-        const char *x = (const char *)parts_dev[k];
-        if (!x || ((uintptr_t)x & 15)) return fail(GAL_E_INVAL, "%s: device pointers must be non-null and 16-byte aligned (part %d)", who, k);
-        if (x < oe && o < x + bytes) return fail(GAL_E_INVAL, "%s: part %d and the output overlap", who, k);
-        if (hits_batch_in_flight(h, x, bytes)) return fail(GAL_E_STATE, "%s: input of the batch in flight (call gal_synth_finish first)", who);
-    }
-    if (hits_batch_in_flight(h, out_dev, bytes)) return fail(GAL_E_STATE, "%s: output of the batch in flight (call gal_synth_finish first)", who);
-    int id[GAL_ENGINE_MAX_CHAN];
-    uint64_t named = 0;  // the lines this call names
-    for (int k = 0; k < n_parts; ++k) {
-        id[k] = hist_id ? hist_id[k] : k;
-        if (id[k] < -1 || id[k] >= GAL_ECHO_LINES) return fail(GAL_E_INVAL, "%s: hist_id %d of part %d (-1..%d)", who, id[k], k, GAL_ECHO_LINES - 1);
-        if (id[k] < 0) continue;
-        if (named >> id[k] & 1) return fail(GAL_E_INVAL, "%s: history line %d is named by two parts", who, id[k]);
-        named |= (uint64_t)1 << id[k];
-    }
-    for (int r = 0; r < n_echo; ++r)
-        if (id[part_of_echo[r]] < 0) return fail(GAL_E_INVAL, "%s: echo %d repeats part %d, which has no history line (hist_id -1)", who, r, part_of_echo[r]);
-    uint64_t row_max = 0;  // the largest of sum g + 2 sum A over the epochs: what w needs (iq_echo.hip)
-    for (int e = 0; e < n_epochs; ++e) {
-        uint64_t row = 0;
-        for (int k = 0; k < n_parts; ++k) {
-            const uint16_t g = gain_q7[(size_t)e * n_parts + k];
-            if (g > GAL_GAIN_MAX) return fail(GAL_E_INVAL, "%s: gain %u of epoch %d, part %d (0..%d)", who, g, e, k, GAL_GAIN_MAX);
-            row += g;
-        }
-        for (int r = 0; r < n_echo; ++r) row += 2 * (uint64_t)echo_rows[(size_t)e * n_echo + r].gain_q7;
-        row_max = std::max(row_max, row);
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = handle_stream(h);
-    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
-    rc = ensure_sat_counter(h, st);
-    if (rc) return rc;
-    if (!h->ev_mp) HIP_TRY(hipEventCreateWithFlags(&h->ev_mp, hipEventDisableTiming));
-    rc = mpath_wait(h);  // one table per handle: the call before has read it
-    if (rc) return rc;
-    if (!h->d_mp_hist) {
-        if (hipMalloc((void **)&h->d_mp_hist, kMpHistBytes) != hipSuccess) {
-            (void)hipGetLastError();
-            h->d_mp_hist = nullptr;
-            return fail(GAL_E_NOMEM, "%s: the history lines of %zu bytes could not be allocated", who, kMpHistBytes);
-        }
-        HIP_TRY(hipMemsetAsync(h->d_mp_hist, 0, kMpHistBytes, st));
-        memset(h->mp_cur, 0, sizeof(h->mp_cur));
-    }
-    // the table of this call: part pointers, history-in and history-out pointers, gains, echo rows, part indices
-    const size_t o_hin = sizeof(void *) * GAL_ENGINE_MAX_CHAN, o_hout = 2 * o_hin, o_gain = 3 * o_hin;
-    const size_t o_rows = align_up(o_gain + (size_t)n_epochs * n_parts * sizeof(int), 16);
-    const size_t o_pof = o_rows + (size_t)n_epochs * n_echo * sizeof(gal_iq_echo_t), need = o_pof + sizeof(int) * GAL_ECHO_MAX;
-    if (need > h->mp_bytes) {
-        if (h->h_mp) hipHostFree(h->h_mp);
-        if (h->d_mp) hipFree(h->d_mp);
-        h->h_mp = h->d_mp = nullptr;
-        h->mp_bytes = 0;
-        const size_t cap = need + need / 4;
-        if (hipHostMalloc((void **)&h->h_mp, cap, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&h->d_mp, cap) != hipSuccess) {
-            (void)hipGetLastError();
-            if (h->h_mp) hipHostFree(h->h_mp);
-            h->h_mp = nullptr;
-            return fail(GAL_E_NOMEM, "%s: the table of %zu bytes could not be allocated", who, cap);
-        }
-        h->mp_bytes = cap;
-    }
-    memset(h->h_mp, 0, o_gain);
-    memcpy(h->h_mp, parts_dev, sizeof(void *) * (size_t)n_parts);
-    uint32_t **const hin = (uint32_t **)(h->h_mp + o_hin), **const hout = (uint32_t **)(h->h_mp + o_hout);
-    for (int k = 0; k < n_parts; ++k) {
-        if (id[k] < 0) continue;
-        uint32_t *const line = h->d_mp_hist + (size_t)id[k] * 2 * kMpLineWords;
-        hin[k] = line + h->mp_cur[id[k]] * kMpLineWords;
-        hout[k] = line + (h->mp_cur[id[k]] ^ 1) * kMpLineWords;
-    }
-    int *const hg = (int *)(h->h_mp + o_gain);
-    for (size_t i = 0; i < (size_t)n_epochs * n_parts; ++i) hg[i] = gain_q7[i];
-    if (n_echo > 0) {
-        memcpy(h->h_mp + o_rows, echo_rows, (size_t)n_epochs * n_echo * sizeof(gal_iq_echo_t));
-        memcpy(h->h_mp + o_pof, part_of_echo, sizeof(int) * (size_t)n_echo);
-    }
-    HIP_TRY(hipMemcpyAsync(h->d_mp, h->h_mp, need, hipMemcpyHostToDevice, st));
-    HIP_TRY(galk_launch_iq_echo((const int16_t *const *)h->d_mp, (const int16_t *const *)(h->d_mp + o_hin), (int16_t *const *)(h->d_mp + o_hout),
-                                (const int *)(h->d_mp + o_gain), h->d_mp + o_rows, (const int *)(h->d_mp + o_pof), n_parts, n_echo, n_epochs,
-                                h->cfg.samples_per_epoch, row_max > 65535 ? 1 : 0, out_dev, h->d_iq_sat, st));
-    for (int k = 0; k < n_parts; ++k)
-        if (id[k] >= 0) h->mp_cur[id[k]] ^= 1;
-    HIP_TRY(hipEventRecord(h->ev_mp, st));
-    h->mp_pending = true;
-    return GAL_OK;
-}
-
-// ---- front-end FIR filter (iq_fir.hip) ---------------------------------------------------------------------------------------------
-static constexpr int kFirTableWords = 4 * 33;  // (GE, GO) x 2 pairs per trip, (128 / 2 + 1 + 1) / 2 trips at most
-static constexpr int kFirHist = 128;           // complex samples of history, as iq_fir.hip keeps them
-
-int gal_synth_fir_check(const int16_t *taps_q14, int32_t n_taps)
-{
-    if (!taps_q14) return fail(GAL_E_INVAL, "gal_synth_fir_check: null taps");
-    if (n_taps < 1 || n_taps > GAL_FIR_MAX_TAPS) return fail(GAL_E_INVAL, "gal_synth_fir_check: %d taps (1..%d)", n_taps, GAL_FIR_MAX_TAPS);
-    long sum = 0;
-    for (int k = 0; k < n_taps; ++k) sum += std::abs((long)taps_q14[k]);
-    if (sum > 65535)
-        return fail(GAL_E_INVAL, "gal_synth_fir_check: the taps' absolute values sum to %ld, more than 65535 (16384 = 1.0): the int32 accumulator could wrap", sum);
-    return GAL_OK;
-}
-
-// the Hamming-windowed sinc of both low-pass designers, as include/galsynth.h states it; `check` = the admission of the caller's filter
-static int lowpass_design(const char *who, double cutoff_hz, double sample_rate, int32_t n_taps, int max_odd, int16_t *taps_q14)
-{
-    if (!taps_q14) return fail(GAL_E_INVAL, "%s: null taps", who);
-    if (n_taps < 3 || n_taps > max_odd || !(n_taps & 1)) return fail(GAL_E_INVAL, "%s: %d taps (odd, 3..%d)", who, n_taps, max_odd);
-    if (!std::isfinite(cutoff_hz) || !std::isfinite(sample_rate) || sample_rate <= 0.0 || !(cutoff_hz > 0.0) || !(cutoff_hz < sample_rate / 2))
-        return fail(GAL_E_INVAL, "%s: cutoff %g Hz must lie inside (0, sample_rate / 2 = %g Hz)", who, cutoff_hz, sample_rate / 2);
-    const double pi = 3.14159265358979323846, fc = cutoff_hz / sample_rate;
-    const int M = n_taps - 1;
-    double ws[GAL_FIRDEC_MAX_TAPS], S = 0.0;
-    for (int k = 0; k <= M; ++k) {
-        const double t = (double)(k - M / 2);
-        const double s = k == M / 2 ? 2.0 * fc : sin(2.0 * pi * fc * t) / (pi * t);
-        const double w = 0.54 - 0.46 * cos(2.0 * pi * (double)k / (double)M);
-        ws[k] = w * s;
-        S += ws[k];
-    }
-    if (!std::isfinite(S) || S == 0.0) return fail(GAL_E_INVAL, "%s: the window's sum is %g", who, S);
-    long long q[GAL_FIRDEC_MAX_TAPS], sum = 0;
-    for (int k = 0; k <= M; ++k) {
-        q[k] = llround(16384.0 * ws[k] / S);
-        sum += q[k];
-    }
-    q[M / 2] += 16384 - sum;
-    int16_t out[GAL_FIRDEC_MAX_TAPS];
-    long asum = 0;
-    for (int k = 0; k <= M; ++k) {
-        if (q[k] < -32768 || q[k] > 32767) return fail(GAL_E_INVAL, "%s: tap %d = %lld does not fit an int16", who, k, q[k]);
-        out[k] = (int16_t)q[k];
-        asum += std::abs((long)out[k]);
-    }
-    if (asum > 65535)
-        return fail(GAL_E_INVAL, "%s: the taps' absolute values sum to %ld, more than 65535 (16384 = 1.0): the int32 accumulator could wrap", who, asum);
-    memcpy(taps_q14, out, sizeof(int16_t) * (size_t)n_taps);
-    return GAL_OK;
-}
-
-int gal_synth_fir_lowpass(double cutoff_hz, double sample_rate, int32_t n_taps, int16_t *taps_q14)
-{
-    return lowpass_design("gal_synth_fir_lowpass", cutoff_hz, sample_rate, n_taps, GAL_FIR_MAX_TAPS - 1, taps_q14);
-}
-
-int gal_synth_fir_set(gal_synth_t *h, const int16_t *taps_q14, int32_t n_taps)
-{
-    const char *who = "gal_synth_fir_set";
-    if (!h) return fail(GAL_E_INVAL, "null handle");
-    if (n_taps != 0) {
-        const int rc = gal_synth_fir_check(taps_q14, n_taps);
-        if (rc) return rc;
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->fir_pending) {  // the table and the histories belong to the kernel in flight
-        HIP_TRY(hipEventSynchronize(h->ev_fir));
-        h->fir_pending = false;
-    }
-    if (n_taps == 0) {
-        if (h->d_fir) hipFree(h->d_fir);
-        if (h->h_fir) hipHostFree(h->h_fir);
-        h->d_fir = h->h_fir = nullptr;
-        h->fir_taps = 0;
-        return GAL_OK;
-    }
-    hipStream_t st = handle_stream(h);
-    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
-    const size_t table_bytes = sizeof(uint32_t) * kFirTableWords, bytes = table_bytes + 2 * sizeof(uint32_t) * kFirHist;
-    if (!h->ev_fir) HIP_TRY(hipEventCreateWithFlags(&h->ev_fir, hipEventDisableTiming));
-    if (!h->d_fir) {
-        uint32_t *d = nullptr, *p = nullptr;
-        if (hipMalloc((void **)&d, bytes) != hipSuccess || hipHostMalloc((void **)&p, table_bytes, hipHostMallocDefault) != hipSuccess) {
-            if (d) hipFree(d);
-            return fail(GAL_E_NOMEM, "%s: the filter table of %zu bytes could not be allocated", who, bytes);
-        }
-        h->d_fir = d;
-        h->h_fir = p;
-        h->fir_taps = 0;
-    }
-    // from here on the filter in force is gone: a failure leaves the handle without one
-    h->fir_taps = 0;
-    memset(h->h_fir, 0, table_bytes);
-    int trips = 0, hs = 0;
-    galk_fir_table(taps_q14, n_taps, h->h_fir, &trips, &hs);
-    HIP_TRY(hipMemcpyAsync(h->d_fir, h->h_fir, table_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(h->d_fir + kFirTableWords, 0, 2 * sizeof(uint32_t) * kFirHist, st));
-    HIP_TRY(hipEventRecord(h->ev_fir, st));  // (the upload reads h_fir: the next call waits for it as for a kernel)
-    h->fir_pending = true;
-    h->fir_taps = n_taps;
-    h->fir_trips = trips;
-    h->fir_hs = hs;
-    h->fir_cur = 0;
-    return GAL_OK;
-}
-
-int gal_synth_iq_fir(gal_synth_t *h, const int16_t *in_dev, size_t n_samples, int16_t *out_dev)
-{
-    const char *who = "gal_synth_iq_fir";
-    if (!h) return fail(GAL_E_INVAL, "null handle");
-    if (!in_dev || !out_dev || ((uintptr_t)in_dev & 15) || ((uintptr_t)out_dev & 15))
-        return fail(GAL_E_INVAL, "%s: device pointers must be non-null and 16-byte aligned", who);
-    if ((uint64_t)n_samples >> 41) return fail(GAL_E_INVAL, "%s: n_samples must be below 2^41", who);
-    if (!h->fir_taps) return fail(GAL_E_STATE, "%s: no filter set (call gal_synth_fir_set first)", who);
-    if (n_samples == 0) return GAL_OK;
-    const size_t bytes = 4 * n_samples;
-    const char *x = (const char *)in_dev, *o = (const char *)out_dev;
-    if (x < o + bytes && o < x + bytes) return fail(GAL_E_INVAL, "%s: input and output overlap (in place is not possible: tiles read their neighbours' input)", who);
-    if (hits_batch_in_flight(h, in_dev, bytes)) return fail(GAL_E_STATE, "%s: input of the batch in flight (call gal_synth_finish first)", who);
-    if (hits_batch_in_flight(h, out_dev, bytes)) return fail(GAL_E_STATE, "%s: output of the batch in flight (call gal_synth_finish first)", who);
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = handle_stream(h);
-    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
-    const int rc = ensure_sat_counter(h, st);
-    if (rc) return rc;
-    uint32_t *const hist = h->d_fir + kFirTableWords;
-    HIP_TRY(galk_launch_iq_fir(in_dev, out_dev, (uint64_t)n_samples, h->d_fir, h->fir_trips, h->fir_hs, hist + h->fir_cur * kFirHist,
-                               hist + (h->fir_cur ^ 1) * kFirHist, h->d_iq_sat, st));
-    h->fir_cur ^= 1;
-    HIP_TRY(hipEventRecord(h->ev_fir, st));
-    h->fir_pending = true;
-    return GAL_OK;
-}
-
-// ---- decimating front-end filter (iq_firdec.hip) --------------------------------------------------------------------------------------
-static constexpr int kFdTableWords = 640;  // min(M, T) branches x trips x 4 words <= T - 1 + 5 M (galk_firdec_table checks it)
-static constexpr int kFdHist = 512;        // complex samples of history, as iq_firdec.hip keeps them
-
-int gal_synth_firdec_check(const int16_t *taps_q14, int32_t n_taps, int32_t decim)
-{
-    const char *who = "gal_synth_firdec_check";
-    if (!taps_q14) return fail(GAL_E_INVAL, "%s: null taps", who);
-    if (n_taps < 1 || n_taps > GAL_FIRDEC_MAX_TAPS) return fail(GAL_E_INVAL, "%s: %d taps (1..%d)", who, n_taps, GAL_FIRDEC_MAX_TAPS);
-    if (decim < 2 || decim > GAL_FIRDEC_MAX_DECIM) return fail(GAL_E_INVAL, "%s: decimation %d (2..%d)", who, decim, GAL_FIRDEC_MAX_DECIM);
-    long sum = 0;
-    for (int k = 0; k < n_taps; ++k) sum += std::abs((long)taps_q14[k]);
-    if (sum > 65535)
-        return fail(GAL_E_INVAL, "%s: the taps' absolute values sum to %ld, more than 65535 (16384 = 1.0): the int32 accumulator could wrap", who, sum);
-    return GAL_OK;
-}
-
-int gal_synth_firdec_lowpass(double cutoff_hz, double sample_rate_in, int32_t n_taps, int16_t *taps_q14)
-{
-    return lowpass_design("gal_synth_firdec_lowpass", cutoff_hz, sample_rate_in, n_taps, GAL_FIRDEC_MAX_TAPS - 1, taps_q14);
-}
-
-uint64_t gal_synth_firdec_out_samples(uint64_t first_sample, uint64_t n_in, int32_t decim)
-{
-    if (decim < 2 || decim > GAL_FIRDEC_MAX_DECIM || first_sample + n_in < first_sample) return 0;
-    const uint64_t M = (uint64_t)decim, end = first_sample + n_in;
-    // ceil(a / M) = a / M + (a % M != 0), without a + M - 1 (which could wrap)
-    return (end / M + (end % M != 0)) - (first_sample / M + (first_sample % M != 0));
-}
-
-int gal_synth_firdec_set(gal_synth_t *h, const int16_t *taps_q14, int32_t n_taps, int32_t decim, uint64_t first_sample)
-{
-    const char *who = "gal_synth_firdec_set";
-    if (!h) return fail(GAL_E_INVAL, "null handle");
-    if (n_taps != 0) {
-        const int rc = gal_synth_firdec_check(taps_q14, n_taps, decim);
-        if (rc) return rc;
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->fd_pending) {  // the table and the histories belong to the kernel in flight
-        HIP_TRY(hipEventSynchronize(h->ev_fd));
-        h->fd_pending = false;
-    }
-    if (n_taps == 0) {
-        if (h->d_fd) hipFree(h->d_fd);
-        if (h->h_fd) hipHostFree(h->h_fd);
-        h->d_fd = h->h_fd = nullptr;
-        h->fd_taps = 0;
-        return GAL_OK;
-    }
-    hipStream_t st = handle_stream(h);
-    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
-    const size_t table_bytes = sizeof(uint32_t) * kFdTableWords, bytes = table_bytes + 2 * sizeof(uint32_t) * kFdHist;
-    if (!h->ev_fd) HIP_TRY(hipEventCreateWithFlags(&h->ev_fd, hipEventDisableTiming));
-    if (!h->d_fd) {
-        uint32_t *d = nullptr, *p = nullptr;
-        if (hipMalloc((void **)&d, bytes) != hipSuccess || hipHostMalloc((void **)&p, table_bytes, hipHostMallocDefault) != hipSuccess) {
-            if (d) hipFree(d);
-            return fail(GAL_E_NOMEM, "%s: the filter table of %zu bytes could not be allocated", who, bytes);
-        }
-        h->d_fd = d;
-        h->h_fd = p;
-        h->fd_taps = 0;
-    }
-    // from here on the decimator in force is gone: a failure leaves the handle without one
-    h->fd_taps = 0;
-    memset(h->h_fd, 0, table_bytes);
-    int trips = 0;
-    const int words = galk_firdec_table(taps_q14, n_taps, decim, h->h_fd, &trips);
-    if (words <= 0 || words > kFdTableWords) return fail(GAL_E_INVAL, "%s: no kernel shape for %d taps at decimation %d", who, n_taps, decim);
-    HIP_TRY(hipMemcpyAsync(h->d_fd, h->h_fd, table_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(h->d_fd + kFdTableWords, 0, 2 * sizeof(uint32_t) * kFdHist, st));
-    HIP_TRY(hipEventRecord(h->ev_fd, st));  // (the upload reads h_fd: the next call waits for it as for a kernel)
-    h->fd_pending = true;
-    h->fd_taps = n_taps;
-    h->fd_decim = decim;
-    h->fd_phase = (int)(first_sample % (uint64_t)decim);
-    h->fd_cur = 0;
-    return GAL_OK;
-}
-
-int gal_synth_iq_firdec(gal_synth_t *h, const int16_t *in_dev, size_t n_in, int16_t *out_dev, size_t *n_out)
-{
-    const char *who = "gal_synth_iq_firdec";
-    if (!h) return fail(GAL_E_INVAL, "null handle");
-    if (!n_out) return fail(GAL_E_INVAL, "%s: null n_out", who);
-    if (!in_dev || !out_dev || ((uintptr_t)in_dev & 15) || ((uintptr_t)out_dev & 15))
-        return fail(GAL_E_INVAL, "%s: device pointers must be non-null and 16-byte aligned", who);
-    if ((uint64_t)n_in >> 41) return fail(GAL_E_INVAL, "%s: n_in must be below 2^41", who);
-    if (!h->fd_taps) return fail(GAL_E_STATE, "%s: no decimator set (call gal_synth_firdec_set first)", who);
-    if (n_in == 0) {
-        *n_out = 0;
-        return GAL_OK;
-    }
-    const uint64_t outs = gal_synth_firdec_out_samples((uint64_t)h->fd_phase, (uint64_t)n_in, h->fd_decim);
-    const size_t in_bytes = 4 * n_in, out_bytes = 4 * (size_t)outs;
-    const char *x = (const char *)in_dev, *o = (const char *)out_dev;
-    if (x < o + out_bytes && o < x + in_bytes) return fail(GAL_E_INVAL, "%s: input and output overlap (tiles read their neighbours' input)", who);
-    if (hits_batch_in_flight(h, in_dev, in_bytes)) return fail(GAL_E_STATE, "%s: input of the batch in flight (call gal_synth_finish first)", who);
-    if (outs && hits_batch_in_flight(h, out_dev, out_bytes)) return fail(GAL_E_STATE, "%s: output of the batch in flight (call gal_synth_finish first)", who);
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = handle_stream(h);
-    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
-    const int rc = ensure_sat_counter(h, st);
-    if (rc) return rc;
-    uint32_t *const hist = h->d_fd + kFdTableWords;
-    const int i0 = (h->fd_decim - h->fd_phase) % h->fd_decim;  // the local index of the first input whose global index M divides
-    HIP_TRY(galk_launch_iq_firdec(in_dev, out_dev, (uint64_t)n_in, outs, i0, h->fd_taps, h->fd_decim, h->d_fd, hist + h->fd_cur * kFdHist,
-                                  hist + (h->fd_cur ^ 1) * kFdHist, h->d_iq_sat, st));
-    h->fd_cur ^= 1;
-    h->fd_phase = (int)(((uint64_t)h->fd_phase + (uint64_t)n_in) % (uint64_t)h->fd_decim);
-    HIP_TRY(hipEventRecord(h->ev_fd, st));
-    h->fd_pending = true;
-    *n_out = (size_t)outs;
-    return GAL_OK;
-}
-
-// ---- block AGC and 2-bit quantiser (iq_agc.hip) ------------------------------------------------------------------------------------
-static constexpr int kAgcState = GAL_AGC_MAX_WINDOW + 1;  // words of one state buffer, as iq_agc.hip keeps them
-
-int gal_synth_agc_check(const gal_iq_agc_t *a)
-{
-    const char *who = "gal_synth_agc_check";
-    if (!a) return fail(GAL_E_INVAL, "%s: null argument", who);
-    if (a->block_len < GAL_AGC_MIN_BLOCK || a->block_len > GAL_AGC_MAX_BLOCK)
-        return fail(GAL_E_INVAL, "%s: block_len %u (%d..%d)", who, a->block_len, GAL_AGC_MIN_BLOCK, GAL_AGC_MAX_BLOCK);
-    if (a->window < 1 || a->window > GAL_AGC_MAX_WINDOW) return fail(GAL_E_INVAL, "%s: window %u (1..%d)", who, a->window, GAL_AGC_MAX_WINDOW);
-    if ((uint64_t)a->block_len * a->window > GAL_AGC_MAX_SPAN)
-        return fail(GAL_E_INVAL, "%s: block_len %u x window %u = %llu samples, more than %d: the window sum could pass 2^47", who, a->block_len,
-                    a->window, (unsigned long long)a->block_len * a->window, GAL_AGC_MAX_SPAN);
-    if (a->target_q8 < 1 || a->target_q8 > 32767u * 256u) return fail(GAL_E_INVAL, "%s: target_q8 %u (1..%u)", who, a->target_q8, 32767u * 256u);
-    if (a->gain_min_q12 < 1 || a->gain_min_q12 > a->gain_max_q12 || a->gain_max_q12 > GAL_AGC_GAIN_MAX)
-        return fail(GAL_E_INVAL, "%s: gain clamps %u .. %u (1 <= min <= max <= %u; 4096 = 1.0)", who, a->gain_min_q12, a->gain_max_q12, GAL_AGC_GAIN_MAX);
-    if (a->p_init > ((uint64_t)a->block_len << 31))
-        return fail(GAL_E_INVAL, "%s: p_init %llu is more than 2^31 x block_len = %llu", who, (unsigned long long)a->p_init,
-                    (unsigned long long)a->block_len << 31);
-    if (a->reserved != 0) return fail(GAL_E_INVAL, "%s: reserved %u (0)", who, a->reserved);
-    return GAL_OK;
-}
-
-size_t gal_synth_agc_out_bytes(int32_t format, size_t n_samples)
-{
-    switch (format) {
-    case GAL_IQ_ISHORT: return 4 * n_samples;
-    case GAL_IQ_IBYTE: return 2 * n_samples;
-    case GAL_IQ_I2BIT: return n_samples / 2 + (n_samples & 1);
-    default: return 0;
-    }
-}
-
-uint64_t gal_synth_agc_blocks(uint64_t first_sample, uint64_t n_samples, int32_t block_len)
-{
-    if (block_len < GAL_AGC_MIN_BLOCK || block_len > GAL_AGC_MAX_BLOCK || first_sample + n_samples < first_sample) return 0;
-    const uint64_t B = (uint64_t)block_len, end = first_sample + n_samples;
-    // ceil(a / B) = a / B + (a % B != 0), without a + B - 1 (which could wrap)
-    return (end / B + (end % B != 0)) - (first_sample / B + (first_sample % B != 0));
-}
-
-int gal_synth_agc_from_rms(double target_rms, double init_rms, int32_t block_len, int32_t window, gal_iq_agc_t *out)
-{
-    const char *who = "gal_synth_agc_from_rms";
-    if (!out) return fail(GAL_E_INVAL, "%s: null argument", who);
-    if (!std::isfinite(target_rms) || !std::isfinite(init_rms) || !(init_rms >= 0.0) || !(init_rms <= 32768.0) || !(target_rms >= 0.0) ||
-        !(target_rms <= 32768.0))
-        return fail(GAL_E_INVAL, "%s: target rms %g, initial rms %g (finite, 0..32768 int16 LSB)", who, target_rms, init_rms);
-    if (block_len < 0 || window < 0) return fail(GAL_E_INVAL, "%s: block_len %d, window %d", who, block_len, window);
-    gal_iq_agc_t a;
-    memset(&a, 0, sizeof(a));
-    a.block_len = (uint32_t)block_len;
-    a.window = (uint32_t)window;
-    a.target_q8 = (uint32_t)llround(target_rms * 256.0);
-    a.gain_min_q12 = 1;
-    a.gain_max_q12 = GAL_AGC_GAIN_MAX;
-    const double sq = init_rms * init_rms;
-    a.p_init = 2ull * (uint64_t)block_len * (uint64_t)llround(sq);
-    const int rc = gal_synth_agc_check(&a);
-    if (rc) return rc;
-    *out = a;
-    return GAL_OK;
-}
-
-int gal_synth_agc_set(gal_synth_t *h, const gal_iq_agc_t *agc, uint64_t first_sample)
-{
-    const char *who = "gal_synth_agc_set";
-    if (!h) return fail(GAL_E_INVAL, "null handle");
-    gal_iq_agc_t a;
-    if (agc) {
-        a = *agc;  // the caller's struct is not looked at again
-        const int rc = gal_synth_agc_check(&a);
-        if (rc) return rc;
-        if (first_sample >> 62) return fail(GAL_E_INVAL, "%s: first_sample must be below 2^62", who);
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->agc_pending) {  // the states and the scratch belong to the kernels in flight
-        HIP_TRY(hipEventSynchronize(h->ev_agc));
-        h->agc_pending = false;
-    }
-    if (!agc) {
-        if (h->d_agc) hipFree(h->d_agc);
-        if (h->h_agc) hipHostFree(h->h_agc);
-        if (h->d_agc_scr) hipFree(h->d_agc_scr);
-        h->d_agc = h->h_agc = nullptr;
-        h->d_agc_scr = nullptr;
-        h->agc_scr_bytes = 0;
-        h->agc_on = false;
-        return GAL_OK;
-    }
-    hipStream_t st = handle_stream(h);
-    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
-    const size_t state_bytes = sizeof(unsigned long long) * kAgcState;
-    if (!h->ev_agc) HIP_TRY(hipEventCreateWithFlags(&h->ev_agc, hipEventDisableTiming));
-    if (!h->d_agc) {
-        unsigned long long *d = nullptr, *p = nullptr;
-        if (hipMalloc((void **)&d, 2 * state_bytes) != hipSuccess || hipHostMalloc((void **)&p, state_bytes, hipHostMallocDefault) != hipSuccess) {
-            if (d) hipFree(d);
-            return fail(GAL_E_NOMEM, "%s: the state of %zu bytes could not be allocated", who, 2 * state_bytes);
-        }
-        h->d_agc = d;
-        h->h_agc = p;
-    }
-    // from here on the AGC in force is gone: a failure leaves the handle without one
-    h->agc_on = false;
-    for (int k = 0; k < kAgcState; ++k) h->h_agc[k] = k < (int)a.window ? a.p_init : 0ull;
-    HIP_TRY(hipMemcpyAsync(h->d_agc, h->h_agc, state_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(h->ev_agc, st));  // (the upload reads h_agc: the next call waits for it as for a kernel)
-    h->agc_pending = true;
-    h->agc = a;
-    h->agc_pos = first_sample;
-    h->agc_cur = 0;
-    h->agc_on = true;
-    return GAL_OK;
-}
-
-int gal_synth_iq_agc(gal_synth_t *h, const int16_t *in_dev, size_t n_samples, int32_t format, int32_t param, void *out_dev, uint32_t *gains_dev,
-                     size_t *n_gains)
-{
-    const char *who = "gal_synth_iq_agc";
-    if (!h) return fail(GAL_E_INVAL, "null handle");
-    if (format != GAL_IQ_ISHORT && format != GAL_IQ_IBYTE && format != GAL_IQ_I2BIT)
-        return fail(GAL_E_INVAL, "%s: format %d (GAL_IQ_ISHORT 0, GAL_IQ_IBYTE 1, GAL_IQ_I2BIT 3; a sign, GAL_IQ_IBIT, needs no gain control)", who, format);
-    if (format == GAL_IQ_IBYTE ? (param < 0 || param > 15) : format == GAL_IQ_I2BIT ? (param < 1 || param > 32767) : param != 0)
-        return fail(GAL_E_INVAL, "%s: param %d (the shift 0..15 for GAL_IQ_IBYTE, the threshold 1..32767 for GAL_IQ_I2BIT, 0 for GAL_IQ_ISHORT)", who, param);
-    if (!in_dev || !out_dev || ((uintptr_t)in_dev & 15) || ((uintptr_t)out_dev & 15))
-        return fail(GAL_E_INVAL, "%s: device pointers must be non-null and 16-byte aligned", who);
-    if ((uintptr_t)gains_dev & 3) return fail(GAL_E_INVAL, "%s: gains_dev must be 4-byte aligned", who);
-    if ((uint64_t)n_samples >> 41) return fail(GAL_E_INVAL, "%s: n_samples must be below 2^41", who);
-    if (!h->agc_on) return fail(GAL_E_STATE, "%s: no AGC set (call gal_synth_agc_set first)", who);
-    if (n_samples == 0) {
-        if (n_gains) *n_gains = 0;
-        return GAL_OK;
-    }
-    const uint32_t B = h->agc.block_len, off0 = (uint32_t)(h->agc_pos % B);
-    const uint64_t ng = gal_synth_agc_blocks(h->agc_pos, (uint64_t)n_samples, (int32_t)B);
-    const size_t in_bytes = 4 * n_samples, out_bytes = gal_synth_agc_out_bytes(format, n_samples), g_bytes = gains_dev ? 4 * (size_t)ng : 0;
-    const char *x = (const char *)in_dev, *o = (const char *)out_dev, *g = (const char *)gains_dev;
-    if (x < o + out_bytes && o < x + in_bytes) return fail(GAL_E_INVAL, "%s: input and output overlap", who);
-    if (g_bytes && ((x < g + g_bytes && g < x + in_bytes) || (o < g + g_bytes && g < o + out_bytes)))
-        return fail(GAL_E_INVAL, "%s: the gains overlap the input or the output", who);
-    if (hits_batch_in_flight(h, in_dev, in_bytes)) return fail(GAL_E_STATE, "%s: input of the batch in flight (call gal_synth_finish first)", who);
-    if (hits_batch_in_flight(h, out_dev, out_bytes)) return fail(GAL_E_STATE, "%s: output of the batch in flight (call gal_synth_finish first)", who);
-    if (g_bytes && hits_batch_in_flight(h, gains_dev, g_bytes)) return fail(GAL_E_STATE, "%s: gains in the batch in flight (call gal_synth_finish first)", who);
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = handle_stream(h);
-    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
-    const int rc = ensure_sat_counter(h, st);
-    if (rc) return rc;
-    // the scratch of this call: one per handle, grown when a call touches more blocks than any before it (only then the host waits
-    // for the kernels of the call before)
-    const uint64_t need = galk_agc_scratch_bytes((uint64_t)n_samples, off0, B);
-    if (need > h->agc_scr_bytes) {
-        if (h->agc_pending) {
-            HIP_TRY(hipEventSynchronize(h->ev_agc));
-            h->agc_pending = false;
-        }
-        if (h->d_agc_scr) hipFree(h->d_agc_scr);
-        h->d_agc_scr = nullptr;
-        h->agc_scr_bytes = 0;
-        const uint64_t cap = need + need / 4 + 256;
-        if (cap != (uint64_t)(size_t)cap || hipMalloc(&h->d_agc_scr, (size_t)cap) != hipSuccess) {
-            h->d_agc_scr = nullptr;
-            (void)hipGetLastError();
-            return fail(GAL_E_NOMEM, "%s: the scratch of %llu bytes (12 per block touched) could not be allocated", who, (unsigned long long)cap);
-        }
-        h->agc_scr_bytes = (size_t)cap;
-    }
-    HIP_TRY(galk_launch_iq_agc(in_dev, (uint64_t)n_samples, off0, format, param, &h->agc, h->d_agc + h->agc_cur * kAgcState,
-                               h->d_agc + (h->agc_cur ^ 1) * kAgcState, h->d_agc_scr, out_dev, gains_dev, h->d_iq_sat, st));
-    h->agc_cur ^= 1;
-    h->agc_pos += (uint64_t)n_samples;
-    HIP_TRY(hipEventRecord(h->ev_agc, st));
-    h->agc_pending = true;
-    if (n_gains) *n_gains = (size_t)ng;
-    return GAL_OK;
-}
-
-// ---- receiver oscillator (iq_osc.hip) ----------------------------------------------------------------------------------------------
-static constexpr uint64_t kOscMaxS = 1ull << 48;
-
-int gal_synth_osc_check(const gal_iq_osc_t *o)
-{
-    const char *who = "gal_synth_osc_check";
-    if (!o) return fail(GAL_E_INVAL, "%s: null argument", who);
-    if (o->reserved != 0) return fail(GAL_E_INVAL, "%s: reserved %u (0)", who, o->reserved);
-    if (o->s > kOscMaxS) return fail(GAL_E_INVAL, "%s: s %llu is more than 2^48", who, (unsigned long long)o->s);
-    return GAL_OK;
-}
-
-// M2 = the sum of mag(w)^2 over the 2^31 words w of the Gauss table's input (exact: below 2^31 x 2^30): per octave the 13 bits under
-// the leading one choose the cell and the fraction, every (cell, fraction) 2^(low - 13) times where the octave has low >= 13 bits
-// under its leading one, else only those whose missing low bits are 0, once
-static uint64_t gauss_m2()
-{
-    const int32_t(*T)[32][2] = (const int32_t(*)[32][2])gal_tables_gauss();
-    uint64_t m2 = 0;
-    for (int o = 0; o < 31; ++o) {
-        const int low = 30 - o, step = low >= 13 ? 1 : 1 << (13 - low);
-        uint64_t acc = 0;
-        for (int sf = 0; sf < 8192; sf += step) {
-            const int64_t a = T[o][sf >> 8][0], b = T[o][sf >> 8][1], mag = a - (((a - b) * (sf & 255) + 128) >> 8);
-            acc += (uint64_t)(mag * mag);
-        }
-        m2 += low >= 13 ? acc << (low - 13) : acc;
-    }
-    const int64_t m0 = T[31][0][0];  // w = 0
-    return m2 + (uint64_t)(m0 * m0);
-}
-
-int gal_synth_osc_make(double f_hz, double drift_hz_s, double h0, double sample_rate, double carrier_hz, gal_iq_osc_t *out)
-{
-    const char *who = "gal_synth_osc_make";
-    if (!out) return fail(GAL_E_INVAL, "%s: null argument", who);
-    if (!std::isfinite(f_hz) || !std::isfinite(drift_hz_s) || !std::isfinite(h0) || !std::isfinite(sample_rate) || !std::isfinite(carrier_hz))
-        return fail(GAL_E_INVAL, "%s: an argument is not finite", who);
-    if (!(sample_rate > 0.0) || carrier_hz < 0.0 || h0 < 0.0)
-        return fail(GAL_E_INVAL, "%s: sample rate %g (> 0), carrier %g Hz (>= 0), h0 %g s (>= 0)", who, sample_rate, carrier_hz, h0);
-    if (!(fabs(f_hz) < sample_rate / 2)) return fail(GAL_E_INVAL, "%s: offset %g Hz must lie inside +-sample_rate / 2 = %g Hz", who, f_hz, sample_rate / 2);
-    const double two64 = 18446744073709551616.0, two63 = 9223372036854775808.0;
-    const double fv = f_hz / sample_rate * two64, dv = drift_hz_s / sample_rate / sample_rate * two64;
-    if (!(fabs(fv) < two63)) return fail(GAL_E_INVAL, "%s: offset %g Hz must lie inside +-sample_rate / 2 = %g Hz", who, f_hz, sample_rate / 2);
-    if (!(fabs(dv) < two63))
-        return fail(GAL_E_INVAL, "%s: drift %g Hz/s does not fit (|drift| < sample_rate^2 / 2 = %g Hz/s)", who, drift_hz_s, sample_rate * sample_rate / 2);
-    const double v = (double)gauss_m2() / 36028797018963968.0;  // 2^55 = 2^31 words x 4096^2
-    const double sigma_cycles = carrier_hz * sqrt(h0 / (2.0 * sample_rate));
-    const double sv = sigma_cycles / sqrt(v) * 4503599627370496.0;  // 2^52
-    if (!(sv <= (double)kOscMaxS)) return fail(GAL_E_INVAL, "%s: the phase noise of h0 %g s needs s = %g, more than 2^48", who, h0, sv);
-    gal_iq_osc_t o;
-    memset(&o, 0, sizeof(o));
-    o.seed = 1;
-    o.f = (int64_t)llround(fv);
-    o.d = (int64_t)llround(dv);
-    o.s = (uint64_t)llround(sv);
-    *out = o;
-    return GAL_OK;
-}
-
-int gal_synth_osc_lo_step(const gal_iq_osc_t *osc, uint64_t N, int32_t *carr_dph)
-{
-    if (!osc || !carr_dph) return fail(GAL_E_INVAL, "gal_synth_osc_lo_step: null argument");
-    *carr_dph = (int32_t)(uint32_t)(((uint64_t)osc->f + N * (uint64_t)osc->d) >> 32);
-    return GAL_OK;
-}
-
-int gal_synth_osc_set(gal_synth_t *h, const gal_iq_osc_t *osc, uint64_t first_sample)
-{
-    const char *who = "gal_synth_osc_set";
-    if (!h) return fail(GAL_E_INVAL, "null handle");
-    gal_iq_osc_t o;
-    if (osc) {
-        o = *osc;  // the caller's struct is not looked at again
-        const int rc = gal_synth_osc_check(&o);
-        if (rc) return rc;
-        if (first_sample >> 62) return fail(GAL_E_INVAL, "%s: first_sample must be below 2^62", who);
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->osc_pending) {  // the state and the scratch belong to the kernels in flight
-        HIP_TRY(hipEventSynchronize(h->ev_osc));
-        h->osc_pending = false;
-    }
-    if (!osc) {
-        if (h->d_osc) hipFree(h->d_osc);
-        if (h->d_osc_scr) hipFree(h->d_osc_scr);
-        h->d_osc = nullptr;
-        h->d_osc_scr = nullptr;
-        h->osc_scr_bytes = 0;
-        h->osc_on = false;
-        return GAL_OK;
-    }
-    hipStream_t st = handle_stream(h);
-    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
-    if (!h->ev_osc) HIP_TRY(hipEventCreateWithFlags(&h->ev_osc, hipEventDisableTiming));
-    if (!h->d_osc && hipMalloc((void **)&h->d_osc, 2 * sizeof(long long)) != hipSuccess) {
-        h->d_osc = nullptr;
-        (void)hipGetLastError();
-        return fail(GAL_E_NOMEM, "%s: the state of 16 bytes could not be allocated", who);
-    }
-    // from here on the oscillator in force is gone: a failure leaves the handle without one
-    h->osc_on = false;
-    HIP_TRY(hipMemsetAsync(h->d_osc, 0, 2 * sizeof(long long), st));
-    HIP_TRY(hipEventRecord(h->ev_osc, st));
-    h->osc_pending = true;
-    h->osc = o;
-    h->osc_n0 = h->osc_pos = first_sample;
-    h->osc_cur = 0;
-    h->osc_on = true;
-    return GAL_OK;
-}
-
-int gal_synth_iq_osc(gal_synth_t *h, const int16_t *in_dev, size_t n_samples, int16_t *out_dev)
-{
-    const char *who = "gal_synth_iq_osc";
-    if (!h) return fail(GAL_E_INVAL, "null handle");
-    if (!in_dev || !out_dev || ((uintptr_t)in_dev & 15) || ((uintptr_t)out_dev & 15))
-        return fail(GAL_E_INVAL, "%s: device pointers must be non-null and 16-byte aligned", who);
-    if ((uint64_t)n_samples >> 41) return fail(GAL_E_INVAL, "%s: n_samples must be below 2^41", who);
-    if (!h->osc_on) return fail(GAL_E_STATE, "%s: no oscillator set (call gal_synth_osc_set first)", who);
-    if (n_samples == 0) return GAL_OK;
-    const size_t bytes = 4 * n_samples;
-    const char *x = (const char *)in_dev, *o = (const char *)out_dev;
-    if (x != o && x < o + bytes && o < x + bytes) return fail(GAL_E_INVAL, "%s: input and output overlap (only exactly in place may)", who);
-    if (hits_batch_in_flight(h, in_dev, bytes)) return fail(GAL_E_STATE, "%s: input of the batch in flight (call gal_synth_finish first)", who);
-    if (hits_batch_in_flight(h, out_dev, bytes)) return fail(GAL_E_STATE, "%s: output of the batch in flight (call gal_synth_finish first)", who);
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = handle_stream(h);
-    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
-    const int rc = ensure_sat_counter(h, st);
-    if (rc) return rc;
-    const bool noise = h->osc.s != 0;
-    // the scratch of this call: one per handle, grown when a call is longer than any before it (only then the host waits for the
-    // kernels of the call before)
-    const uint64_t need = noise ? galk_osc_scratch_bytes((uint64_t)n_samples) : 0;
-    if (need > h->osc_scr_bytes) {
-        if (h->osc_pending) {
-            HIP_TRY(hipEventSynchronize(h->ev_osc));
-            h->osc_pending = false;
-        }
-        if (h->d_osc_scr) hipFree(h->d_osc_scr);
-        h->d_osc_scr = nullptr;
-        h->osc_scr_bytes = 0;
-        const uint64_t cap = need + need / 4 + 256;
-        if (cap != (uint64_t)(size_t)cap || hipMalloc(&h->d_osc_scr, (size_t)cap) != hipSuccess) {
-            h->d_osc_scr = nullptr;
-            (void)hipGetLastError();
-            return fail(GAL_E_NOMEM, "%s: the scratch of %llu bytes (12 per tile of 1024 samples) could not be allocated", who, (unsigned long long)cap);
-        }
-        h->osc_scr_bytes = (size_t)cap;
-    }
-    HIP_TRY(galk_launch_iq_osc(in_dev, out_dev, (uint64_t)n_samples, h->osc_pos, h->osc_n0, &h->osc, h->d_osc + h->osc_cur, h->d_osc + (h->osc_cur ^ 1),
-                               h->d_osc_scr, h->d_iq_sat, st));
-    if (noise) h->osc_cur ^= 1;
-    h->osc_pos += (uint64_t)n_samples;
-    HIP_TRY(hipEventRecord(h->ev_osc, st));
-    h->osc_pending = true;
-    return GAL_OK;
-}
-
-// gal_synth_run_gains (n_echo = 0) and gal_synth_run_mpath: the slot groups, one synthesis run per group, then the weighted sum or the
-// echo pass
-static int run_groups(const char *who, gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_epochs, const gal_chan_state_t *state_in,
-                      const uint16_t *gain_q7, const int32_t *slot_of_echo, const gal_iq_echo_t *echo_rows, int32_t n_echo, int16_t *iq_dev,
-                      gal_chan_state_t *state_out)
-{
-    if (!h || !params || !gain_q7 || !iq_dev || n_epochs < 1) return fail(GAL_E_INVAL, "%s: null argument or n_epochs %d (>= 1)", who, n_epochs);
-    if ((uintptr_t)iq_dev & 15) return fail(GAL_E_INVAL, "%s: iq_dev must be 16-byte aligned", who);
-    if (h->in_flight) return fail(GAL_E_STATE, "%s while a batch is in flight: call gal_synth_finish first", who);
-    if (h->staged_pending)  // (gal_synth_plan would replace it silently: here the caller has not asked for a plan)
-        return fail(GAL_E_STATE, "%s with a plan of gal_synth_plan_async waiting for its gal_synth_execute", who);
-    const int E = n_epochs, S = h->cfg.n_slots;
-    for (size_t i = 0; i < (size_t)E * S; ++i)
-        if (gain_q7[i] > GAL_GAIN_MAX)
-            return fail(GAL_E_INVAL, "%s: gain %u of epoch %zu, slot %zu (0..%d)", who, gain_q7[i], i / S, i % S, GAL_GAIN_MAX);
-    // Slot groups: the slots of a group have the same gain in every epoch in which they are active, so one run of the existing path
-    // with only those slots active is the part sum_s x_s of the group, and the group's gain of an epoch is that common value (first
-    // fit; a slot that is never active joins no group).  All slots at one gain -- the unity case -- make one group
-    struct Group {
-        std::vector<int> slots;
-        std::vector<int> g;  // [E]; -1: no slot of the group is active in that epoch
-        bool solo = false;   // the one slot of the group carries an echo: no other slot joins it
-    };
-    std::vector<Group> groups;
-    std::vector<int> group_of(S, -1);
-    // a slot that carries an echo is a group of its own, idle or not: its part is what the echo delays, its line follows the slot
-    std::vector<char> solo(S, 0);
-    for (int r = 0; r < n_echo; ++r) solo[slot_of_echo[r]] = 1;
-    for (int s = 0; s < S; ++s) {
-        bool active = solo[s];
-        for (int e = 0; e < E && !active; ++e) active = params[(size_t)e * S + s].prn > 0;
-        if (!active) continue;
-        size_t k = solo[s] ? groups.size() : 0;
-        for (; k < groups.size(); ++k) {
-            bool fits = !groups[k].solo;
-            for (int e = 0; e < E && fits; ++e)
-                fits = params[(size_t)e * S + s].prn <= 0 || groups[k].g[e] < 0 || groups[k].g[e] == (int)gain_q7[(size_t)e * S + s];
-            if (fits) break;
-        }
-        if (k == groups.size()) {
-            groups.emplace_back();
-            groups[k].g.assign(E, -1);
-            groups[k].solo = solo[s];
-        }
-        groups[k].slots.push_back(s);
-        group_of[s] = (int)k;
-        for (int e = 0; e < E; ++e)
-            if (params[(size_t)e * S + s].prn > 0) groups[k].g[e] = gain_q7[(size_t)e * S + s];
-    }
-    const int n_parts = groups.empty() ? 1 : (int)groups.size();  // (an empty sky: one run of nothing)
-    bool unity = n_parts == 1 && n_echo == 0;  // one part at gain 128 wherever it is not zero: y = x, the run goes straight into iq_dev
-    if (!groups.empty())
-        for (int e = 0; e < E && unity; ++e) unity = groups[0].g[e] < 0 || groups[0].g[e] == GAL_GAIN_UNITY;
-    const size_t bytes = (size_t)E * (size_t)h->cfg.samples_per_epoch * 4;
-    // the weighted sum of the call before may still read the scratch buffers: wait for it here, whatever stream the handle is on now
-    // (on one stream the runs below would order behind it by themselves)
-    if (h->gain_pending) {
-        HIP_TRY(hipSetDevice(h->device));
-        HIP_TRY(hipEventSynchronize(h->ev_gain));
-        h->gain_pending = false;
-    }
-    if (h->mp_pending) {
-        HIP_TRY(hipSetDevice(h->device));
-        HIP_TRY(hipEventSynchronize(h->ev_mp));
-        h->mp_pending = false;
-    }
-    h->gain_runs = 0;
-    if (!unity && bytes * (size_t)n_parts > h->own_parts_bytes) {
-        HIP_TRY(hipSetDevice(h->device));
-        if (h->own_parts) hipFree(h->own_parts);
-        h->own_parts = nullptr;
-        h->own_parts_bytes = 0;
-        if (hipMalloc(&h->own_parts, bytes * (size_t)n_parts) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(GAL_E_NOMEM, "%s: %d slot groups of %zu bytes each: hipMalloc of %zu bytes of scratch failed", who, n_parts, bytes,
-                        bytes * (size_t)n_parts);
-        }
-        h->own_parts_bytes = bytes * (size_t)n_parts;
-    }
-    std::vector<gal_chan_epoch_t> one((size_t)E * S);
-    std::vector<gal_chan_state_t> st_k(S), st_all(S);
-    const int16_t *parts[GAL_ENGINE_MAX_CHAN];
-    for (int k = 0; k < n_parts; ++k) {
-        memcpy(one.data(), params, sizeof(gal_chan_epoch_t) * (size_t)E * S);
-        for (int e = 0; e < E; ++e)
-            for (int s = 0; s < S; ++s)
-                if (group_of[s] != k) one[(size_t)e * S + s].prn = 0;
-        int16_t *dst = unity ? iq_dev : (int16_t *)((char *)h->own_parts + bytes * (size_t)k);
-        parts[k] = dst;
-        int rc = gal_synth_plan(h, one.data(), E, state_in);
-        if (rc == GAL_OK) rc = gal_synth_execute(h, dst);
-        if (rc == GAL_OK) rc = gal_synth_finish_n(h, st_k.data(), nullptr, 0);
-        if (rc != GAL_OK) return rc;
-        h->gain_runs += 1;
-        // the end state of a slot is that of its own run; a slot that is never active is idle in every run (the first one's record)
-        for (int s = 0; s < S; ++s)
-            if (group_of[s] == k || (k == 0 && group_of[s] < 0)) st_all[s] = st_k[s];
-    }
-    if (!unity) {
-        std::vector<uint16_t> gp((size_t)E * n_parts);
-        for (int e = 0; e < E; ++e)
-            for (int k = 0; k < n_parts; ++k) gp[(size_t)e * n_parts + k] = (uint16_t)(groups[k].g[e] < 0 ? 0 : groups[k].g[e]);
-        int rc;
-        if (n_echo > 0) {
-            std::vector<int32_t> hist_id(n_parts, -1), part_of(n_echo);
-            for (int k = 0; k < n_parts; ++k)
-                if (groups[k].solo) hist_id[k] = groups[k].slots[0];
-            for (int r = 0; r < n_echo; ++r) part_of[r] = group_of[slot_of_echo[r]];
-            rc = gal_synth_iq_mpath(h, parts, n_parts, hist_id.data(), gp.data(), E, part_of.data(), echo_rows, n_echo, iq_dev);
-        } else {
-            rc = gal_synth_iq_wsum(h, parts, n_parts, gp.data(), E, iq_dev);
-        }
-        if (rc != GAL_OK) return rc;
-    }
-    if (state_out) memcpy(state_out, st_all.data(), sizeof(gal_chan_state_t) * S);
-    return GAL_OK;
-}
-
-int gal_synth_run_gains(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_epochs, const gal_chan_state_t *state_in,
-                        const uint16_t *gain_q7, int16_t *iq_dev, gal_chan_state_t *state_out)
-{
-    return run_groups("gal_synth_run_gains", h, params, n_epochs, state_in, gain_q7, nullptr, nullptr, 0, iq_dev, state_out);
-}
-
-int gal_synth_run_mpath(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_epochs, const gal_chan_state_t *state_in,
-                        const uint16_t *gain_q7, const int32_t *slot_of_echo, const gal_iq_echo_t *echo_rows, int32_t n_echo, int16_t *iq_dev,
-                        gal_chan_state_t *state_out)
-{
-    const char *who = "gal_synth_run_mpath";
-    if (n_echo == 0) return run_groups(who, h, params, n_epochs, state_in, gain_q7, nullptr, nullptr, 0, iq_dev, state_out);
-    if (!h) return fail(GAL_E_INVAL, "%s: null handle", who);
-    if (h->cfg.n_slots > GAL_ECHO_LINES) return fail(GAL_E_INVAL, "%s: %d slots, more than the %d history lines", who, h->cfg.n_slots, GAL_ECHO_LINES);
-    const int rc = gal_synth_mpath_check(echo_rows, n_echo, n_epochs, slot_of_echo, h->cfg.n_slots);
-    if (rc) return rc;
-    return run_groups(who, h, params, n_epochs, state_in, gain_q7, slot_of_echo, echo_rows, n_echo, iq_dev, state_out);
-}
-
-int gal_synth_gain_runs(const gal_synth_t *h, int32_t *n_runs)
-{
-    if (!h || !n_runs) return fail(GAL_E_INVAL, "gal_synth_gain_runs: null argument");
-    *n_runs = h->gain_runs;
-    return GAL_OK;
-}
-
-// ---- correlator bank and C/N0 monitor (iq_corr.hip) --------------------------------------------------------------------------
-static constexpr uint64_t kCorrL = (uint64_t)(2 * GAL_CODE_LEN) << 32;  // one code period: 8184 half chips x 2^32
-
-// nullptr: the request is fine; otherwise what is wrong with it
-static const char *corr_req_fault(const gal_corr_req_t *q)
-{
-    if (q->prn < 1 || q->prn > GAL_NUM_PRN) return "prn outside 1..50";
-    if (q->max_periods < 1 || q->max_periods > 1024) return "max_periods outside 1..1024";
-    if (q->code_ph0 >= kCorrL) return "code_ph0 outside [0, 8184 x 2^32)";
-    if (q->code_dph > ((uint64_t)1 << 32)) return "code_dph above 2^32 (one half chip per sample)";
-    if (q->delay_step < 1) return "delay_step below 1";
-    if (q->n_delay < 1 || q->n_delay > 2 * GAL_CODE_LEN) return "n_delay outside 1..8184";
-    if (q->n_dopp < 1 || q->n_dopp > 64) return "n_dopp outside 1..64";
-    return nullptr;
-}
-
-size_t gal_synth_corr_out_bytes(const gal_corr_req_t *req)
-{
-    if (!req || req->max_periods < 1 || req->max_periods > 1024 || req->n_delay < 1 || req->n_delay > 2 * GAL_CODE_LEN || req->n_dopp < 1 ||
-        req->n_dopp > 64)
-        return 0;
-    return (size_t)req->max_periods * (size_t)req->n_dopp * (size_t)req->n_delay * 4 * sizeof(int64_t);
-}
-
-int gal_synth_correlate(gal_synth_t *h, const void *buf_dev, int32_t format, size_t n_samples, const gal_corr_req_t *reqs, int32_t n_req,
-                        int64_t *out_dev)
-{
-    if (!h) return fail(GAL_E_INVAL, "null handle");
-    if (format != GAL_IQ_ISHORT && format != GAL_IQ_IBYTE && format != GAL_IQ_IBIT)
-        return fail(GAL_E_INVAL, "gal_synth_correlate: unknown format %d (GAL_IQ_ISHORT 0, GAL_IQ_IBYTE 1, GAL_IQ_IBIT 2)", format);
-    if (!buf_dev || !out_dev || !reqs || ((uintptr_t)buf_dev & 15) || ((uintptr_t)out_dev & 15))
-        return fail(GAL_E_INVAL, "gal_synth_correlate: pointers must be non-null, the device pointers 16-byte aligned");
-    if (n_req < 1 || n_req > GAL_CORR_MAX_REQ) return fail(GAL_E_INVAL, "gal_synth_correlate: %d requests (1..%d)", n_req, GAL_CORR_MAX_REQ);
-    if (n_samples == 0 || n_samples > ((size_t)1 << 32)) return fail(GAL_E_INVAL, "gal_synth_correlate: n_samples %zu (1..2^32)", n_samples);
-    size_t total = 0;
-    for (int r = 0; r < n_req; ++r) {
-        const char *what = corr_req_fault(&reqs[r]);
-        if (what) return fail(GAL_E_INVAL, "gal_synth_correlate: request %d: %s", r, what);
-        // P(n) = code_ph0 + n code_dph must stay below 2^64 for every n < n_samples
-        if (reqs[r].code_dph && (uint64_t)(n_samples - 1) > (UINT64_MAX - reqs[r].code_ph0) / reqs[r].code_dph)
-            return fail(GAL_E_INVAL, "gal_synth_correlate: request %d: the code phase overflows 64 bits within %zu samples", r, n_samples);
-        total += gal_synth_corr_out_bytes(&reqs[r]);
-        if (total > GAL_CORR_MAX_OUT_BYTES)
-            return fail(GAL_E_INVAL, "gal_synth_correlate: the requests take more than %zu bytes of output", (size_t)GAL_CORR_MAX_OUT_BYTES);
-    }
-    {
-        const char *x = (const char *)buf_dev, *y = x + gal_synth_iq_bytes(format, n_samples);
-        const char *o = (const char *)out_dev, *e = o + total;
-        if (x < e && o < y) return fail(GAL_E_INVAL, "gal_synth_correlate: buffer and output overlap");
-        if (h->in_flight && h->last_iq) {  // the batch in flight may still be synthesised again by gal_synth_finish
-            const char *a = (const char *)h->last_iq, *b = a + (size_t)h->range_ne * (size_t)h->P.N * 4;
-            if ((x < b && a < y) || (o < b && a < e))
-                return fail(GAL_E_STATE, "gal_synth_correlate: buffer of the batch in flight (call gal_synth_finish first)");
-        }
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = handle_stream(h);
-    if (!st) return fail(GAL_E_DEVICE, "hipStreamCreate failed");
-    if (!h->d_corr_tab) {
-        // [512] cos | sin << 16, then per PRN 8184 half chips x 2 bits: bit 2 (h & 15) of word h >> 4 = (b[h] < 0), the next one (c[h] < 0);
-        // b[h] = (E1B chip: set bit -1) x (sboc: even half chip -1), as the synthesis kernels take them out of the same tables
-        init_tables();
-        std::vector<uint32_t> tab(512 + 50 * 512, 0u);
-        for (int k = 0; k < 512; ++k) tab[k] = (uint32_t)(uint16_t)g_cos[k] | ((uint32_t)(uint16_t)g_sin[k] << 16);
-        for (int prn = 0; prn < 50; ++prn)
-            for (int hc = 0; hc < 2 * GAL_CODE_LEN; ++hc) {
-                const int chip = hc >> 1;
-                const uint32_t b = (kE1B[prn][chip >> 5] >> (chip & 31)) & 1u, c = (kE1C[prn][chip >> 5] >> (chip & 31)) & 1u;
-                const uint32_t even = (uint32_t)(~hc & 1);
-                tab[512 + prn * 512 + (hc >> 4)] |= ((b ^ even) | ((c ^ even) << 1)) << (2 * (hc & 15));
-            }
-        uint32_t *d = nullptr;
-        HIP_TRY(hipMalloc((void **)&d, tab.size() * sizeof(uint32_t)));
-        const hipError_t err = hipMemcpy(d, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-        if (err != hipSuccess) {
-            hipFree(d);
-            return fail(GAL_E_DEVICE, "gal_synth_correlate: table upload failed: %s", hipGetErrorString(err));
-        }
-        h->d_corr_tab = d;
-    }
-    HIP_TRY(hipMemsetAsync(out_dev, 0, total, st));
-    size_t off = 0;
-    for (int r = 0; r < n_req; ++r) {  // the request travels as kernel arguments: copied when this returns
-        const gal_corr_req_t &q = reqs[r];
-        // the first sample of period max_periods: nothing from there on is wanted
-        uint64_t n_eff = n_samples;
-        if (q.code_dph) {
-            const uint64_t span = (uint64_t)q.max_periods * kCorrL - q.code_ph0;  // > 0
-            const uint64_t first = (span + q.code_dph - 1) / q.code_dph;
-            if (first < n_eff) n_eff = first;
-        }
-        HIP_TRY(galk_launch_corr(format, buf_dev, n_eff, q.code_ph0, q.code_dph, q.carr_ph0, (uint32_t)q.carr_dph + (uint32_t)q.dopp0,
-                                 (uint32_t)q.dopp_step, q.delay0, q.delay_step, q.n_delay, q.n_dopp, q.max_periods, h->d_corr_tab,
-                                 h->d_corr_tab + 512 + (size_t)(q.prn - 1) * 512, (long long *)((char *)out_dev + off), st));
-        off += gal_synth_corr_out_bytes(&q);
-    }
-    return GAL_OK;
-}
-
-int gal_corr_from_epoch(const gal_chan_epoch_t *rec, double sample_rate, int64_t sample_offset, gal_corr_req_t *out)
-{
-    if (!rec || !out) return fail(GAL_E_INVAL, "gal_corr_from_epoch: null argument");
-    if (rec->prn < 1 || rec->prn > GAL_NUM_PRN) return fail(GAL_E_INVAL, "gal_corr_from_epoch: prn %d (1..50)", rec->prn);
-    if (sample_offset < 0 || sample_offset > ((int64_t)1 << 32)) return fail(GAL_E_INVAL, "gal_corr_from_epoch: sample_offset outside 0..2^32");
-    if (!std::isfinite(sample_rate) || sample_rate <= 0.0 || !std::isfinite(rec->f_code) || !std::isfinite(rec->f_carr) ||
-        !std::isfinite(rec->code_phase0) || !std::isfinite(rec->carr_phase0))
-        return fail(GAL_E_INVAL, "gal_corr_from_epoch: a rate or phase is not finite, or sample_rate <= 0");
-    const double two32 = 4294967296.0;
-    const double dph = 2.0 * rec->f_code / sample_rate * two32, cdph = rec->f_carr / sample_rate * two32;
-    if (!(dph >= 0.0 && dph <= two32)) return fail(GAL_E_INVAL, "gal_corr_from_epoch: f_code %g outside [0, sample_rate / 2]", rec->f_code);
-    if (!(std::fabs(cdph) < 2147483647.5)) return fail(GAL_E_INVAL, "gal_corr_from_epoch: |f_carr| %g is not below sample_rate / 2", rec->f_carr);
-    if (!(rec->code_phase0 >= 0.0 && rec->code_phase0 < 3.0 * GAL_CODE_LEN))
-        return fail(GAL_E_INVAL, "gal_corr_from_epoch: code_phase0 %g outside [0, 3 x 4092)", rec->code_phase0);
-    out->prn = rec->prn;
-    out->code_dph = (uint64_t)llround(dph);
-    const unsigned __int128 p = (unsigned __int128)(uint64_t)llround(2.0 * rec->code_phase0 * two32) +
-                                (unsigned __int128)(uint64_t)sample_offset * out->code_dph;
-    out->code_ph0 = (uint64_t)(p % kCorrL);
-    out->carr_dph = (int32_t)llround(cdph);
-    out->carr_ph0 = 0;
-    if (rec->flags & GAL_CH_RESTART) {
-        const double fr = rec->carr_phase0 - std::floor(rec->carr_phase0);
-        out->carr_ph0 = (uint32_t)((uint64_t)llround(fr * two32) + (uint64_t)sample_offset * (uint64_t)(int64_t)out->carr_dph);
-    }
-    return GAL_OK;
-}
-
-int gal_corr_cn0(const int64_t *out_host, const gal_corr_req_t *req, int32_t k_prompt, int32_t k_noise, int32_t d, double sample_rate,
-                 double *cn0_dbhz, double *peak_ratio)
-{
-    if (!out_host || !req || !cn0_dbhz || !peak_ratio) return fail(GAL_E_INVAL, "gal_corr_cn0: null argument");
-    if (gal_synth_corr_out_bytes(req) == 0 || req->max_periods < 3 || req->code_dph == 0 || k_prompt < 0 || k_prompt >= req->n_delay ||
-        k_noise < 0 || k_noise >= req->n_delay || d < 0 || d >= req->n_dopp || !std::isfinite(sample_rate) || sample_rate <= 0.0)
-        return fail(GAL_E_INVAL, "gal_corr_cn0: a grid outside the caps, fewer than 3 periods, code_dph 0, an index outside the grid or a bad sample rate");
-    double pp = 0.0, pn = 0.0;
-    for (int m = 1; m < req->max_periods - 1; ++m) {
-        const int64_t *a = out_host + (((size_t)m * req->n_dopp + d) * req->n_delay + k_prompt) * 4;
-        const int64_t *b = out_host + (((size_t)m * req->n_dopp + d) * req->n_delay + k_noise) * 4;
-        for (int r = 0; r < 4; ++r) {
-            pp += (double)a[r] * (double)a[r];
-            pn += (double)b[r] * (double)b[r];
-        }
-    }
-    const int M = req->max_periods - 2;
-    pp /= M;
-    pn /= M;
-    *cn0_dbhz = 0.0;
-    *peak_ratio = pn > 0.0 ? pp / pn : 0.0;
-    if (!(pp > pn) || !(pn > 0.0)) return fail(GAL_E_INVAL, "gal_corr_cn0: no peak (Pp %g <= Pn %g)", pp, pn);
-    const double T = (double)kCorrL / (double)req->code_dph / sample_rate;
-    *cn0_dbhz = 10.0 * log10((pp - pn) / (pn * T / 2.0));
     return GAL_OK;
 }
 
