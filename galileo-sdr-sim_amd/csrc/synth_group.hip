@@ -16,7 +16,13 @@
 // the fixed-point DDA t = 2^20 + 512 + 2^-26 + 511 p advanced by t += 511 |d| (a double in [2^20, 2^21) is a fixed-point
 // number with 32 fraction bits: the high word is the table address, the low word the fraction of 511 p; a sample whose
 // fraction word is below 2^7, i.e. 511 p within 2^-26 of an integer, is UNDECIDED; the error of t against the sequential
-// phase is below 18 x 2^-33 + 2^-34 < 2^-28).  A lane that met an undecided sample appends its group to a list; k_repair_g
+// phase is below 18 x 2^-33 + 2^-34 < 2^-28).  The BOC(1,1) bin-table instances give the chip phase the same form (SG_FIX below): the
+// loader lane stores y_c + 2^20 (y_c < 8184 + 1008, so the biased phase stays below 2^20 + 9192, inside [2^20, 2^21)), the group's
+// fma rounds to the same 32 fraction bits -- two more roundings of at most 2^-33 each,
+//     Y_g = fma(16 g, s, y_c + 2^20)               |frac word of Y_g - sequential y| <= 2^-31 + 2^-32
+// -- and the high word IS the half-chip index (under the exponent field 0x41300000), the low word IS the fraction: no conversion.
+// The undecided band stays 2^-22 (1024 units of the word on either side of a threshold), the bins' RW_EDGE 2^-20.
+// A lane that met an undecided sample appends its group to a list; k_repair_g
 // walks each listed group's exact start state out of the same checkpoint (nco_walk.h: code_walk / carr_walk_track) and
 // replays its 16 samples x all channels with the reference's statements.  About 2000 of the 19.5 million groups of a 120 s
 // batch are listed (1.7e-4 of them for a chip threshold, 6e-6 for a carrier index).
@@ -68,6 +74,12 @@ using namespace galdev;
 #define SG_LUT_N 1152   // entries per carrier table: 512 (mirrored phase still negative) + 511 + 129 (behind a wrap inside a group)
 #define SG_AMB 128u
 #define SG_BIAS (1049088.0 + 1.4901161193847656250e-08)  // 2^20 + 512 + 2^-26
+#define SG_YBIAS 1048576.0   // 2^20: the bias of the fixed-point chip phase ...
+#define SG_YEXP 0x41300000u  // ... and the exponent field its high word carries above the 20 bits of the half-chip index
+#define SG_DW 1024u          // RW_DELTA = 2^-22 in units of the fraction word
+// the chip side of a group start in fixed point: the BOC(1,1) instances that look their pattern up in the bin table.  The bisection
+// instances (which compare with the float row s_thr) and CBOC (which also needs 6 A) keep the float form.
+#define SG_FIX(SIG, SEARCH) ((SIG) == 0 && !(SEARCH))
 #define SG_MAXCH 12     // channel positions of the instances for up to 12 channels (two blocks of 512 threads per CU) ...
 #define SG_MAXCH_WIDE 24  // ... and of the wide instances, 13 .. 24 positions in ONE launch (round 6: 24 stream rows = 56 KB of 133 KB
                           // of LDS, one block of 1024 threads per CU -- the same four waves per SIMD; rounds 3-5 ran such a batch as two
@@ -77,7 +89,7 @@ using namespace galdev;
 // fetches channel j's checkpoint of the NEXT chunk while the wave works on the current one) into the wave's own LDS slots, read
 // back by every lane as one-address reads.  No scalar registers, nothing loop-invariant for the compiler to hoist into them.
 struct SgRec {
-    double yc;   // code phase of the chunk's first sample (pre-check, :491), in half chips: 2 x
+    double yc;   // code phase of the chunk's first sample (pre-check, :491), in half chips: 2 x (SG_FIX instances: + 2^20)
     double pm;   // carrier phase there, MIRRORED: times the sign of the epoch's step (k_synth: ChanState::p)
     double s;    // code step in half chips per sample, 2 f_code delt
     double dabs; // |f_carr delt|
@@ -135,7 +147,8 @@ __device__ __forceinline__ void sg_part(int (&o)[16], uint32_t &amb, uint64_t &u
         // ---- phase A: the wave's records; approximate pre-check code phase at the group start; bin entry, stream words and
         // sign masks in flight
         int ic0[CNT];
-        float f[CNT];
+        [[maybe_unused]] float f[CNT];
+        [[maybe_unused]] uint32_t fw[CNT];
         uint2 be[CNT];
         uint32_t lo[CNT], hi[CNT], mask[CNT];
         double praw[CNT];
@@ -148,9 +161,16 @@ __device__ __forceinline__ void sg_part(int (&o)[16], uint32_t &amb, uint64_t &u
             const sg_u4 r0 = ((sg_lds_u4)(uintptr_t)(rec + j))[0], r1 = ((sg_lds_u4)(uintptr_t)(rec + j))[1];
             const uint32_t sa0 = *(sg_lds_u32)(uintptr_t)(sya + j);
             const double A = __builtin_fma(g16, sg_f64(r1.x, r1.y), sg_f64(r0.x, r0.y));
+            if constexpr (SG_FIX(SIG, SEARCH)) {
+                // the biased phase: high word = 0x41300000 + half-chip index, low word = the fraction in units of 2^-32
+                ic0[q] = (int)(uint32_t)(d2u(A) >> 32);
+                fw[q] = (uint32_t)d2u(A);
+                be[q] = s_bin[j * BPITCH + (fw[q] >> (32 - __builtin_ctz(BINS)))];
+            } else {
             ic0[q] = (int)A;  // < 8184 + 1008: the row continues behind the period's end (:491-507 is a matter of the signs)
             f[q] = (float)__builtin_amdgcn_fract(A);
-            if constexpr (!SEARCH) {
+            }
+            if constexpr (!SEARCH && !SG_FIX(SIG, SEARCH)) {
                 const int bi = (int)(f[q] * (float)BINS);
                 be[q] = s_bin[j * BPITCH + bi];
             }
@@ -160,14 +180,15 @@ __device__ __forceinline__ void sg_part(int (&o)[16], uint32_t &amb, uint64_t &u
                 f6[q] = (float)__builtin_amdgcn_fract(y6);
                 be6[q] = s_bin6[j * CB_BIN_PITCH + (int)(f6[q] * (float)CB_BINS)];
             }
-            const uint32_t *wp = s_str + j * SG_STR_PITCH + (ic0[q] >> 4);
+            // (fixed point: the word index is bits 4 .. 19 of the high word, the exponent field stays behind)
+            const uint32_t *wp = s_str + j * SG_STR_PITCH + (SG_FIX(SIG, SEARCH) ? (int)__builtin_amdgcn_ubfe((uint32_t)ic0[q], 4, 16) : (ic0[q] >> 4));
             lo[q] = wp[0];
             hi[q] = wp[1];
             // XOR mask of the data / secondary-code signs (:517-518) on the window's 16 half chips: the chunk's first symbol
             // up to the code wrap, its successor behind it -- one table row per pair of sign pairs, one entry per position of
             // the wrap relative to the window
             int pos;
-            asm("v_med3_i32 %0, %1, 0, 16" : "=v"(pos) : "v"(ic0[q] - (8184 - 16)));
+            asm("v_med3_i32 %0, %1, 0, 16" : "=v"(pos) : "v"(ic0[q] - (8184 - 16) - (SG_FIX(SIG, SEARCH) ? (int)SG_YEXP : 0)));
             mask[q] = *(sg_lds_u32)(uintptr_t)(sa0 + ((uint32_t)pos << 2));
             praw[q] = __builtin_fma(g16, sg_f64(r1.z, r1.w), sg_f64(r0.z, r0.w));
         }
@@ -197,6 +218,22 @@ __device__ __forceinline__ void sg_part(int (&o)[16], uint32_t &amb, uint64_t &u
                 M[q] = s_pat[j * 16 + id];
                 const bool near = !(up - f[q] >= RW_DELTA) | ((id > 0) & !(f[q] - lo >= RW_DELTA)) | !(f[q] >= RW_DELTA) | !(f[q] <= 1.0f - RW_DELTA);
                 undec |= __builtin_amdgcn_ballot_w64(near);
+            } else if constexpr (SG_FIX(SIG, SEARCH)) {
+                // be.x = threshold + delta as a fraction word, be.y = pattern offset below it | at or above it << 8 | decidable << 16
+                // (build_bins).  d = be.x - fraction: the borrow says "above the band" and selects the offset's byte, d <= 2 delta says
+                // "inside it"; an undecidable bin's zero byte 2 clears d.  ONE statement, in this order: a VALU read of VCC needs two
+                // wait states behind the VALU write of it (gfx940 and later), and nothing pads the inside of an asm string -- the
+                // mask and the shift count of phase C's v_alignbit_b32 (2 x the low bits of the half-chip index), neither of which
+                // touches VCC, are those two states.
+                uint32_t d, po, sh;
+                asm("v_sub_co_u32 %0, vcc, %3, %4\n\t"
+                    "v_and_b32_sdwa %0, %0, sext(%5) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2\n\t"
+                    "v_lshlrev_b32 %2, 1, %6\n\t"
+                    "v_cndmask_b32_sdwa %1, %5, %5, vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:BYTE_1"
+                    : "=&v"(d), "=&v"(po), "=&v"(sh) : "v"(be[q].x), "v"(fw[q]), "v"(be[q].y), "v"(ic0[q]) : "vcc");
+                ic0[q] = (int)sh;
+                M[q] = *reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(s_pat + j * 16) + po);
+                undec |= __builtin_amdgcn_ballot_w64(d <= 2u * SG_DW);
             } else {
             const float thr = __uint_as_float(be[q].x);
             const uint32_t po = be[q].y + (f[q] >= thr ? 16u : 0u);
@@ -211,7 +248,8 @@ __device__ __forceinline__ void sg_part(int (&o)[16], uint32_t &amb, uint64_t &u
         // ---- phase C: window (signs applied), spread
 #pragma unroll
         for (int q = 0; q < CNT; ++q) {
-            const uint32_t W = __builtin_amdgcn_alignbit(hi[q], lo[q], (uint32_t)ic0[q] << 1) ^ mask[q];
+            // (fixed point: phase B has doubled ic0 already)
+            const uint32_t W = __builtin_amdgcn_alignbit(hi[q], lo[q], SG_FIX(SIG, SEARCH) ? (uint32_t)ic0[q] : (uint32_t)ic0[q] << 1) ^ mask[q];
             if constexpr (SIG == 1) {
                 // fields (B != C, sign of C x secondary) per SAMPLE; the half chip of sample u is ic0 + u - (holds before u): its
                 // parity comes out of the hold masks.  X: the (B - C) factor of every sample as a signed 2-bit field; XB: the (B + C)
@@ -336,6 +374,7 @@ void k_synth_g(const DevPlan *__restrict__ Pd, SynGeom G, const uint8_t *__restr
     static_assert(NCH >= 1 && NCH <= SG_MAXCH_WIDE, "1..24 channel positions per launch");
     static_assert(SIG == 0 || NCH <= SG_MAXCH, "the CBOC mode is built for up to 12 positions per launch");
     static_assert(!SEARCH || (SIG == 0 && NCH <= SG_MAXCH), "the threshold search is built for BOC(1,1), up to 12 positions per launch");
+    static_assert(!SG_FIX(SIG, SEARCH) || (RW_BINS & (RW_BINS - 1)) == 0, "the fixed-point bin index is the top bits of the fraction word");
     constexpr int MC = NCH <= SG_MAXCH ? SG_MAXCH : SG_MAXCH_WIDE;  // positions the per-wave records are laid out for
     // CBOC keeps two bin tables per channel (chip holds, half-period parity) of 64 bins each, as in k_synth
     constexpr int BINS = SIG ? CB_BINS : RW_BINS, BPITCH = SIG ? CB_BIN_PITCH : RW_BIN_PITCH;
@@ -536,7 +575,7 @@ void k_synth_g(const DevPlan *__restrict__ Pd, SynGeom G, const uint8_t *__restr
     }
     __syncthreads();
     // ---- step B: the bin tables (NCH x (BINS + 1) entries) and the 16 patterns of each channel
-    auto build_bins = [&](uint2 *bins, const float *thrs, const int nbins, const int pitch, const uint32_t unit) {
+    auto build_bins = [&](uint2 *bins, const float *thrs, const int nbins, const int pitch, const uint32_t unit, const bool fix = false) {
         for (int t = tid; t < NCH * (nbins + 1); t += nthr) {
             const int j = t / (nbins + 1), b = t - j * (nbins + 1);
             const float lo = (float)b * (1.0f / (float)nbins) - RW_EDGE, hi = (float)(b + 1) * (1.0f / (float)nbins) + RW_EDGE;
@@ -549,6 +588,23 @@ void k_synth_g(const DevPlan *__restrict__ Pd, SynGeom G, const uint8_t *__restr
             idb += th[idb] < lo ? 1 : 0;
             const float t0 = th[idb], t1 = idb < 15 ? th[idb + 1] : 2.0f;
             int cnt = (t0 < hi) + (t1 < hi);
+            if (fix) {
+                // The entry of the fixed-point compare (sg_part, phase B), same cases as the float entry below: x = threshold + 2^-22 in
+                // units of 2^-32 (mod 2^32), y = pattern offset below the threshold | at or above it << 8 | decidable ? 0xff << 16 : 0
+                // (an undecidable bin -- two thresholds, a pattern threshold beside 0 or 1, entry `nbins` -- lists every group: its x
+                // does not matter).  No threshold: x half a turn away from the bin, never close, both offsets the same.  Bin 0
+                // against 0: x = delta, nothing lies below, what lies above the band takes the bin's own pattern; the last bin against
+                // 1 = 2^32: x wraps to delta, every fraction of the bin is "above" x and takes the pattern BELOW 1.  A float
+                // threshold inside a bin is a multiple of 2^-32 below 1: scaling and conversion are exact.
+                const bool edge = b == 0 || b == nbins - 1, has = cnt == 1 && !edge, on = j < nact;
+                const uint32_t o = on ? (uint32_t)idb * unit : 0u;
+                const uint32_t far = ((uint32_t)b << (32 - __builtin_ctz(RW_BINS))) ^ 0x80000000u;  // (fix: the table has RW_BINS bins)
+                const uint32_t x = !on ? far : has ? (uint32_t)(t0 * 4294967296.0f) + SG_DW
+                                   : edge ? SG_DW : far;
+                const bool und = on && (cnt >= 2 || b == nbins || (edge && cnt));
+                bins[j * pitch + b] = make_uint2(x, o | ((has && on ? o + unit : o) << 8) | (und ? 0u : 0xff0000u));
+                continue;
+            }
             float thr = t0 < hi ? t0 : 4.0f;  // 4: "no threshold near this bin" -- never reached, never close
             // 0 and 1 are thresholds too -- of sample 0's own half chip (half period), which the approximate phase decides only away
             // from them (k_synth knows its group-start phase exactly): bin 0 compares with 0 (never below it: the pattern offset
@@ -562,7 +618,7 @@ void k_synth_g(const DevPlan *__restrict__ Pd, SynGeom G, const uint8_t *__restr
             bins[j * pitch + b] = make_uint2(__float_as_uint(thr), off);
         }
     };
-    if constexpr (!SEARCH) build_bins(s_bin, s_thr, BINS, BPITCH, 16u);
+    if constexpr (!SEARCH) build_bins(s_bin, s_thr, BINS, BPITCH, 16u, SG_FIX(SIG, SEARCH));
     if constexpr (SIG == 1) {
         build_bins(s_bin6, s_thr6, CB_BINS, CB_BIN_PITCH, 4u);
         for (int t = tid; t < NCH * 16; t += nthr) {
@@ -674,6 +730,7 @@ void k_synth_g(const DevPlan *__restrict__ Pd, SynGeom G, const uint8_t *__restr
         // (idle positions: phases far from every boundary the kernel looks at -- their zero checkpoints would sit ON one, 511 p = 0,
         // and list every group of the epoch)
         r.yc = onl ? x + x : 0.5;
+        if constexpr (SG_FIX(SIG, SEARCH)) r.yc += SG_YBIAS;  // (x + x is exact, the bias rounds once: at most 2^-33)
         r.pm = onl ? u2d(d2u(lp) ^ ((uint64_t)dsgnl << 32)) : 0.25;
         if (onl && dabsl == 0.0) {
             // a carrier that stands still (step exactly 0: `p += 0; p -= (long)p` leaves every phase of the epoch at the checkpoint's):
@@ -836,8 +893,9 @@ __global__ __launch_bounds__(256) void k_repair_g(DevPlan P, SynGeom G, uint32_t
                 // ... and both chains walked on to the END of the chunk: they must arrive at the next checkpoint, bit for bit (the
                 // end-of-epoch state behind the last chunk).  The listed groups are scattered over the batch by the bits of the
                 // phases, so this is a random sample of ~20 000 (chunk, channel) pairs per 120 s batch -- one more check beside
-                // k_verify (synth_kernels.hip), which re-walks every leg of BOTH chains in every batch of this kernel family (an eighth
-                // per batch under GAL_CFG_VERIFY_SAMPLED).  A mismatch ends the batch in gal_synth_finish's repair path.
+                // k_verify (synth_kernels.hip), the ONE launch that re-walks every leg of the code chain and of the carrier chain in
+                // every batch of this kernel family (an eighth per batch under GAL_CFG_VERIFY_SAMPLED).  A mismatch ends the batch in
+                // gal_synth_finish's repair path.
                 int nR = G.N - c * G.R;
                 nR = nR > G.R ? G.R : nR;
                 const int rem = nR - 16 * g;
