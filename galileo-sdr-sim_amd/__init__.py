@@ -22,6 +22,7 @@ from .synth import (  # noqa: F401
     GAL_IQ_IBYTE,
     GAL_IQ_ISHORT,
     IQ_FORMATS,
+    SCINT_DTYPE,
     GalSynthError,
     SynthEngine,
     corr_cn0,
@@ -40,6 +41,9 @@ from .synth import (  # noqa: F401
     osc_lo_step,
     osc_make,
     pack_page,
+    scint_check,
+    scint_make,
+    scint_rows,
     tables,
     unpack_page,
 )

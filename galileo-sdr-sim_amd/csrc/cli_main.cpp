@@ -240,6 +240,7 @@ struct Run {
     std::vector<gal_iq_echo_t> mp_rows;  // ... its echo table [epochs][echoes in view] ...
     std::vector<int32_t> slot_of;        // ... and per echo in view its slot and its line of the file
     std::vector<const EchoSpec *> spec_of;
+    std::vector<gal_iq_scint_t> sc_rows;  // --scint: the batch's rows [epochs][slots]
     gal_corr_req_t mon_shape;  // what every monitor request shares
     MonSummary mon_sum[GAL_NUM_PRN + 1];
     uint64_t agc_logged = 0;  // blocks written to the log
@@ -421,8 +422,18 @@ int synth_mpath(Run &r, const RowRing::Buf &rows, int n, int16_t *d_iq)
                                                &r.mp_rows[(size_t)e * n_echo + k]);
             if (rc != GAL_OK) return rc;
         }
-    return gal_synth_run_mpath(r.eng, rec, n, r.have_state ? r.state.data() : nullptr, r.mp_gains.data(), r.slot_of.data(), r.mp_rows.data(), n_echo,
-                               d_iq, r.state.data());
+    // --scint: the row of the PRN a slot carries in the epoch; every other record the identity
+    if (r.c.sc_on()) {
+        gal_iq_scint_t ident;
+        memset(&ident, 0, sizeof(ident));
+        ident.seed = 1, ident.node_len = GAL_SCINT_MIN_NODE, ident.a_q12 = 4096;
+        r.sc_rows.assign((size_t)n * S, ident);
+        for (size_t i = 0; i < (size_t)n * S; ++i)
+            for (const ScintSpec &s : r.c.scints)
+                if (rec[i].prn == s.prn) r.sc_rows[i] = s.row;
+    }
+    return gal_synth_run_scint(r.eng, rec, n, r.have_state ? r.state.data() : nullptr, r.mp_gains.data(), r.slot_of.data(), r.mp_rows.data(), n_echo,
+                               r.c.sc_on() ? r.sc_rows.data() : nullptr, (uint64_t)r.emitted * (uint64_t)r.cfg.samples_per_epoch, d_iq, r.state.data());
 }
 
 // ---- the output chain behind a batch, on the engine's stream ------------------------------------------------------------------------------------
@@ -506,8 +517,8 @@ int run_loop(Run &r, RowRing &ring, SlotPair &sp, int total, Clock::time_point t
     const Config &c = r.c;
     const bool batch_timing = getenv("GAL_CLI_TIMING") != nullptr;
     const auto ms_since = [](Clock::time_point a) { return std::chrono::duration<double, std::milli>(Clock::now() - a).count(); };
-    const auto synth = c.mp_on() ? synth_mpath : c.power_on ? synth_gains : synth_plain;
-    const bool finished_inside = c.mp_on() || c.power_on;  // run_gains / run_mpath return with every group finished
+    const auto synth = c.parts_on() ? synth_mpath : c.power_on ? synth_gains : synth_plain;
+    const bool finished_inside = c.parts_on() || c.power_on;  // run_gains / run_mpath return with every group finished
     int cur = 0;
     for (int ri = 0; r.emitted < total && !sp.io_error && !g_stop; cur ^= 1, ri = (ri + 1) % RowRing::kBufs) {
         const auto tb0 = Clock::now();
@@ -558,7 +569,7 @@ int run_loop(Run &r, RowRing &ring, SlotPair &sp, int total, Clock::time_point t
         if (batch_timing)
             fprintf(stderr, "[timing] batch at %7.2f ms: %3d epochs, waited %.2f ms for rows, %.2f for a free slot, %s %.2f\n",
                     std::chrono::duration<double, std::milli>(tb0 - t_start).count(), n, tb_rows, tb_slot - tb_rows,
-                    c.mp_on()    ? "run_mpath (every group's plan + execute + finish, the echo pass enqueued)"
+                    c.parts_on() ? "run_scint (every group's plan + execute + finish, scintillation and the echo pass enqueued)"
                     : c.power_on ? "run_gains (every group's plan + execute + finish, the sum enqueued)"
                                  : "plan + execute + finish",
                     tb_synth - tb_slot);

@@ -286,6 +286,67 @@ bool load_multipath(const char *path, std::vector<EchoSpec> *out, std::string *w
     return ok;
 }
 
+bool load_scint(const char *path, std::vector<ScintSpec> *out, std::string *why)
+{
+    FILE *fp = fopen(path, "r");
+    if (!fp) {
+        *why = "cannot read it";
+        return false;
+    }
+    char line[1024];
+    int lineno = 0;
+    bool seen[GAL_NUM_PRN + 1] = {false}, ok = true;
+    while (ok && fgets(line, sizeof(line), fp)) {
+        ++lineno;
+        const char *p = line;
+        while (*p == ' ' || *p == '\t') ++p;
+        if (*p == '#' || *p == '\n' || *p == '\r' || !*p) continue;
+        double v[3] = {0, 0, 0};
+        int n = 0;
+        for (; n < 3; ++n) {
+            char *end = nullptr;
+            v[n] = strtod(p, &end);
+            if (end == p || !std::isfinite(v[n])) break;
+            p = end;
+            while (*p == ' ' || *p == '\t') ++p;
+            if (*p != ',') {
+                ++n;
+                break;
+            }
+            ++p;
+        }
+        while (*p == ' ' || *p == '\t' || *p == '\n' || *p == '\r') ++p;
+        if (*p == '#') p = "";  // a comment behind the values
+        const std::string at = "line " + std::to_string(lineno);
+        if (n < 3 || *p) {
+            *why = at + " is not prn,s4,tau0_s";
+            ok = false;
+        } else if (v[0] != floor(v[0]) || v[0] < 1 || v[0] > GAL_NUM_PRN) {
+            *why = at + ": PRN outside 1.." + std::to_string(GAL_NUM_PRN);
+            ok = false;
+        } else if (seen[(int)v[0]]) {
+            *why = at + ": a second line for PRN " + std::to_string((int)v[0]);
+            ok = false;
+        } else if (!(v[1] >= 0.0 && v[1] <= 1.0)) {
+            *why = at + ": s4 outside 0..1";
+            ok = false;
+        } else {
+            ScintSpec s;
+            memset(&s, 0, sizeof(s));
+            s.prn = (int)v[0];
+            s.s4 = v[1], s.tau0_s = v[2];
+            seen[s.prn] = true;
+            out->push_back(s);
+        }
+    }
+    fclose(fp);
+    if (ok && out->empty()) {
+        *why = "it holds no satellite";
+        ok = false;
+    }
+    return ok;
+}
+
 // ---- refusing and parsing: the message stays at the call site ------------------------------------------------------------------------------
 // the whole string is one number (no range: --cn0 leaves that to the library)
 bool parse_double(const char *s, double *v)
@@ -357,7 +418,8 @@ struct Args {
     const char *iq_format = "ishort", *iq_shift = nullptr, *monitor = nullptr, *monitor_every = nullptr, *fir = nullptr, *fir_lowpass = nullptr,
                *oversample = nullptr, *multipath = nullptr, *agc = nullptr, *agc_block = nullptr, *agc_window = nullptr, *agc_init = nullptr,
                *agc_log = nullptr, *i2bit_thr = nullptr, *antenna = nullptr, *cn0 = nullptr, *noise_seed = nullptr, *noise_stream = nullptr,
-               *signal_gain = nullptr, *lo_offset = nullptr, *phase_noise = nullptr, *osc_seed = nullptr, *osc_stream = nullptr;
+               *signal_gain = nullptr, *lo_offset = nullptr, *phase_noise = nullptr, *osc_seed = nullptr, *osc_stream = nullptr,
+               *scint = nullptr, *scint_seed = nullptr, *scint_site = nullptr;
     std::vector<const char *> prn_power, jam;
     long agc_window_n = 8;
     double agc_target = 0.0, agc_init_rms = -1.0;  // (0 / < 0: the defaults, known once shift and sigma are)
@@ -396,6 +458,8 @@ const OptRow kOptions[] = {
     {"i2bit-threshold", ARG, OPT_STRING + 16, true, &Args::i2bit_thr}, {"multipath", ARG, OPT_STRING + 17, true, &Args::multipath},
     {"lo-offset", ARG, OPT_STRING + 18, true, &Args::lo_offset}, {"phase-noise", ARG, OPT_STRING + 19, true, &Args::phase_noise},
     {"osc-seed", ARG, OPT_STRING + 20, true, &Args::osc_seed}, {"osc-stream", ARG, OPT_STRING + 21, false, &Args::osc_stream},
+    {"scint", ARG, OPT_STRING + 22, true, &Args::scint}, {"scint-seed", ARG, OPT_STRING + 23, true, &Args::scint_seed},
+    {"scint-site", ARG, OPT_STRING + 24, false, &Args::scint_site},
 };
 
 // the command line into Args and the Config's plain fields; every option with to_children also into c->child_args
@@ -567,16 +631,14 @@ void cfg_signals(Args &a, Config &c)
             a.antenna ? a.antenna : "isotropic", a.prn_power.size(), a.prn_power.size() == 1 ? "" : "s", power_peak, 20.0 * log10(power_peak));
     }
     // a satellite with echoes can reach 1 + sum alpha times its own amplitude: the largest such sum
-    double echo_peak = 1.0;
+    double echo_peak = 1.0, echo_sum[GAL_NUM_PRN + 1] = {0};
     if (a.multipath) {
         if (!load_multipath(a.multipath, &c.echoes, &why)) die("ERROR: --multipath %s: %s.\n", a.multipath, why.c_str());
-        double sum[GAL_NUM_PRN + 1] = {0};
         for (const EchoSpec &e : c.echoes) {
-            sum[e.prn] += pow(10.0, e.rel_db / 20.0);
-            echo_peak = 1.0 + sum[e.prn] > echo_peak ? 1.0 + sum[e.prn] : echo_peak;
+            echo_sum[e.prn] += pow(10.0, e.rel_db / 20.0);
+            echo_peak = 1.0 + echo_sum[e.prn] > echo_peak ? 1.0 + echo_sum[e.prn] : echo_peak;
         }
     }
-    a.sig_peak = 4100.0 * power_peak * echo_peak;
     long v = 0;
     if (a.oversample && !parse_long(a.oversample, 2, 15, &v))
         die("ERROR: --oversample '%s' out of range (2..15: the engine synthesises at up to 40 MS/s).\n", a.oversample);
@@ -592,6 +654,28 @@ void cfg_signals(Args &a, Config &c)
     }
     if (c.mp_on() && echo_peak > 1.0)
         say(c, "Multipath: %zu echo%s; a satellite reaches up to %.3f times its own amplitude\n", c.echoes.size(), c.echoes.size() == 1 ? "" : "es", echo_peak);
+    // --scint: a scintillating satellite is taken at (A + 4 B) / 4096 times its own amplitude (the direct component plus four sigma of
+    // a scattered one), its echoes with it: the largest of (A + 4 B) / 4096 x (1 + sum alpha) over the PRNs, and of echo_peak
+    double sat_peak = echo_peak;
+    if (!a.scint && (a.scint_seed || a.scint_site)) die("ERROR: --scint-seed and --scint-site need --scint <file>.\n");
+    if (a.scint) {
+        if (!load_scint(a.scint, &c.scints, &why)) die("ERROR: --scint %s: %s.\n", a.scint, why.c_str());
+        uint64_t seed = 1;
+        uint32_t site = 0;
+        if (a.scint_seed && !parse_u64(a.scint_seed, &seed)) die("ERROR: --scint-seed '%s' is not an unsigned 64-bit integer.\n", a.scint_seed);
+        if (a.scint_site && (!parse_u32(a.scint_site, &site) || site >> 24)) die("ERROR: --scint-site '%s' is not an integer in 0..2^24-1.\n", a.scint_site);
+        for (ScintSpec &s : c.scints) {
+            if (gal_synth_scint_make(s.s4, s.tau0_s, rate, &s.row) != GAL_OK) die("ERROR: --scint %s, PRN %d: %s\n", a.scint, s.prn, gal_synth_last_error());
+            s.row.seed = seed;
+            s.row.stream = (site << 8) | (uint32_t)s.prn;
+            const double f = (s.row.a_q12 + 4.0 * s.row.b_q12) / 4096.0 * (1.0 + echo_sum[s.prn]);
+            sat_peak = f > sat_peak ? f : sat_peak;
+            say(c, "Scintillation: PRN %d, S4 %g, tau0 %g s -> A %u, B %u, L %u (tau0 %.6g s at %g MS/s), seed %llu, stream %u\n", s.prn, s.s4, s.tau0_s,
+                s.row.a_q12, s.row.b_q12, s.row.node_len, 8.0 * s.row.node_len / rate, rate / 1e6, (unsigned long long)s.row.seed, s.row.stream);
+        }
+        if (sat_peak > 1.0) say(c, "Scintillation: a satellite is taken at up to %.3f times its own amplitude\n", sat_peak);
+    }
+    a.sig_peak = 4100.0 * power_peak * sat_peak;
 }
 
 void given_gain(Args &a)
@@ -833,7 +917,7 @@ int run_sites(const char *self, const Config &c)
     int n_gpus = c.sites_gpus, per_gpu = c.sites_per_gpu;
     const int udp_base = c.udp_given ? c.sc.udp_port : 0;
     const double bytes_per_sample = (double)c.out_bytes(4) / 4.0;
-    const bool noise_on = c.noise_on, osc_on = c.osc_on;
+    const bool noise_on = c.noise_on, osc_on = c.osc_on, sc_on = c.sc_on();
     std::vector<Site> sites;
     FILE *fp = fopen(sites_file, "r");
     if (!fp) {
@@ -907,6 +991,10 @@ int run_sites(const char *self, const Config &c)
             }
             if (osc_on) {  // ... nor their oscillator's phase noise
                 args.push_back("--osc-stream");
+                args.push_back(std::to_string(next));
+            }
+            if (sc_on) {  // ... nor their satellites' fading
+                args.push_back("--scint-site");
                 args.push_back(std::to_string(next));
             }
             if (monitor_file) {  // site i: <file>.site<i>

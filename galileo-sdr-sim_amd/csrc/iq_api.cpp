@@ -1,5 +1,5 @@
 // iq_api.cpp -- the output chain's half of the C ABI (include/galsynth.h): every pass over the finished int16 stream -- formats, noise
-// floor, interference, per-satellite gains, multipath, FIR, decimating FIR, AGC, oscillator -- and the correlator bank, over the kernels of
+// floor, interference, per-satellite gains, multipath, scintillation, FIR, decimating FIR, AGC, oscillator -- and the correlator bank, over the kernels of
 // csrc/iq_*.hip.  Host-side plumbing only: validation, the stages' device state, kernel sequencing.  The handle itself, plan, execute
 // and finish are synth_api.cpp's; synth_handle.h is what the two share.  Nothing here depends on GAL_TEST_HOOKS: one object serves
 // libgalsynth.so and libgalsynth_hooks.so.
@@ -31,6 +31,7 @@ uint64_t galk_agc_scratch_bytes(uint64_t n, uint32_t off0, uint32_t block_len);
 hipError_t galk_launch_iq_osc(const int16_t *in, int16_t *out, uint64_t n, uint64_t first_sample, uint64_t n0, const gal_iq_osc_t *p,
                               const long long *state_in, long long *state_out, void *scratch, unsigned long long *sat, hipStream_t st);
 uint64_t galk_osc_scratch_bytes(uint64_t n);
+hipError_t galk_launch_iq_scint(const void *jobs_dev, int n_jobs, uint64_t max_n, unsigned long long *sat, hipStream_t st);
 hipError_t galk_launch_iq_echo(const int16_t *const *parts_dev, const int16_t *const *hist_in_dev, int16_t *const *hist_out_dev, const int *gain_dev,
                                const void *rows_dev, const int *part_of_dev, int n_parts, int n_echo, int n_epochs, int samples_per_epoch, int wide,
                                int16_t *out, unsigned long long *sat, hipStream_t st);
@@ -1002,11 +1003,131 @@ int gal_synth_iq_osc(gal_synth_t *h, const int16_t *in_dev, size_t n_samples, in
     return GAL_OK;
 }
 
-// gal_synth_run_gains (n_echo = 0) and gal_synth_run_mpath: the slot groups, one synthesis run per group, then the weighted sum or the
-// echo pass
+// ---- per-satellite ionospheric scintillation (iq_scint.hip) ------------------------------------------------------------------------
+int gal_synth_scint_check(const gal_iq_scint_t *row)
+{
+    const char *who = "gal_synth_scint_check";
+    if (!row) return fail(GAL_E_INVAL, "%s: null argument", who);
+    if (row->reserved != 0) return fail(GAL_E_INVAL, "%s: reserved %u (0)", who, row->reserved);
+    if (row->node_len < GAL_SCINT_MIN_NODE || row->node_len > GAL_SCINT_MAX_NODE)
+        return fail(GAL_E_INVAL, "%s: node_len %u (%d..%u)", who, row->node_len, GAL_SCINT_MIN_NODE, GAL_SCINT_MAX_NODE);
+    if (row->a_q12 > 4096 || row->b_q12 > 4096) return fail(GAL_E_INVAL, "%s: a_q12 %u, b_q12 %u (0..4096)", who, row->a_q12, row->b_q12);
+    return GAL_OK;
+}
+
+static bool scint_identity(const gal_iq_scint_t &r) { return r.a_q12 == 4096 && r.b_q12 == 0; }
+
+int gal_synth_scint_make(double s4, double tau0_s, double sample_rate, gal_iq_scint_t *out)
+{
+    const char *who = "gal_synth_scint_make";
+    if (!out) return fail(GAL_E_INVAL, "%s: null argument", who);
+    if (!std::isfinite(s4) || !std::isfinite(tau0_s) || !std::isfinite(sample_rate)) return fail(GAL_E_INVAL, "%s: an argument is not finite", who);
+    if (!(s4 >= 0.0 && s4 <= 1.0) || !(sample_rate > 0.0)) return fail(GAL_E_INVAL, "%s: s4 %g (0..1), sample rate %g (> 0)", who, s4, sample_rate);
+    const double lv = tau0_s * sample_rate / 8.0;
+    if (!(lv >= 0.0 && lv < 4294967296.0)) return fail(GAL_E_INVAL, "%s: tau0 %g s gives no node_len in %d..%u", who, tau0_s, GAL_SCINT_MIN_NODE, GAL_SCINT_MAX_NODE);
+    const long long L = llround(lv);
+    if (L < GAL_SCINT_MIN_NODE || L > (long long)GAL_SCINT_MAX_NODE)
+        return fail(GAL_E_INVAL, "%s: tau0 %g s at %g S/s gives node_len %lld (%d..%u)", who, tau0_s, sample_rate, L, GAL_SCINT_MIN_NODE, GAL_SCINT_MAX_NODE);
+    const int32_t *ht = gal_tables_scint();
+    int64_t h2 = 0;
+    for (int t = 0; t < 32; ++t) h2 += (int64_t)ht[t] * ht[t];
+    const double v = ((double)h2 / 1073741824.0) * ((double)gauss_m2() / 36028797018963968.0);  // (H2 / 2^30) x (M2 / 2^55)
+    gal_iq_scint_t r;
+    memset(&r, 0, sizeof(r));
+    r.seed = 1;
+    r.node_len = (uint32_t)L;
+    if (s4 == 0.0) {
+        r.a_q12 = 4096;
+    } else if (s4 == 1.0) {
+        r.b_q12 = (uint16_t)llround(4096.0 * sqrt(1.0 / (2.0 * v)));
+    } else {
+        const double m = 1.0 / (s4 * s4), q = sqrt(m * m - m), K = q / (m - q);
+        r.a_q12 = (uint16_t)llround(4096.0 * sqrt(K / (K + 1.0)));
+        r.b_q12 = (uint16_t)llround(4096.0 * sqrt(1.0 / (2.0 * (K + 1.0) * v)));
+    }
+    *out = r;
+    return GAL_OK;
+}
+
+// one job as k_iq_scint reads it (iq_scint.hip: struct ScintJob)
+struct ScintJobDev {
+    const int16_t *in;
+    int16_t *out;
+    uint64_t n, first;
+    uint32_t k0, k1, stream, L, R;
+    int32_t A, B;
+    uint32_t pad;
+};
+static_assert(sizeof(ScintJobDev) == 64, "iq_scint.hip reads 64 bytes per job");
+
+int gal_synth_iq_scint(gal_synth_t *h, const gal_scint_job_t *jobs, int32_t n_jobs)
+{
+    const char *who = "gal_synth_iq_scint";
+    if (!h) return fail(GAL_E_INVAL, "null handle");
+    if (!jobs || n_jobs < 1 || n_jobs > GAL_SCINT_MAX_JOBS) return fail(GAL_E_INVAL, "%s: null argument or n_jobs %d (1..%d)", who, n_jobs, GAL_SCINT_MAX_JOBS);
+    for (int k = 0; k < n_jobs; ++k) {
+        const gal_scint_job_t &j = jobs[k];
+        GAL_TRY(check_aligned(who, j.in_dev, k));
+        GAL_TRY(check_aligned(who, j.out_dev, k));
+        GAL_TRY(gal_synth_scint_check(&j.row));
+        if (j.n_samples >> 41) return fail(GAL_E_INVAL, "%s: n_samples of job %d must be below 2^41", who, k);
+        if (j.first_sample >> 62) return fail(GAL_E_INVAL, "%s: first_sample of job %d must be below 2^62", who, k);
+    }
+    for (int k = 0; k < n_jobs; ++k) {
+        const gal_scint_job_t &j = jobs[k];
+        const size_t bytes = 4 * (size_t)j.n_samples;
+        if (bytes == 0) continue;
+        if (j.in_dev != j.out_dev && ranges_overlap(j.in_dev, bytes, j.out_dev, bytes))
+            return fail(GAL_E_INVAL, "%s: input and output of job %d overlap (only exactly in place may)", who, k);
+        for (int i = 0; i < n_jobs; ++i) {  // the output of job k against the buffers of every other job
+            const size_t other = 4 * (size_t)jobs[i].n_samples;
+            if (i == k || other == 0) continue;
+            if (ranges_overlap(j.out_dev, bytes, jobs[i].in_dev, other) || ranges_overlap(j.out_dev, bytes, jobs[i].out_dev, other))
+                return fail(GAL_E_INVAL, "%s: the output of job %d meets a buffer of job %d", who, k, i);
+        }
+        GAL_TRY(check_in_flight(who, h, j.in_dev, bytes, "input of"));
+        GAL_TRY(check_in_flight(who, h, j.out_dev, bytes, "output of"));
+    }
+    hipStream_t st;
+    GAL_TRY(enter(h, &st));
+    HIP_TRY(h->scint.sync.wait());  // one table per handle: the call before has read it
+    uint64_t cap = 0;
+    const int rc = h->scint.table.reserve(sizeof(ScintJobDev) * GAL_SCINT_MAX_JOBS, 0, true, h->scint.sync, &cap);
+    if (rc == GAL_E_NOMEM) return fail(GAL_E_NOMEM, "%s: the job table of %zu bytes could not be allocated", who, (size_t)cap);
+    if (rc) return rc;
+    ScintJobDev *const tab = (ScintJobDev *)h->scint.table.host;
+    int n = 0;
+    uint64_t max_n = 0;
+    for (int k = 0; k < n_jobs; ++k) {
+        const gal_scint_job_t &j = jobs[k];
+        if (j.n_samples == 0 || (scint_identity(j.row) && j.in_dev == j.out_dev)) continue;  // nothing to do
+        ScintJobDev &d = tab[n++];
+        d.in = j.in_dev;
+        d.out = j.out_dev;
+        d.n = j.n_samples;
+        d.first = j.first_sample;
+        d.k0 = (uint32_t)j.row.seed;
+        d.k1 = (uint32_t)(j.row.seed >> 32);
+        d.stream = j.row.stream;
+        d.L = j.row.node_len;
+        d.R = (uint32_t)(4294967296ull / j.row.node_len);
+        d.A = j.row.a_q12;
+        d.B = j.row.b_q12;
+        d.pad = 0;
+        max_n = std::max(max_n, d.n);
+    }
+    if (n == 0) return GAL_OK;
+    HIP_TRY(hipMemcpyAsync(h->scint.table.dev, tab, sizeof(ScintJobDev) * (size_t)n, hipMemcpyHostToDevice, st));
+    HIP_TRY(galk_launch_iq_scint(h->scint.table.dev, n, max_n, h->d_iq_sat, st));
+    HIP_TRY(h->scint.sync.mark(st));
+    return GAL_OK;
+}
+
+// gal_synth_run_gains (n_echo = 0), gal_synth_run_mpath and gal_synth_run_scint (scint_rows != null): the slot groups, one synthesis
+// run per group, the scintillation of the parts that have one, then the weighted sum or the echo pass
 static int run_groups(const char *who, gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_epochs, const gal_chan_state_t *state_in,
                       const uint16_t *gain_q7, const int32_t *slot_of_echo, const gal_iq_echo_t *echo_rows, int32_t n_echo, int16_t *iq_dev,
-                      gal_chan_state_t *state_out)
+                      gal_chan_state_t *state_out, const gal_iq_scint_t *scint_rows = nullptr, uint64_t first_sample = 0)
 {
     if (!h || !params || !gain_q7 || !iq_dev || n_epochs < 1) return fail(GAL_E_INVAL, "%s: null argument or n_epochs %d (>= 1)", who, n_epochs);
     if ((uintptr_t)iq_dev & 15) return fail(GAL_E_INVAL, "%s: iq_dev must be 16-byte aligned", who);
@@ -1030,6 +1151,12 @@ static int run_groups(const char *who, gal_synth_t *h, const gal_chan_epoch_t *p
     // a slot that carries an echo is a group of its own, idle or not: its part is what the echo delays, its line follows the slot
     std::vector<char> solo(S, 0);
     for (int r = 0; r < n_echo; ++r) solo[slot_of_echo[r]] = 1;
+    const std::vector<char> has_echo = solo;
+    // ... and so is a slot that scintillates in any epoch of the batch: its part is what gal_synth_iq_scint turns
+    std::vector<char> fades(S, 0);
+    bool any_fade = false;
+    for (size_t i = 0; scint_rows && i < (size_t)E * S; ++i)
+        if (!scint_identity(scint_rows[i])) fades[i % S] = solo[i % S] = 1, any_fade = true;
     for (int s = 0; s < S; ++s) {
         bool active = solo[s];
         for (int e = 0; e < E && !active; ++e) active = params[(size_t)e * S + s].prn > 0;
@@ -1052,16 +1179,17 @@ static int run_groups(const char *who, gal_synth_t *h, const gal_chan_epoch_t *p
             if (params[(size_t)e * S + s].prn > 0) groups[k].g[e] = gain_q7[(size_t)e * S + s];
     }
     const int n_parts = groups.empty() ? 1 : (int)groups.size();  // (an empty sky: one run of nothing)
-    bool unity = n_parts == 1 && n_echo == 0;  // one part at gain 128 wherever it is not zero: y = x, the run goes straight into iq_dev
+    bool unity = n_parts == 1 && n_echo == 0 && !any_fade;  // one part at gain 128 wherever it is not zero: y = x, the run goes straight into iq_dev
     if (!groups.empty())
         for (int e = 0; e < E && unity; ++e) unity = groups[0].g[e] < 0 || groups[0].g[e] == GAL_GAIN_UNITY;
     const size_t bytes = (size_t)E * (size_t)h->cfg.samples_per_epoch * 4;
     // the weighted sum of the call before may still read the scratch buffers: wait for it here, whatever stream the handle is on now
     // (on one stream the runs below would order behind it by themselves)
-    if (h->gain.sync.pending || h->mp.sync.pending) {
+    if (h->gain.sync.pending || h->mp.sync.pending || h->scint.sync.pending) {
         HIP_TRY(hipSetDevice(h->device));
         HIP_TRY(h->gain.sync.wait());
         HIP_TRY(h->mp.sync.wait());
+        HIP_TRY(h->scint.sync.wait());
     }
     h->gain_runs = 0;
     if (!unity && bytes * (size_t)n_parts > h->own_parts_bytes) {
@@ -1095,6 +1223,34 @@ static int run_groups(const char *who, gal_synth_t *h, const gal_chan_epoch_t *p
         for (int s = 0; s < S; ++s)
             if (group_of[s] == k || (k == 0 && group_of[s] < 0)) st_all[s] = st_k[s];
     }
+    if (any_fade) {
+        // one job per slot and maximal run of epochs with an equal row, in place on the slot's part; all jobs in one call (of 64)
+        const uint64_t spe = (uint64_t)h->cfg.samples_per_epoch;
+        std::vector<gal_scint_job_t> jobs;
+        for (int s = 0; s < S; ++s) {
+            if (!fades[s]) continue;
+            for (int e0 = 0, e1; e0 < E; e0 = e1) {
+                const gal_iq_scint_t &row = scint_rows[(size_t)e0 * S + s];
+                for (e1 = e0 + 1; e1 < E && !memcmp(&scint_rows[(size_t)e1 * S + s], &row, sizeof(row)); ++e1) {}
+                if (scint_identity(row)) continue;
+                if ((e0 * spe) & 3)
+                    return fail(GAL_E_INVAL, "%s: the row of slot %d changes at epoch %d, %llu samples into the batch (a multiple of 4 only)", who, s, e0,
+                                (unsigned long long)(e0 * spe));
+                gal_scint_job_t j;
+                memset(&j, 0, sizeof(j));
+                j.out_dev = (int16_t *)((char *)h->own_parts + bytes * (size_t)group_of[s]) + 2 * e0 * spe;
+                j.in_dev = j.out_dev;
+                j.n_samples = (uint64_t)(e1 - e0) * spe;
+                j.first_sample = first_sample + e0 * spe;
+                j.row = row;
+                jobs.push_back(j);
+            }
+        }
+        for (size_t at = 0; at < jobs.size(); at += GAL_SCINT_MAX_JOBS) {
+            const int rc = gal_synth_iq_scint(h, jobs.data() + at, (int32_t)std::min<size_t>(GAL_SCINT_MAX_JOBS, jobs.size() - at));
+            if (rc != GAL_OK) return rc;
+        }
+    }
     if (!unity) {
         std::vector<uint16_t> gp((size_t)E * n_parts);
         for (int e = 0; e < E; ++e)
@@ -1103,7 +1259,7 @@ static int run_groups(const char *who, gal_synth_t *h, const gal_chan_epoch_t *p
         if (n_echo > 0) {
             std::vector<int32_t> hist_id(n_parts, -1), part_of(n_echo);
             for (int k = 0; k < n_parts; ++k)
-                if (groups[k].solo) hist_id[k] = groups[k].slots[0];
+                if (groups[k].solo && has_echo[groups[k].slots[0]]) hist_id[k] = groups[k].slots[0];
             for (int r = 0; r < n_echo; ++r) part_of[r] = group_of[slot_of_echo[r]];
             rc = gal_synth_iq_mpath(h, parts, n_parts, hist_id.data(), gp.data(), E, part_of.data(), echo_rows, n_echo, iq_dev);
         } else {
@@ -1132,6 +1288,25 @@ int gal_synth_run_mpath(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t 
     const int rc = gal_synth_mpath_check(echo_rows, n_echo, n_epochs, slot_of_echo, h->cfg.n_slots);
     if (rc) return rc;
     return run_groups(who, h, params, n_epochs, state_in, gain_q7, slot_of_echo, echo_rows, n_echo, iq_dev, state_out);
+}
+
+int gal_synth_run_scint(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_epochs, const gal_chan_state_t *state_in,
+                        const uint16_t *gain_q7, const int32_t *slot_of_echo, const gal_iq_echo_t *echo_rows, int32_t n_echo,
+                        const gal_iq_scint_t *scint_rows, uint64_t first_sample, int16_t *iq_dev, gal_chan_state_t *state_out)
+{
+    const char *who = "gal_synth_run_scint";
+    if (!scint_rows) return gal_synth_run_mpath(h, params, n_epochs, state_in, gain_q7, slot_of_echo, echo_rows, n_echo, iq_dev, state_out);
+    if (!h) return fail(GAL_E_INVAL, "%s: null handle", who);
+    if (n_epochs < 1) return fail(GAL_E_INVAL, "%s: n_epochs %d (>= 1)", who, n_epochs);
+    const uint64_t total = (uint64_t)n_epochs * (uint64_t)h->cfg.samples_per_epoch;
+    if (first_sample >> 62 || (first_sample + total) >> 62) return fail(GAL_E_INVAL, "%s: the batch must end below sample 2^62", who);
+    for (size_t i = 0; i < (size_t)n_epochs * h->cfg.n_slots; ++i) GAL_TRY(gal_synth_scint_check(&scint_rows[i]));
+    if (n_echo != 0) {
+        if (h->cfg.n_slots > GAL_ECHO_LINES) return fail(GAL_E_INVAL, "%s: %d slots, more than the %d history lines", who, h->cfg.n_slots, GAL_ECHO_LINES);
+        GAL_TRY(gal_synth_mpath_check(echo_rows, n_echo, n_epochs, slot_of_echo, h->cfg.n_slots));
+    }
+    return run_groups(who, h, params, n_epochs, state_in, gain_q7, n_echo ? slot_of_echo : nullptr, n_echo ? echo_rows : nullptr, n_echo, iq_dev, state_out,
+                      scint_rows, first_sample);
 }
 
 int gal_synth_gain_runs(const gal_synth_t *h, int32_t *n_runs)

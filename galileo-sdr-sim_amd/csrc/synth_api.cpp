@@ -428,6 +428,7 @@ int gal_synth_destroy(gal_synth_t *h)
     h->fd.release();
     h->agc.release();
     h->osc.release();
+    h->scint.release();
     if (h->d_lut) hipFree(h->d_lut);
     if (h->d_str) hipFree(h->d_str);
     if (h->h_up) hipHostFree(h->h_up);

@@ -196,8 +196,20 @@ struct MpathStage {
     }
 };
 
+// gal_synth_iq_scint (iq_scint.hip): table = the job table of the last call (GAL_SCINT_MAX_JOBS jobs of 64 bytes as the kernel reads
+// them), pinned on the host and on the device; sync = that call's kernel is done
+struct ScintStage {
+    GrownBuf table;
+    StageSync sync;
+    void release()
+    {
+        table.release();
+        sync.destroy();
+    }
+};
+
 struct gal_synth {
-    StagedPlan staged;            // the plan made while a batch was in flight (or being committed)
+    StagedPlan staged;           // the plan made while a batch was in flight (or being committed)
     bool staged_pending = false;  // ... waits for its commit
     gal_synth_cfg_t cfg{};
     int device = 0;
@@ -286,6 +298,7 @@ struct gal_synth {
     FirdecStage fd;
     AgcStage agc;
     OscStage osc;
+    ScintStage scint;
 };
 
 // The stream the handle works on: the caller's (gal_synth_set_stream), or one of its own, made at first need.

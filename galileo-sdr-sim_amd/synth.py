@@ -169,6 +169,32 @@ assert ctypes.sizeof(_Osc) == 48
 GAL_OSC_MAX_S = 1 << 48
 
 
+class _Scint(ctypes.Structure):  # gal_iq_scint_t (24 bytes)
+    _fields_ = [
+        ("seed", ctypes.c_uint64),
+        ("stream", ctypes.c_uint32),
+        ("node_len", ctypes.c_uint32),
+        ("a_q12", ctypes.c_uint16),
+        ("b_q12", ctypes.c_uint16),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+class _ScintJob(ctypes.Structure):  # gal_scint_job_t (56 bytes)
+    _fields_ = [("in_dev", ctypes.c_void_p), ("out_dev", ctypes.c_void_p), ("n_samples", ctypes.c_uint64), ("first_sample", ctypes.c_uint64),
+                ("row", _Scint)]
+
+
+SCINT_FIELDS = ("seed", "stream", "node_len", "a_q12", "b_q12")
+assert ctypes.sizeof(_Scint) == 24 and ctypes.sizeof(_ScintJob) == 56
+# one row of a scintillation table as numpy sees it: scint_rows are arrays of this type, [n_epochs, n_slots]
+SCINT_DTYPE = np.dtype([("seed", "<u8"), ("stream", "<u4"), ("node_len", "<u4"), ("a_q12", "<u2"), ("b_q12", "<u2"), ("reserved", "<u4")])
+assert SCINT_DTYPE.itemsize == 24
+GAL_SCINT_MIN_NODE = 64
+GAL_SCINT_MAX_NODE = 1 << 24
+GAL_SCINT_MAX_JOBS = 64
+
+
 class _Echo(ctypes.Structure):  # gal_iq_echo_t (16 bytes)
     _fields_ = [
         ("gain_q7", ctypes.c_uint16),
@@ -280,6 +306,10 @@ EXPORTED_SYMBOLS = (
     "gal_synth_osc_set",
     "gal_synth_iq_osc",
     "gal_synth_osc_lo_step",
+    "gal_synth_scint_check",
+    "gal_synth_scint_make",
+    "gal_synth_iq_scint",
+    "gal_synth_run_scint",
     "gal_synth_corr_out_bytes",
     "gal_synth_correlate",
     "gal_tables_e1b",
@@ -289,6 +319,7 @@ EXPORTED_SYMBOLS = (
     "gal_tables_cs25",
     "gal_tables_gauss",
     "gal_tables_cos1024",
+    "gal_tables_scint",
 )
 
 _libs = {}
@@ -408,6 +439,14 @@ def load_library(hooks=False):
     lib.gal_synth_iq_osc.restype = ctypes.c_int
     lib.gal_synth_osc_lo_step.argtypes = [ctypes.POINTER(_Osc), ctypes.c_uint64, ctypes.POINTER(i32)]
     lib.gal_synth_osc_lo_step.restype = ctypes.c_int
+    lib.gal_synth_scint_check.argtypes = [ctypes.POINTER(_Scint)]
+    lib.gal_synth_scint_check.restype = ctypes.c_int
+    lib.gal_synth_scint_make.argtypes = [ctypes.c_double] * 3 + [ctypes.POINTER(_Scint)]
+    lib.gal_synth_scint_make.restype = ctypes.c_int
+    lib.gal_synth_iq_scint.argtypes = [vp, ctypes.POINTER(_ScintJob), i32]
+    lib.gal_synth_iq_scint.restype = ctypes.c_int
+    lib.gal_synth_run_scint.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, vp, ctypes.c_uint64, vp, vp]
+    lib.gal_synth_run_scint.restype = ctypes.c_int
     lib.gal_synth_corr_out_bytes.argtypes = [ctypes.POINTER(_CorrReq)]
     lib.gal_synth_corr_out_bytes.restype = ctypes.c_size_t
     lib.gal_synth_correlate.argtypes = [vp, vp, i32, ctypes.c_size_t, ctypes.POINTER(_CorrReq), i32, vp]
@@ -417,7 +456,8 @@ def load_library(hooks=False):
     lib.gal_corr_cn0.argtypes = [vp, ctypes.POINTER(_CorrReq), i32, i32, i32, ctypes.c_double, ctypes.POINTER(ctypes.c_double),
                                  ctypes.POINTER(ctypes.c_double)]
     lib.gal_corr_cn0.restype = ctypes.c_int
-    for name in ("gal_tables_e1b", "gal_tables_e1c", "gal_tables_cos512", "gal_tables_sin512", "gal_tables_gauss", "gal_tables_cos1024"):
+    for name in ("gal_tables_e1b", "gal_tables_e1c", "gal_tables_cos512", "gal_tables_sin512", "gal_tables_gauss", "gal_tables_cos1024",
+                 "gal_tables_scint"):
         getattr(lib, name).restype = vp
     lib.gal_tables_cs25.restype = ctypes.c_uint32
     _libs[hooks] = lib
@@ -673,6 +713,54 @@ def osc_lo_step(osc, n):
     return int(out.value)
 
 
+def _scint_struct(row):
+    """dict with the fields of gal_iq_scint_t but `reserved` (seed defaults to 1, stream to 0, node_len to 64, a_q12 to 4096, b_q12 to 0:
+    the identity), or a _Scint."""
+    if isinstance(row, _Scint):
+        return row
+    unknown = set(row) - set(SCINT_FIELDS)
+    if unknown:
+        raise ValueError("scint: unknown keys %s" % sorted(unknown))
+    d = {"seed": 1, "stream": 0, "node_len": GAL_SCINT_MIN_NODE, "a_q12": 4096, "b_q12": 0}
+    d.update(row)
+    for k, bits in (("seed", 64), ("stream", 32), ("node_len", 32), ("a_q12", 16), ("b_q12", 16)):
+        if not 0 <= int(d[k]) < 1 << bits:
+            raise ValueError("scint: %s = %r does not fit its field" % (k, d[k]))
+    return _Scint(int(d["seed"]), int(d["stream"]), int(d["node_len"]), int(d["a_q12"]), int(d["b_q12"]), 0)
+
+
+def scint_check(row):
+    """gal_synth_scint_check (no GPU needed): raises GalSynthError unless the scintillation row is admitted (64 <= node_len <= 2^24,
+    a_q12 and b_q12 <= 4096)."""
+    lib = load_library()
+    r = _scint_struct(row)
+    rc = lib.gal_synth_scint_check(ctypes.byref(r))
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+
+
+def scint_make(s4, tau0_s, sample_rate=2.6e6):
+    """gal_synth_scint_make (no GPU needed): the scintillation row, as a dict, of the index s4 (0 .. 1) and the 1/e decorrelation time
+    tau0_s of the scattered field at sample_rate: a_q12, b_q12 from the Rician K with that S4, node_len = llround(tau0_s sample_rate /
+    8); seed 1, stream 0."""
+    lib = load_library()
+    r = _Scint()
+    rc = lib.gal_synth_scint_make(float(s4), float(tau0_s), float(sample_rate), ctypes.byref(r))
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+    return {k: int(getattr(r, k)) for k in SCINT_FIELDS}
+
+
+def scint_rows(rows, n_epochs, n_slots):
+    """A scintillation table [n_epochs, n_slots] (SCINT_DTYPE): rows = {slot: row dict}, every other slot the identity."""
+    out = np.zeros((int(n_epochs), int(n_slots)), dtype=SCINT_DTYPE)
+    out["seed"], out["node_len"], out["a_q12"] = 1, GAL_SCINT_MIN_NODE, 4096
+    for slot, row in rows.items():
+        r = _scint_struct(row)
+        out[:, int(slot)] = (r.seed, r.stream, r.node_len, r.a_q12, r.b_q12, 0)
+    return out
+
+
 def _echo_table(echo_rows, n_epochs, who):
     """echo_rows -> a contiguous ECHO_DTYPE array [n_epochs, n_echo] (None or an empty one: no echoes)."""
     if echo_rows is None:
@@ -790,6 +878,7 @@ def tables():
         "cs25": int(lib.gal_tables_cs25()),
         "gauss": arr(lib.gal_tables_gauss(), ctypes.c_int32, 32 * 32 * 2, (32, 32, 2)),
         "cos1024": arr(lib.gal_tables_cos1024(), ctypes.c_int16, 1024, (1024,)),
+        "scint": arr(lib.gal_tables_scint(), ctypes.c_int32, 32, (32,)),
     }
 
 
@@ -995,6 +1084,46 @@ class SynthEngine:
         st = np.zeros(self.n_slots, dtype=CHAN_STATE_DTYPE)
         self._check(self._lib.gal_synth_run_mpath(self._h, p.ctypes.data, p.shape[0], s.ctypes.data if s is not None else None, g.ctypes.data,
                                                   sof.ctypes.data if sof.size else None, rows.ctypes.data if rows.size else None, rows.shape[1],
+                                                  ctypes.c_void_p(int(iq_dev_ptr)), st.ctypes.data))
+        self.n_epochs = p.shape[0]
+        return st
+
+    def iq_scint(self, jobs):
+        """gal_synth_iq_scint, enqueued on the handle's stream, ALL JOBS IN ONE LAUNCH: jobs = a sequence of (in_ptr, out_ptr, n_samples,
+        first_sample, row) -- device addresses (16-byte aligned; the same address or disjoint), the global index of the job's first
+        sample and a row dict (scint_make makes one).  z is a function of (row, global index) alone: any cut of a stream into calls
+        gives the same bytes.  iq_saturated() is the fence and counts the clamped samples."""
+        arr = (_ScintJob * max(1, len(jobs)))()
+        for k, (src, dst, n, first, row) in enumerate(jobs):
+            arr[k] = _ScintJob(int(src) or None, int(dst) or None, int(n), int(first), _scint_struct(row))
+        self._check(self._lib.gal_synth_iq_scint(self._h, arr, len(jobs)))
+
+    def run_scint(self, params, gain_q7, iq_dev_ptr, scint_rows=None, first_sample=0, slot_of_echo=(), echo_rows=None, state_in=None):
+        """gal_synth_run_scint: run_mpath with the scintillation table scint_rows [n_epochs, n_slots] (SCINT_DTYPE; the module's
+        scint_rows makes one) -- every slot with a non-identity row is a synthesis run of its own and its part goes through iq_scint in
+        place before the echo pass (or the weighted sum); first_sample = the global index of the batch's first sample.  None:
+        run_mpath.  Returns state_out."""
+        p = self._params(params)
+        s = self._state(state_in)
+        g = np.asarray(gain_q7)
+        if g.shape != p.shape:
+            raise ValueError("run_scint: gain_q7 must have shape [n_epochs, n_slots=%d]" % self.n_slots)
+        if g.size and (g.min() < 0 or g.max() > 65535):
+            raise ValueError("run_scint: a gain does not fit a uint16")
+        g = np.ascontiguousarray(g, dtype=np.uint16)
+        rows = _echo_table(echo_rows, p.shape[0], "run_scint")
+        sof = np.ascontiguousarray(slot_of_echo, dtype=np.int32).ravel()
+        if sof.size != rows.shape[1]:
+            raise ValueError("run_scint: slot_of_echo must have n_echo = %d entries" % rows.shape[1])
+        sc = None
+        if scint_rows is not None:
+            sc = np.ascontiguousarray(scint_rows, dtype=SCINT_DTYPE)
+            if sc.shape != p.shape:
+                raise ValueError("run_scint: scint_rows must have shape [n_epochs, n_slots=%d]" % self.n_slots)
+        st = np.zeros(self.n_slots, dtype=CHAN_STATE_DTYPE)
+        self._check(self._lib.gal_synth_run_scint(self._h, p.ctypes.data, p.shape[0], s.ctypes.data if s is not None else None, g.ctypes.data,
+                                                  sof.ctypes.data if sof.size else None, rows.ctypes.data if rows.size else None, rows.shape[1],
+                                                  sc.ctypes.data if sc is not None else None, int(first_sample),
                                                   ctypes.c_void_p(int(iq_dev_ptr)), st.ctypes.data))
         self.n_epochs = p.shape[0]
         return st

@@ -825,6 +825,82 @@ int gal_synth_iq_osc(gal_synth_t *h, const int16_t *in_dev, size_t n_samples, in
  * GAL_E_INVAL for a null pointer. */
 int gal_synth_osc_lo_step(const gal_iq_osc_t *osc, uint64_t N, int32_t *carr_dph);
 
+/*
+ * Ionospheric scintillation (not in the reference): ONE satellite's stream -- a "part" of gal_synth_run_gains /
+ * gal_synth_run_mpath -- times a slowly varying complex factor z, a Rician field with a Gaussian spectrum: random, per-satellite
+ * fading and phase wander.  z is a FIXED INTEGER FUNCTION of (row, index N of the sample in the whole stream); with the int16 input
+ * that fixes every byte.  It keeps NO STATE: any cut of the stream into calls gives the same bytes as one call, without conditions
+ * (tests/scint_model.py states it in numpy).
+ *
+ * Draw i (uint64): Philox4x32-10 as the noise floor uses it, key = (seed & 0xffffffff, seed >> 32), counter = (i & 0xffffffff,
+ * i >> 32, stream, 2) -- counter word 3 is 0 for the noise floor and 1 for the oscillator, so the three are disjoint.  gI(i) = the Q12
+ * Gaussian of output word 0, gQ(i) that of word 1 (the noise floor's table T and steps; |g| <= 25960).
+ * h = gal_tables_scint(): h[t] = round(32768 c exp(-(t - 15.5)^2 / 32)), t < 32, c such that H2 = sum h^2 is as close to 2^30 as it
+ * gets (sum h = 123382, H2 / 2^30 = 1.0000136; the committed table is the definition).
+ * Node j (uint64):
+ *   SI    = sum_t h[t] gI(j + t)  (int64);  XI = (SI + 2^14) >> 15                           (likewise SQ, XQ; |X| < 2^17)
+ *   ZI[j] = clamp(A + ((B XI + 2048) >> 12), -32767, 32767);  ZQ[j] = clamp((B XQ + 2048) >> 12, -32767, 32767)
+ * Sample N, with L = node_len:
+ *   j  = N div L, m = N mod L;  R = floor(2^32 / L) (m R < 2^32);  fr = (m R) >> 20          (Q12, 0 .. 4095)
+ *   zI = ZI[j] + (((ZI[j + 1] - ZI[j]) fr + 2048) >> 12)                                     (likewise zQ: linear between the nodes)
+ *   yI = clamp((xI zI - xQ zQ + 2048) >> 12, -32768, 32767);  yQ = clamp((xI zQ + xQ zI + 2048) >> 12, -32768, 32767)
+ * All shifts are arithmetic.  A complex sample counts ONCE in the handle's saturation counter if either clamp changed it.  The node
+ * clamp keeps |z| <= 32767, so |xI zI - xQ zQ| + 2048 <= 2 x 32768 x 32767 + 2048 < 2^31: every product and sum fits an int32 for any
+ * int16 input (B XI < 2^29 too).  A = 4096, B = 0 gives z = 4096 and y = x bit for bit.
+ * The nodes are a unit-variance (at 4096) Gaussian sequence with the autocorrelation exp(-k^2 / 64): 1/e at a lag of 8 nodes, so
+ * tau0 = 8 L / sample_rate is the 1/e decorrelation time of the scattered field.
+ */
+typedef struct gal_iq_scint {
+    uint64_t seed;      /* Philox key                                                                                        */
+    uint32_t stream;    /* Philox counter word 2 (the CLI: site index << 8 | PRN)                                            */
+    uint32_t node_len;  /* L: samples between two nodes, 64 .. 2^24                                                          */
+    uint16_t a_q12;     /* A <= 4096: the direct (specular) component of z                                                   */
+    uint16_t b_q12;     /* B <= 4096: the scale of the scattered component                                                   */
+    uint32_t reserved;  /* 0                                                                                                 */
+} gal_iq_scint_t;       /* 24 bytes */
+#define GAL_SCINT_MIN_NODE 64
+#define GAL_SCINT_MAX_NODE (1u << 24)
+#define GAL_SCINT_MAX_JOBS 64
+/* GAL_OK if the row is admitted, else GAL_E_INVAL: a null pointer, node_len outside 64 .. 2^24, a_q12 or b_q12 above 4096,
+ * reserved != 0.  Host only, needs no GPU. */
+int gal_synth_scint_check(const gal_iq_scint_t *row);
+/* A row from physical figures; host only, needs no GPU.  In double, operation for operation, rounding to nearest (llround):
+ *   s4 in (0, 1):  m = 1 / s4^2 (the Nakagami m);  q = sqrt(m^2 - m);  K = q / (m - q) (the Rician K with that S4)
+ *                  A = llround(4096 sqrt(K / (K + 1)));  B = llround(4096 sqrt(1 / (2 (K + 1) v)))
+ *   v = the variance of XI / 4096 taken from the tables themselves: (H2 / 2^30) x (M2 / 2^55), M2 as for gal_synth_osc_make
+ *   s4 = 0: A = 4096, B = 0 (the identity);  s4 = 1 (Rayleigh): A = 0, B = llround(4096 sqrt(1 / (2 v)))
+ *   node_len = llround(tau0_s x sample_rate / 8)
+ * seed = 1, stream = 0, reserved = 0.  The mean of |z|^2 is 4096^2.  GAL_E_INVAL for a null `out`, an argument that is not finite, s4
+ * outside [0, 1], sample_rate <= 0, a node_len outside 64 .. 2^24. */
+int gal_synth_scint_make(double s4, double tau0_s, double sample_rate, gal_iq_scint_t *out);
+typedef struct gal_scint_job {
+    const int16_t *in_dev;   /* DEVICE, 16-byte aligned, 4 n_samples bytes                                                   */
+    int16_t       *out_dev;  /* DEVICE, 16-byte aligned: in_dev itself (in place) or a buffer that does not meet it          */
+    uint64_t       n_samples;    /* complex samples, < 2^41 (0: the job does nothing)                                        */
+    uint64_t       first_sample; /* N of the job's first sample, < 2^62                                                      */
+    gal_iq_scint_t row;
+} gal_scint_job_t;           /* 56 bytes */
+/* Enqueue on the handle's stream: every job's y of the definition above, ALL JOBS IN ONE LAUNCH (1 <= n_jobs <= GAL_SCINT_MAX_JOBS).
+ * `jobs` is HOST memory, copied before the call returns.  A job may run exactly IN PLACE; any other overlap of its two buffers is
+ * refused, and so is a job's output that meets another job's input or output (two jobs may read one input).  A job with A = 4096,
+ * B = 0 copies, or does nothing in place.  A handle holds one job table: a call waits (on the host) for the kernel of the call before
+ * it.  gal_synth_iq_saturated is the fence and the counter.  GAL_E_INVAL for a null handle or pointer, n_jobs outside 1 .. 64, what
+ * gal_synth_scint_check refuses, a misaligned pointer, first_sample >= 2^62, n_samples >= 2^41, an overlap; GAL_E_STATE for a buffer of
+ * the batch in flight; GAL_E_NOMEM if the job table cannot be had. */
+int gal_synth_iq_scint(gal_synth_t *h, const gal_scint_job_t *jobs, int32_t n_jobs);
+/* gal_synth_run_mpath with scintillation: scint_rows is HOST [n_epochs][n_slots], the row of every slot in every epoch (a slot without
+ * scintillation: A = 4096, B = 0, any admitted L; such a row is not looked at further), first_sample (< 2^62) the global index of the
+ * batch's first sample.  Every slot that has a non-identity row in any epoch of the batch is a group (a synthesis run) of its own, as
+ * a slot with an echo is; its part goes through gal_synth_iq_scint in place BEFORE gal_synth_iq_mpath (or the weighted sum), so its
+ * echoes are echoes of the scintillated stream.  One job per slot and maximal run of epochs with an equal row, all jobs of the batch
+ * in one call (in calls of 64 where there are more).  A row may change only at an epoch whose first sample is a multiple of four
+ * samples into the batch (always, where samples_per_epoch is one).  scint_rows == NULL is gal_synth_run_mpath bit for bit;
+ * gal_synth_gain_runs counts the runs.  The refusals are those of gal_synth_run_mpath, gal_synth_scint_check (every row) and
+ * gal_synth_iq_scint. */
+int gal_synth_run_scint(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_epochs, const gal_chan_state_t *state_in,
+                        const uint16_t *gain_q7, const int32_t *slot_of_echo, const gal_iq_echo_t *echo_rows, int32_t n_echo,
+                        const gal_iq_scint_t *scint_rows, uint64_t first_sample, int16_t *iq_dev, gal_chan_state_t *state_out);
+
 /* Signal tables as the engine uses them (for tests and for the oracle to share DATA, not code). */
 const uint32_t *gal_tables_e1b(void);   /* [50][128] */
 const uint32_t *gal_tables_e1c(void);   /* [50][128] */
@@ -833,6 +909,7 @@ const int16_t  *gal_tables_sin512(void);/* [512]     */
 uint32_t        gal_tables_cs25(void);
 const int32_t  *gal_tables_gauss(void); /* [32][32][2] = T of the noise floor (above); needs no GPU */
 const int16_t  *gal_tables_cos1024(void);/* [1024] = C of the interference sources (above); needs no GPU */
+const int32_t  *gal_tables_scint(void); /* [32] = h of the scintillation (above); needs no GPU */
 
 #ifdef __cplusplus
 }
