@@ -23,8 +23,10 @@ from .synth import (  # noqa: F401
     GAL_IQ_ISHORT,
     IQ_FORMATS,
     SCINT_DTYPE,
+    STEER_DTYPE,
     GalSynthError,
     SynthEngine,
+    array_phase,
     corr_cn0,
     corr_from_epoch,
     corr_out_bytes,
@@ -44,6 +46,8 @@ from .synth import (  # noqa: F401
     scint_check,
     scint_make,
     scint_rows,
+    steer_check,
+    steer_make,
     tables,
     unpack_page,
 )

@@ -171,6 +171,7 @@ struct RowRing {
     struct Buf {
         std::vector<gal_chan_epoch_t> rows;
         std::vector<uint16_t> gains;  // per-satellite signal power: [epochs][slots] Q7
+        std::vector<double> azel;     // --array: [epochs][slots][2] azimuth and elevation, radians
         int n = 0;                    // epochs in it; < 0: front-end error, 0: end of the scenario
         bool ready = false;           // under mu: the producer's until ready, the main thread's until it clears it
     } buf[kBufs];
@@ -193,8 +194,9 @@ void produce_rows(RowRing &ring, gal_scen_t *scen, const Config &c, Clock::time_
         // -r: FIFO-style pacing (the reference: src/fifo.cpp + src/galileo-sdr.cpp:570-595): epoch k is produced no earlier than
         // k * 0.1 s after the start, so that position updates are current
         if (c.realtime) std::this_thread::sleep_until(t_start + std::chrono::milliseconds(100) * produced_epochs);
-        const int n = g_stop       ? 0
-                      : c.power_on ? gal_scen_next_gains(scen, c.batch_epochs, b.rows.data(), b.gains.data())
+        const int n = g_stop         ? 0
+                      : c.array_on() ? gal_scen_next_azel(scen, c.batch_epochs, b.rows.data(), c.power_on ? b.gains.data() : nullptr, b.azel.data())
+                      : c.power_on   ? gal_scen_next_gains(scen, c.batch_epochs, b.rows.data(), b.gains.data())
                                    : gal_scen_next(scen, c.batch_epochs, b.rows.data());
         if (n > 0) produced_epochs += n;
         {
@@ -208,7 +210,8 @@ void produce_rows(RowRing &ring, gal_scen_t *scen, const Config &c, Clock::time_
     }
 }
 
-void write_slots(SlotPair &sp, Sink &sink)
+// sinks: one per element (without --array: one)
+void write_slots(SlotPair &sp, std::vector<Sink> &sinks)
 {
     for (int next = 0;; next ^= 1) {
         Slot &s = sp.s[next].out;
@@ -216,8 +219,9 @@ void write_slots(SlotPair &sp, Sink &sink)
         sp.cv.wait(lk, [&] { return s.full || sp.done; });
         if (!s.full) return;
         lk.unlock();
-        if (hipEventSynchronize(s.copied[0]) != hipSuccess || hipEventSynchronize(s.copied[1]) != hipSuccess || !sink.put((const char *)s.host, s.bytes))
-            sp.io_error = true;
+        bool ok = hipEventSynchronize(s.copied[0]) == hipSuccess && hipEventSynchronize(s.copied[1]) == hipSuccess;
+        for (int k = 0; k < s.n_elem && ok; ++k) ok = sinks[k].put((const char *)s.host + (size_t)k * s.stride, s.bytes);
+        if (!ok) sp.io_error = true;
         lk.lock();
         s.full = false;
         lk.unlock();
@@ -232,6 +236,10 @@ struct Run {
     gal_synth_cfg_t cfg;
     hipStream_t stream = nullptr, copy_stream[2] = {nullptr, nullptr};
     size_t epoch_bytes = 0, batch_bytes = 0;  // in the output format
+    int K = 1;                                // --array: elements; their batches lie iq_stride (int16) / out_stride (format) bytes apart
+    size_t iq_stride = 0, out_stride = 0;
+    std::vector<uint16_t> ar_gains;           // --array: the batch's gains [epochs][slots] and phases [epochs][elements][slots]
+    std::vector<uint32_t> ar_phase;
     int emitted = 0;                          // epochs handed to the writer
     std::vector<gal_chan_state_t> state;
     bool have_state = false;
@@ -281,15 +289,17 @@ bool alloc_slots(const Run &r, SlotPair &sp)
 {
     const Config &c = r.c;
     for (BatchSlot &b : sp.s) {
-        if (hipMalloc((void **)&b.d_iq, (size_t)r.cfg.samples_per_epoch * 4 * c.batch_epochs) != hipSuccess ||
-            hipHostMalloc((void **)&b.out.host, r.batch_bytes, hipHostMallocDefault) != hipSuccess)
+        if (hipMalloc((void **)&b.d_iq, r.iq_stride * r.K) != hipSuccess ||
+            hipHostMalloc((void **)&b.out.host, r.out_stride * r.K, hipHostMallocDefault) != hipSuccess)
             return false;
+        b.out.n_elem = r.K;
+        b.out.stride = r.out_stride;
         b.d_out = b.d_iq;
         if (c.fir_on()) {  // the filtered int16 batch, which then is what the format conversion (ishort: the copies) reads
             if (hipMalloc((void **)&b.d_fir, (size_t)kOutSamplesPerEpoch * 4 * c.batch_epochs) != hipSuccess) return false;
             b.d_out = b.d_fir;
         }
-        if ((c.iq_format != GAL_IQ_ISHORT || c.agc_on) && hipMalloc(&b.d_out, r.batch_bytes) != hipSuccess) return false;
+        if ((c.iq_format != GAL_IQ_ISHORT || c.agc_on) && hipMalloc(&b.d_out, r.out_stride * r.K) != hipSuccess) return false;
         if (c.chain_on_engine_stream() && hipEventCreateWithFlags(&b.converted, hipEventDisableTiming) != hipSuccess) return false;
         hipEventCreate(&b.out.copied[0]);
         hipEventCreate(&b.out.copied[1]);
@@ -436,6 +446,50 @@ int synth_mpath(Run &r, const RowRing::Buf &rows, int n, int16_t *d_iq)
                                r.c.sc_on() ? r.sc_rows.data() : nullptr, (uint64_t)r.emitted * (uint64_t)r.cfg.samples_per_epoch, d_iq, r.state.data());
 }
 
+// --array: every active satellite a run of its own, then the array pass into the K element batches that lie one behind the other in
+// d_iq.  The gains are those of --power-model and its kin, or unity; the phases come from the front-end's azimuth and elevation
+int synth_array(Run &r, const RowRing::Buf &rows, int n, int16_t *d_iq)
+{
+    const Config &c = r.c;
+    const int S = r.cfg.n_slots, K = r.K;
+    const gal_chan_epoch_t *rec = rows.rows.data();
+    if (c.power_on) {
+        r.ar_gains.assign(rows.gains.begin(), rows.gains.begin() + (size_t)n * S);
+        r.note_gains(rec, r.ar_gains.data(), (size_t)n * S);
+    } else {
+        r.ar_gains.assign((size_t)n * S, (uint16_t)GAL_GAIN_UNITY);
+    }
+    r.ar_phase.assign((size_t)n * K * S, 0u);
+    for (int e = 0; e < n; ++e)
+        for (int s = 0; s < S; ++s) {
+            const size_t i = (size_t)e * S + s;
+            if (rec[i].prn <= 0) continue;
+            const double az = rows.azel[2 * i], el = rows.azel[2 * i + 1];
+            if (c.array_log_fp) fprintf(c.array_log_fp, "%.1f,%d,%.4f,%.4f", (r.emitted + e) * 0.1, rec[i].prn, az * 57.29577951308232, el * 57.29577951308232);
+            for (int a = 0; a < K; ++a) {
+                uint32_t ph = 0;
+                const int rc = gal_synth_array_phase(c.array[a].enu, az, el, &ph);
+                if (rc != GAL_OK) return rc;
+                r.ar_phase[((size_t)e * K + a) * S + s] = ph;
+                if (c.array_log_fp) fprintf(c.array_log_fp, ",%u", ((ph + (1u << 21)) >> 22) & 1023u);
+            }
+            if (c.array_log_fp) fputc('\n', c.array_log_fp);
+        }
+    if (c.sc_on()) {
+        gal_iq_scint_t ident;
+        memset(&ident, 0, sizeof(ident));
+        ident.seed = 1, ident.node_len = GAL_SCINT_MIN_NODE, ident.a_q12 = 4096;
+        r.sc_rows.assign((size_t)n * S, ident);
+        for (size_t i = 0; i < (size_t)n * S; ++i)
+            for (const ScintSpec &sp : c.scints)
+                if (rec[i].prn == sp.prn) r.sc_rows[i] = sp.row;
+    }
+    int16_t *outs[GAL_ARRAY_MAX_ELEM];
+    for (int a = 0; a < K; ++a) outs[a] = (int16_t *)((char *)d_iq + (size_t)a * r.iq_stride);
+    return gal_synth_run_array(r.eng, rec, n, r.have_state ? r.state.data() : nullptr, r.ar_gains.data(), r.ar_phase.data(), K,
+                               c.sc_on() ? r.sc_rows.data() : nullptr, (uint64_t)r.emitted * (uint64_t)r.cfg.samples_per_epoch, outs, r.state.data());
+}
+
 // ---- the output chain behind a batch, on the engine's stream ------------------------------------------------------------------------------------
 //   1. noise and interference, in place        2. the oscillator, in place
 //   3. --fir or the decimator into d_fir       4. the AGC or the format conversion into d_out
@@ -447,6 +501,26 @@ bool run_chain(Run &r, BatchSlot &b, int n)
     // --oversample: the batch is n x M x 260 000 samples up to the decimator, which keeps n x 260 000 of them
     const size_t n_samples = (size_t)n * r.cfg.samples_per_epoch, n_kept = (size_t)n * kOutSamplesPerEpoch;
     const uint64_t first_sample = (uint64_t)r.emitted * (uint64_t)r.cfg.samples_per_epoch;
+    if (c.array_on()) {
+        // every element on its own through the one fused pass: the SAME sigma and signal gain, a noise stream of its own
+        // (8 x --noise-stream + k), and its copy of every --jam source at the phase its direction of arrival gives it at the element
+        if (c.iq_format == GAL_IQ_ISHORT && !c.mix_on()) return true;
+        for (int k = 0; k < r.K; ++k) {
+            gal_iq_noise_t nz = c.noise;
+            nz.stream = 8u * c.noise.stream + (uint32_t)k;
+            gal_iq_interf_t src[GAL_INTERF_MAX];
+            for (int j = 0; j < c.n_jam; ++j) {
+                uint32_t ph = 0;
+                if (gal_synth_array_phase(c.array[k].enu, c.jam_az[j], c.jam_el[j], &ph) != GAL_OK) return r.lib_fail();
+                src[j] = c.interf[j];
+                src[j].ph0 += ph;
+            }
+            if (gal_synth_iq_convert_interf(r.eng, (const int16_t *)((const char *)b.d_iq + (size_t)k * r.iq_stride), n_samples, first_sample,
+                                            c.mix_on() ? &nz : NULL, src, c.n_jam, c.iq_format, c.iq_shift, (char *)b.d_out + (size_t)k * r.out_stride) != GAL_OK)
+                return r.lib_fail();
+        }
+        return true;
+    }
     if (!c.fir_on() && !c.agc_on && !c.osc_on) {
         // nothing needs the int16 stream between the noise and the format: ONE fused pass does both (ishort: in place in d_iq).
         // (without --cn0, `noise` still carries the signal gain of the --jam sources; with neither the library converts plainly)
@@ -478,6 +552,14 @@ bool run_chain(Run &r, BatchSlot &b, int n)
 // device -> host in two halves on the two copy streams, split at an epoch boundary: epoch_bytes is whole bytes in every format
 bool enqueue_copies(Run &r, BatchSlot &b, int n)
 {
+    if (r.K > 1 || r.c.array_on()) {  // --array: every element's batch, the elements alternating between the two copy streams
+        hipError_t cerr = hipSuccess;
+        for (int k = 0; k < r.K && cerr == hipSuccess; ++k)
+            cerr = hipMemcpyAsync((char *)b.out.host + (size_t)k * r.out_stride, (const char *)b.d_out + (size_t)k * r.out_stride, b.out.bytes,
+                                  hipMemcpyDeviceToHost, r.copy_stream[k & 1]);
+        for (int k = 0; k < 2 && cerr == hipSuccess; ++k) cerr = hipEventRecord(b.out.copied[k], r.copy_stream[k]);
+        return cerr == hipSuccess || r.fail("device -> host copy failed: %s", hipGetErrorString(cerr));
+    }
     const size_t half = r.epoch_bytes * (size_t)((n + 1) / 2);
     const size_t part[2] = {half, b.out.bytes - half};
     size_t off = 0;
@@ -517,8 +599,8 @@ int run_loop(Run &r, RowRing &ring, SlotPair &sp, int total, Clock::time_point t
     const Config &c = r.c;
     const bool batch_timing = getenv("GAL_CLI_TIMING") != nullptr;
     const auto ms_since = [](Clock::time_point a) { return std::chrono::duration<double, std::milli>(Clock::now() - a).count(); };
-    const auto synth = c.parts_on() ? synth_mpath : c.power_on ? synth_gains : synth_plain;
-    const bool finished_inside = c.parts_on() || c.power_on;  // run_gains / run_mpath return with every group finished
+    const auto synth = c.array_on() ? synth_array : c.parts_on() ? synth_mpath : c.power_on ? synth_gains : synth_plain;
+    const bool finished_inside = c.array_on() || c.parts_on() || c.power_on;  // run_gains / run_mpath return with every group finished
     int cur = 0;
     for (int ri = 0; r.emitted < total && !sp.io_error && !g_stop; cur ^= 1, ri = (ri + 1) % RowRing::kBufs) {
         const auto tb0 = Clock::now();
@@ -569,7 +651,8 @@ int run_loop(Run &r, RowRing &ring, SlotPair &sp, int total, Clock::time_point t
         if (batch_timing)
             fprintf(stderr, "[timing] batch at %7.2f ms: %3d epochs, waited %.2f ms for rows, %.2f for a free slot, %s %.2f\n",
                     std::chrono::duration<double, std::milli>(tb0 - t_start).count(), n, tb_rows, tb_slot - tb_rows,
-                    c.parts_on() ? "run_scint (every group's plan + execute + finish, scintillation and the echo pass enqueued)"
+                    c.array_on() ? "run_array (every satellite's plan + execute + finish, the array pass enqueued)"
+                    : c.parts_on() ? "run_scint (every group's plan + execute + finish, scintillation and the echo pass enqueued)"
                     : c.power_on ? "run_gains (every group's plan + execute + finish, the sum enqueued)"
                                  : "plan + execute + finish",
                     tb_synth - tb_slot);
@@ -685,7 +768,7 @@ gal_scen_t *open_scenario(Config &c)
     }
     if (orc != GAL_OK) {
         fprintf(stderr, "%s\n", gal_scen_last_error());
-        if (orc == GAL_E_EMPTY && c.outfile != "-") {
+        if (orc == GAL_E_EMPTY && c.outfile != "-" && !c.array_on()) {
             // (int)(10 d + 0.5) < 2: the reference opens its sink, finds no epoch to generate and closes it (src/galileo-sdr.cpp:438)
             FILE *f = fopen(c.outfile.c_str(), "wb");
             if (f) fclose(f);
@@ -763,13 +846,27 @@ int run(Config &c, gal_scen_t *scen)
     // what round 3's first measurements showed): the kernel inserts pages into ONE file's page cache at ~6 GB/s whoever
     // asks -- write(), page faults of many threads, pwrite()s of many threads (inode lock) -- profiles/archive/r03a_sink_probe.log.
     if (c.n_writers < 0) c.n_writers = 0;
-    Sink sink;
-    if (!sink.open(c.outfile.c_str(), c.realtime ? 0 : (size_t)total * r.epoch_bytes, c.n_writers))  // (paced runs stream: they are slow by design)
-        die("ERROR: Failed to open output file.\n");
+    r.K = c.n_elem();
+    if (c.array_log_file && !(c.array_log_fp = fopen(c.array_log_file, "w"))) die("ERROR: --array-log %s cannot be written.\n", c.array_log_file);
+    std::vector<Sink> sinks(r.K);
+    for (int k = 0; k < r.K; ++k) {
+        std::string path = c.outfile;
+        if (c.array_on()) {  // NAME.EXT -> NAME.a<k>.EXT (no extension: NAME.a<k>), always with the suffix
+            const size_t slash = path.find_last_of('/'), dot = path.find_last_of('.');
+            const std::string tag = ".a" + std::to_string(k);
+            if (dot == std::string::npos || (slash != std::string::npos && dot < slash) || dot == (slash == std::string::npos ? 0 : slash + 1)) path += tag;
+            else path.insert(dot, tag);
+            fprintf(stderr, "Element %d -> %s\n", k, path.c_str());
+        }
+        if (!sinks[k].open(path.c_str(), c.realtime ? 0 : (size_t)total * r.epoch_bytes, c.n_writers))  // (paced runs stream: they are slow by design)
+            die("ERROR: Failed to open output file.\n");
+    }
     stage("sink opened");
     open_engine(r);
     if (c.batch_epochs > total) c.batch_epochs = total > 0 ? total : 1;
     r.batch_bytes = r.epoch_bytes * c.batch_epochs;
+    r.iq_stride = (size_t)r.cfg.samples_per_epoch * 4 * c.batch_epochs;  // (a multiple of 16: 260 000 samples of 4 bytes)
+    r.out_stride = (r.batch_bytes + 15) / 16 * 16;                       // the library's buffers begin on 16 bytes
     memset(&r.mon_shape, 0, sizeof(r.mon_shape));
     r.mon_shape.max_periods = kMonPeriods;
     r.mon_shape.delay_step = 1;
@@ -785,13 +882,14 @@ int run(Config &c, gal_scen_t *scen)
     open_streams(r, sp);
     stage("copy path warmed");
 
-    std::thread writer(write_slots, std::ref(sp), std::ref(sink));
+    std::thread writer(write_slots, std::ref(sp), std::ref(sinks));
     signal(SIGINT, on_sigint);
     const auto t_start = Clock::now();
     RowRing ring;
     for (auto &b : ring.buf) {
         b.rows.resize((size_t)c.batch_epochs * c.sc.n_slots);
         if (c.power_on) b.gains.resize((size_t)c.batch_epochs * c.sc.n_slots);
+        if (c.array_on()) b.azel.resize((size_t)c.batch_epochs * c.sc.n_slots * 2);
     }
     std::thread producer(produce_rows, std::ref(ring), scen, std::cref(c), t_start);
     r.state.resize(c.sc.n_slots);
@@ -814,7 +912,12 @@ int run(Config &c, gal_scen_t *scen)
     writer.join();
     // (the sink is closed inside the reported time: unmapping a 1.2 GB file mapping is not free, and the file is only
     // the caller's once it is closed)
-    if (!sink.finish()) sp.io_error = true;
+    for (Sink &s : sinks)
+        if (!s.finish()) sp.io_error = true;
+    if (c.array_log_fp && fclose(c.array_log_fp) != 0) {
+        fprintf(stderr, "ERROR: writing the array log %s failed\n", c.array_log_file);
+        sp.io_error = true;
+    }
     stage("run (= Process time)");
     const double el = std::chrono::duration<double>(Clock::now() - t_start).count();
     fprintf(stderr, "\nDone!\nProcess time = %.2f [sec]  (%.1f Msamples/s, %.0fx real time)\n", el, r.emitted * 0.26 / el, r.emitted * 0.1 / el);

@@ -419,8 +419,8 @@ struct Args {
                *oversample = nullptr, *multipath = nullptr, *agc = nullptr, *agc_block = nullptr, *agc_window = nullptr, *agc_init = nullptr,
                *agc_log = nullptr, *i2bit_thr = nullptr, *antenna = nullptr, *cn0 = nullptr, *noise_seed = nullptr, *noise_stream = nullptr,
                *signal_gain = nullptr, *lo_offset = nullptr, *phase_noise = nullptr, *osc_seed = nullptr, *osc_stream = nullptr,
-               *scint = nullptr, *scint_seed = nullptr, *scint_site = nullptr;
-    std::vector<const char *> prn_power, jam;
+               *scint = nullptr, *scint_seed = nullptr, *scint_site = nullptr, *array = nullptr, *array_log = nullptr;
+    std::vector<const char *> prn_power, jam, jam_dir;
     long agc_window_n = 8;
     double agc_target = 0.0, agc_init_rms = -1.0;  // (0 / < 0: the defaults, known once shift and sigma are)
     double sig_peak = 4100.0;                      // the largest |x| of the signal sum: 4100 in the reference's scenarios
@@ -428,7 +428,7 @@ struct Args {
 };
 
 enum { OPT_STRICT = 1000, OPT_SITES, OPT_WRITERS, OPT_GPUS, OPT_PER_GPU, OPT_EXACT, OPT_SHIFT_TOE, OPT_REF_T, OPT_JAM, OPT_POWER_MODEL, OPT_PRN_POWER, OPT_AGC,
-       OPT_STRING };  // OPT_STRING + k: the k-th row whose argument is only kept (Args::*dest)
+       OPT_JAM_DIR, OPT_STRING };  // OPT_STRING + k: the k-th row whose argument is only kept (Args::*dest)
 constexpr int NO = no_argument, ARG = required_argument, MAYBE = optional_argument;
 struct OptRow {
     const char *name;  // one letter: a short option (its id is the letter)
@@ -459,7 +459,8 @@ const OptRow kOptions[] = {
     {"lo-offset", ARG, OPT_STRING + 18, true, &Args::lo_offset}, {"phase-noise", ARG, OPT_STRING + 19, true, &Args::phase_noise},
     {"osc-seed", ARG, OPT_STRING + 20, true, &Args::osc_seed}, {"osc-stream", ARG, OPT_STRING + 21, false, &Args::osc_stream},
     {"scint", ARG, OPT_STRING + 22, true, &Args::scint}, {"scint-seed", ARG, OPT_STRING + 23, true, &Args::scint_seed},
-    {"scint-site", ARG, OPT_STRING + 24, false, &Args::scint_site},
+    {"scint-site", ARG, OPT_STRING + 24, false, &Args::scint_site}, {"array", ARG, OPT_STRING + 25, false, &Args::array},
+    {"array-log", ARG, OPT_STRING + 26, false, &Args::array_log}, {"jam-dir", ARG, OPT_JAM_DIR, false, nullptr},
 };
 
 // the command line into Args and the Config's plain fields; every option with to_children also into c->child_args
@@ -536,6 +537,7 @@ void parse_args(int argc, char *argv[], Args *a, Config *c)
         case OPT_GPUS: c->sites_gpus = atoi(optarg); break;
         case OPT_PER_GPU: c->sites_per_gpu = atoi(optarg); break;
         case OPT_JAM: a->jam.push_back(optarg); break;
+        case OPT_JAM_DIR: a->jam_dir.push_back(optarg); break;
         case OPT_POWER_MODEL: a->power_model = true; break;
         case OPT_PRN_POWER: a->prn_power.push_back(optarg); break;
         case OPT_AGC: a->agc_given = true; break;
@@ -609,6 +611,75 @@ void cfg_format(Args &a, Config &c)
     }
 }
 
+// --array <file>: east_m,north_m,up_m per line; what follows a # is a comment
+bool load_array(const char *path, std::vector<ArrayElem> *out, std::string *why)
+{
+    FILE *f = fopen(path, "r");
+    if (!f) return *why = "cannot be opened", false;
+    char line[512];
+    for (int ln = 1; fgets(line, sizeof(line), f); ++ln) {
+        if (char *h = strchr(line, '#')) *h = 0;
+        const char *p = line;
+        while (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n') ++p;
+        if (!*p) continue;
+        ArrayElem e;
+        char tail = 0;
+        if (sscanf(p, "%lf , %lf , %lf %c", &e.enu[0], &e.enu[1], &e.enu[2], &tail) != 3 || !std::isfinite(e.enu[0]) || !std::isfinite(e.enu[1]) ||
+            !std::isfinite(e.enu[2])) {
+            fclose(f);
+            return *why = "line " + std::to_string(ln) + " is not east_m,north_m,up_m", false;
+        }
+        out->push_back(e);
+    }
+    fclose(f);
+    if (out->empty() || out->size() > GAL_ARRAY_MAX_ELEM) return *why = "it must hold 1 to " + std::to_string(GAL_ARRAY_MAX_ELEM) + " elements", false;
+    return true;
+}
+
+// --array, --array-log, --jam-dir: the elements, the directions of the --jam sources, and what does not go with an array.  Echo
+// directions need a direction of arrival per echo, and the four stateful stages keep ONE state per handle where an array needs one per
+// element
+void cfg_array(const Args &a, Config &c)
+{
+    const double kD2R = 3.14159265358979323846 / 180.0;
+    for (int k = 0; k < GAL_INTERF_MAX; ++k) c.jam_az[k] = 0.0, c.jam_el[k] = 90.0 * kD2R;
+    if (!a.array) {
+        if (a.array_log) die("ERROR: --array-log needs --array <file>.\n");
+        if (!a.jam_dir.empty()) die("ERROR: --jam-dir needs --array <file>.\n");
+        return;
+    }
+    if (a.multipath) die("ERROR: --array does not go with --multipath: an echo needs a direction of arrival of its own.\n");
+    if (a.lo_offset || a.phase_noise) die("ERROR: --array does not go with --lo-offset / --phase-noise: the oscillator keeps one state per engine, an array needs one per element.\n");
+    if (a.fir || a.fir_lowpass) die("ERROR: --array does not go with --fir / --fir-lowpass: the filter keeps one history per engine, an array needs one per element.\n");
+    if (a.oversample) die("ERROR: --array does not go with --oversample: the decimator keeps one history per engine, an array needs one per element.\n");
+    if (a.agc_given) die("ERROR: --array does not go with --agc: the AGC keeps one state per engine, an array needs one per element.\n");
+    if (c.iq_format == GAL_IQ_I2BIT) die("ERROR: --array does not go with --iq-format i2bit: the 2-bit format is the AGC's.\n");
+    if (a.monitor) die("ERROR: --array does not go with --monitor: the monitor follows one stream.\n");
+    if (!c.sitesfile.empty()) die("ERROR: --array does not go with --sites.\n");
+    if (c.outfile == "-") die("ERROR: --array writes one file per element; -o - is one stream.\n");
+    if (a.jam_dir.size() > a.jam.size()) die("ERROR: --jam-dir may be given once per --jam (%zu --jam, %zu --jam-dir).\n", a.jam.size(), a.jam_dir.size());
+    for (size_t k = 0; k < a.jam_dir.size(); ++k) {
+        double az = 0.0, el = 0.0;
+        char tail = 0;
+        if (sscanf(a.jam_dir[k], "%lf , %lf %c", &az, &el, &tail) != 2 || !std::isfinite(az) || !std::isfinite(el) || el < -90.0 || el > 90.0)
+            die("ERROR: --jam-dir '%s' is not az_deg,el_deg (elevation -90..90).\n", a.jam_dir[k]);
+        c.jam_az[k] = az * kD2R;
+        c.jam_el[k] = el * kD2R;
+    }
+    std::string why;
+    if (!load_array(a.array, &c.array, &why)) die("ERROR: --array %s: %s.\n", a.array, why.c_str());
+    if (a.array_log && (!*a.array_log || strcmp(a.array_log, "-") == 0)) die("ERROR: --array-log needs a file name.\n");
+    c.array_log_file = a.array_log;
+    say(c, "Antenna array: %zu element%s (east, north, up in metres from the reference point; the body does not rotate)\n", c.array.size(),
+        c.array.size() == 1 ? "" : "s");
+    for (size_t k = 0; k < c.array.size(); ++k)
+        say(c, "  element %zu: %.4f, %.4f, %.4f%s\n", k, c.array[k].enu[0], c.array[k].enu[1], c.array[k].enu[2],
+            a.cn0 ? (" (noise stream 8 x --noise-stream + " + std::to_string(k) + ")").c_str() : "");
+    for (size_t k = 0; k < a.jam.size(); ++k)
+        say(c, "  --jam %zu arrives from azimuth %.2f deg, elevation %.2f deg%s\n", k + 1, c.jam_az[k] / kD2R, c.jam_el[k] / kD2R,
+            k < a.jam_dir.size() ? "" : " (no --jam-dir: the zenith)");
+}
+
 // per-satellite signal power, --multipath and --oversample: what scales the headroom's signal term, and the rate the passes run at
 void cfg_signals(Args &a, Config &c)
 {
@@ -676,6 +747,10 @@ void cfg_signals(Args &a, Config &c)
         if (sat_peak > 1.0) say(c, "Scintillation: a satellite is taken at up to %.3f times its own amplitude\n", sat_peak);
     }
     a.sig_peak = 4100.0 * power_peak * sat_peak;
+    if (c.array_on()) {  // a rotation can move up to sqrt(2) of a part's amplitude onto one rail
+        a.sig_peak *= sqrt(2.0);
+        say(c, "Antenna array: the signal term of the automatic --signal-gain / --iq-shift is taken sqrt(2) larger, %.0f LSB (a rotated part)\n", a.sig_peak);
+    }
 }
 
 void given_gain(Args &a)
@@ -1080,6 +1155,7 @@ void parse_options(int argc, char *argv[], Config *c)
     c->talk = c->sitesfile.empty();
     cfg_time(a, *c);
     cfg_format(a, *c);
+    cfg_array(a, *c);
     cfg_signals(a, *c);
     cfg_mix(a, *c);
     cfg_monitor(a, *c);

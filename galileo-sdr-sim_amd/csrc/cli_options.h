@@ -30,6 +30,11 @@ struct ScintSpec {
     gal_iq_scint_t row;  // made once the sample rate is known; stream = site index << 8 | prn
 };
 
+// --array <file>: one antenna element per line, east_m,north_m,up_m from the array's reference point; # starts a comment
+struct ArrayElem {
+    double enu[3];
+};
+
 struct Config {
     gal_scen_cfg_t sc;  // (nav_file / motion_file point into navfile / umfile: set by main, once the Config has its place)
     std::string navfile, outfile, umfile, sitesfile;
@@ -46,6 +51,10 @@ struct Config {
     double ant_db[GAL_GAIN_PATTERN_LEN], prn_db[GAL_NUM_PRN];
     std::vector<EchoSpec> echoes;  // --multipath
     std::vector<ScintSpec> scints; // --scint
+    std::vector<ArrayElem> array;  // --array: the batch goes through gal_synth_run_array, one output file per element
+    double jam_az[GAL_INTERF_MAX], jam_el[GAL_INTERF_MAX];  // --jam-dir, radians; without one the zenith
+    const char *array_log_file = nullptr;
+    FILE *array_log_fp = nullptr;
     bool noise_on = false;         // --cn0
     gal_iq_noise_t noise;          // (without --cn0 it still carries the signal gain of the --jam sources)
     int n_jam = 0;
@@ -68,12 +77,14 @@ struct Config {
     bool fir_on() const { return n_fir > 0; }
     bool mp_on() const { return !echoes.empty(); }
     bool sc_on() const { return !scints.empty(); }
+    bool array_on() const { return !array.empty(); }
+    int n_elem() const { return array_on() ? (int)array.size() : 1; }
     bool parts_on() const { return mp_on() || sc_on(); }  // the batch goes through gal_synth_run_scint (echoes, scintillation or both)
     bool mix_on() const { return noise_on || n_jam > 0; }  // a pass over the final int16 batch in front of the format
     int agc_param() const { return iq_format == GAL_IQ_IBYTE ? iq_shift : iq_format == GAL_IQ_I2BIT ? i2bit_thr : 0; }
     // bytes of n samples in the output format: the AGC has its own count (i2bit is a format of the AGC call only)
     size_t out_bytes(size_t n) const { return agc_on ? gal_synth_agc_out_bytes(iq_format, n) : gal_synth_iq_bytes(iq_format, n); }
-    bool any_pass() const { return mix_on() || power_on || parts_on() || fir_on() || agc_on || osc_on; }
+    bool any_pass() const { return mix_on() || power_on || parts_on() || array_on() || fir_on() || agc_on || osc_on; }
     // what the copies read was enqueued on the engine's stream: they wait for an event behind it
     bool chain_on_engine_stream() const { return iq_format != GAL_IQ_ISHORT || any_pass(); }
     // the run ends with the saturation report.  Not the predicate above: ibit alone clamps nothing

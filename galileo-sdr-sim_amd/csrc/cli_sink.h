@@ -18,6 +18,8 @@
 struct Slot {  // one pinned host buffer of the double-buffered sink
     int16_t *host = nullptr;
     size_t bytes = 0;
+    int n_elem = 1;     // --array: the elements' outputs lie one behind the other, `stride` bytes apart, `bytes` of each are the batch's;
+    size_t stride = 0;  // the writer thread splits them into the elements' files
     hipEvent_t copied[2] = {nullptr, nullptr};  // the batch leaves the GPU in two halves on two copy streams
     bool full = false;
 };

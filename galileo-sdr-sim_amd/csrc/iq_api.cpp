@@ -1,5 +1,5 @@
 // iq_api.cpp -- the output chain's half of the C ABI (include/galsynth.h): every pass over the finished int16 stream -- formats, noise
-// floor, interference, per-satellite gains, multipath, scintillation, FIR, decimating FIR, AGC, oscillator -- and the correlator bank, over the kernels of
+// floor, interference, per-satellite gains, multipath, scintillation, the antenna array, FIR, decimating FIR, AGC, oscillator -- and the correlator bank, over the kernels of
 // csrc/iq_*.hip.  Host-side plumbing only: validation, the stages' device state, kernel sequencing.  The handle itself, plan, execute
 // and finish are synth_api.cpp's; synth_handle.h is what the two share.  Nothing here depends on GAL_TEST_HOOKS: one object serves
 // libgalsynth.so and libgalsynth_hooks.so.
@@ -37,6 +37,9 @@ hipError_t galk_launch_iq_echo(const int16_t *const *parts_dev, const int16_t *c
                                int16_t *out, unsigned long long *sat, hipStream_t st);
 hipError_t galk_launch_iq_wsum(const int16_t *const *parts_dev, const int *gain_dev, int n_parts, int n_epochs, int samples_per_epoch, int wide,
                                int16_t *out, unsigned long long *sat, hipStream_t st);
+hipError_t galk_launch_iq_array(const int16_t *const *parts_dev, int16_t *const *outs_dev, const uint32_t *wts_dev, int n_parts, int n_elem,
+                                int n_epochs, int samples_per_epoch, int wide, unsigned long long *sat, hipStream_t st);
+void galk_array_pack(int w_re, int w_im, uint32_t *two);
 hipError_t galk_launch_corr(int format, const void *buf, uint64_t n_eff, uint64_t code_ph0, uint64_t code_dph, uint32_t carr_ph0,
                             uint32_t carr_step0, uint32_t dopp_step, int delay0, int delay_step, int n_delay, int n_dopp, int max_periods,
                             const uint32_t *lut_dev, const uint32_t *code_dev, long long *out, hipStream_t st);
@@ -1123,11 +1126,117 @@ int gal_synth_iq_scint(gal_synth_t *h, const gal_scint_job_t *jobs, int32_t n_jo
     return GAL_OK;
 }
 
-// gal_synth_run_gains (n_echo = 0), gal_synth_run_mpath and gal_synth_run_scint (scint_rows != null): the slot groups, one synthesis
-// run per group, the scintillation of the parts that have one, then the weighted sum or the echo pass
+// ---- antenna array (iq_array.hip) ---------------------------------------------------------------------------------------------------
+int gal_synth_steer_check(const gal_iq_steer_t *rows, int32_t n_epochs, int32_t n_elem, int32_t n_parts)
+{
+    const char *who = "gal_synth_steer_check";
+    if (!rows) return fail(GAL_E_INVAL, "%s: null rows", who);
+    if (n_epochs < 1 || n_elem < 1 || n_elem > GAL_ARRAY_MAX_ELEM || n_parts < 1 || n_parts > GAL_ENGINE_MAX_CHAN)
+        return fail(GAL_E_INVAL, "%s: n_epochs %d (>= 1), n_elem %d (1..%d) or n_parts %d (1..%d)", who, n_epochs, n_elem, GAL_ARRAY_MAX_ELEM, n_parts,
+                    GAL_ENGINE_MAX_CHAN);
+    const size_t per = (size_t)n_elem * n_parts;
+    for (size_t i = 0; i < (size_t)n_epochs * per; ++i)
+        if (rows[i].w_re == INT16_MIN || rows[i].w_im == INT16_MIN)
+            return fail(GAL_E_INVAL, "%s: weight (%d, %d) of epoch %zu, element %zu, part %zu (-32767..32767)", who, rows[i].w_re, rows[i].w_im, i / per,
+                        i % per / n_parts, i % n_parts);
+    return GAL_OK;
+}
+
+int gal_synth_steer_make(uint16_t gain_q7, uint32_t phase, gal_iq_steer_t *out)
+{
+    if (!out) return fail(GAL_E_INVAL, "gal_synth_steer_make: null argument");
+    if (gain_q7 > GAL_STEER_GAIN_MAX)
+        return fail(GAL_E_INVAL, "gal_synth_steer_make: gain %u (0..%d: the weight would leave int16)", gain_q7, GAL_STEER_GAIN_MAX);
+    const int16_t *C = gal_tables_cos1024();
+    const uint32_t i = ((phase + (1u << 21)) >> 22) & 1023u;
+    const int g = gain_q7;
+    out->w_re = (int16_t)((g * C[i] + 64) >> 7);
+    out->w_im = (int16_t)((g * C[(i - 256u) & 1023u] + 64) >> 7);
+    return GAL_OK;
+}
+
+int gal_synth_array_phase(const double enu_m[3], double az_rad, double el_rad, uint32_t *phase)
+{
+    if (!enu_m || !phase) return fail(GAL_E_INVAL, "gal_synth_array_phase: null argument");
+    if (!std::isfinite(enu_m[0]) || !std::isfinite(enu_m[1]) || !std::isfinite(enu_m[2]) || !std::isfinite(az_rad) || !std::isfinite(el_rad))
+        return fail(GAL_E_INVAL, "gal_synth_array_phase: an argument is not finite");
+    const double lambda = 299792458.0 / 1575420000.0;
+    const double ce = cos(el_rad);
+    const double u[3] = {sin(az_rad) * ce, cos(az_rad) * ce, sin(el_rad)};
+    const double cyc = (enu_m[0] * u[0] + enu_m[1] * u[1] + enu_m[2] * u[2]) / lambda;
+    *phase = (uint32_t)((uint64_t)llround((cyc - floor(cyc)) * 4294967296.0) & 0xffffffffull);
+    return GAL_OK;
+}
+
+// the element outputs of an array call, `bytes` each: aligned, none meeting another
+static int check_outputs(const char *who, int16_t *const *out_dev, int n_elem, size_t bytes)
+{
+    for (int a = 0; a < n_elem; ++a) {
+        GAL_TRY(check_aligned(who, out_dev[a]));
+        for (int b = 0; b < a; ++b)
+            if (ranges_overlap(out_dev[a], bytes, out_dev[b], bytes)) return fail(GAL_E_INVAL, "%s: the outputs of elements %d and %d overlap", who, b, a);
+    }
+    return GAL_OK;
+}
+
+int gal_synth_iq_array(gal_synth_t *h, const int16_t *const *parts_dev, int32_t n_parts, const gal_iq_steer_t *rows, int32_t n_epochs,
+                       int32_t n_elem, int16_t *const *out_dev)
+{
+    const char *who = "gal_synth_iq_array";
+    if (!h) return fail(GAL_E_INVAL, "null handle");
+    if (!parts_dev || !out_dev) return fail(GAL_E_INVAL, "%s: null argument", who);
+    GAL_TRY(gal_synth_steer_check(rows, n_epochs, n_elem, n_parts));
+    const size_t bytes = (size_t)n_epochs * (size_t)h->cfg.samples_per_epoch * 4;
+    GAL_TRY(check_outputs(who, out_dev, n_elem, bytes));
+    for (int a = 0; a < n_elem; ++a) GAL_TRY(check_parts(who, h, parts_dev, n_parts, out_dev[a], bytes));
+    uint64_t row_max = 0;  // the largest sum of |w_re| + |w_im| over the parts of one (epoch, element): what A needs (iq_array.hip)
+    for (size_t r = 0; r < (size_t)n_epochs * n_elem; ++r) {
+        uint64_t row = 0;
+        for (int k = 0; k < n_parts; ++k) row += (uint64_t)std::abs((int)rows[r * n_parts + k].w_re) + (uint64_t)std::abs((int)rows[r * n_parts + k].w_im);
+        row_max = std::max(row_max, row);
+    }
+    hipStream_t st;
+    GAL_TRY(enter(h, &st));
+    // the table of this call: part pointers, output pointers, then the packed weights.  One per handle: a call waits for the kernel of
+    // the call before it
+    HIP_TRY(h->array.sync.wait());
+    const size_t o_out = sizeof(void *) * GAL_ENGINE_MAX_CHAN, o_w = o_out + sizeof(void *) * GAL_ARRAY_MAX_ELEM;
+    const size_t need = o_w + (size_t)n_epochs * n_parts * n_elem * 2 * sizeof(uint32_t);
+    uint64_t cap = 0;
+    const int rc = h->array.table.reserve(need, 0, true, h->array.sync, &cap);
+    if (rc == GAL_E_NOMEM) return fail(GAL_E_NOMEM, "%s: the weight table of %zu bytes could not be allocated", who, (size_t)cap);
+    if (rc) return rc;
+    memset(h->array.table.host, 0, o_w);
+    memcpy(h->array.table.host, parts_dev, sizeof(void *) * (size_t)n_parts);
+    memcpy(h->array.table.host + o_out, out_dev, sizeof(void *) * (size_t)n_elem);
+    uint32_t *const hw = (uint32_t *)(h->array.table.host + o_w);  // [e][k][a][2]: the elements of one part side by side
+    for (int e = 0; e < n_epochs; ++e)
+        for (int a = 0; a < n_elem; ++a)
+            for (int k = 0; k < n_parts; ++k) {
+                const gal_iq_steer_t &w = rows[((size_t)e * n_elem + a) * n_parts + k];
+                galk_array_pack(w.w_re, w.w_im, hw + (((size_t)e * n_parts + k) * n_elem + a) * 2);
+            }
+    HIP_TRY(hipMemcpyAsync(h->array.table.dev, h->array.table.host, need, hipMemcpyHostToDevice, st));
+    HIP_TRY(galk_launch_iq_array((const int16_t *const *)h->array.table.dev, (int16_t *const *)(h->array.table.dev + o_out),
+                                 (const uint32_t *)(h->array.table.dev + o_w), n_parts, n_elem, n_epochs, h->cfg.samples_per_epoch, row_max > 65535 ? 1 : 0,
+                                 h->d_iq_sat, st));
+    HIP_TRY(h->array.sync.mark(st));
+    return GAL_OK;
+}
+
+// what gal_synth_run_array adds to run_groups: every active slot a group of its own, and gal_synth_iq_array as the final stage
+struct ArrayRun {
+    const uint32_t *phase;  // [E][n_elem][S]
+    int n_elem;
+    int16_t *const *out_dev;
+};
+
+// gal_synth_run_gains (n_echo = 0), gal_synth_run_mpath, gal_synth_run_scint (scint_rows != null) and gal_synth_run_array (arr != null,
+// iq_dev = its first output): the slot groups, one synthesis run per group, the scintillation of the parts that have one, then the
+// weighted sum, the echo pass or the array pass
 static int run_groups(const char *who, gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_epochs, const gal_chan_state_t *state_in,
                       const uint16_t *gain_q7, const int32_t *slot_of_echo, const gal_iq_echo_t *echo_rows, int32_t n_echo, int16_t *iq_dev,
-                      gal_chan_state_t *state_out, const gal_iq_scint_t *scint_rows = nullptr, uint64_t first_sample = 0)
+                      gal_chan_state_t *state_out, const gal_iq_scint_t *scint_rows = nullptr, uint64_t first_sample = 0, const ArrayRun *arr = nullptr)
 {
     if (!h || !params || !gain_q7 || !iq_dev || n_epochs < 1) return fail(GAL_E_INVAL, "%s: null argument or n_epochs %d (>= 1)", who, n_epochs);
     if ((uintptr_t)iq_dev & 15) return fail(GAL_E_INVAL, "%s: iq_dev must be 16-byte aligned", who);
@@ -1157,6 +1266,9 @@ static int run_groups(const char *who, gal_synth_t *h, const gal_chan_epoch_t *p
     bool any_fade = false;
     for (size_t i = 0; scint_rows && i < (size_t)E * S; ++i)
         if (!scint_identity(scint_rows[i])) fades[i % S] = solo[i % S] = 1, any_fade = true;
+    // ... and, for an array, every slot that is active in any epoch: its part is x_s itself, which the elements' weights turn
+    for (size_t i = 0; arr && i < (size_t)E * S; ++i)
+        if (params[i].prn > 0) solo[i % S] = 1;
     for (int s = 0; s < S; ++s) {
         bool active = solo[s];
         for (int e = 0; e < E && !active; ++e) active = params[(size_t)e * S + s].prn > 0;
@@ -1179,17 +1291,18 @@ static int run_groups(const char *who, gal_synth_t *h, const gal_chan_epoch_t *p
             if (params[(size_t)e * S + s].prn > 0) groups[k].g[e] = gain_q7[(size_t)e * S + s];
     }
     const int n_parts = groups.empty() ? 1 : (int)groups.size();  // (an empty sky: one run of nothing)
-    bool unity = n_parts == 1 && n_echo == 0 && !any_fade;  // one part at gain 128 wherever it is not zero: y = x, the run goes straight into iq_dev
+    bool unity = n_parts == 1 && n_echo == 0 && !any_fade && !arr;  // one part at gain 128 wherever it is not zero: y = x, the run goes straight into iq_dev
     if (!groups.empty())
         for (int e = 0; e < E && unity; ++e) unity = groups[0].g[e] < 0 || groups[0].g[e] == GAL_GAIN_UNITY;
     const size_t bytes = (size_t)E * (size_t)h->cfg.samples_per_epoch * 4;
     // the weighted sum of the call before may still read the scratch buffers: wait for it here, whatever stream the handle is on now
     // (on one stream the runs below would order behind it by themselves)
-    if (h->gain.sync.pending || h->mp.sync.pending || h->scint.sync.pending) {
+    if (h->gain.sync.pending || h->mp.sync.pending || h->scint.sync.pending || h->array.sync.pending) {
         HIP_TRY(hipSetDevice(h->device));
         HIP_TRY(h->gain.sync.wait());
         HIP_TRY(h->mp.sync.wait());
         HIP_TRY(h->scint.sync.wait());
+        HIP_TRY(h->array.sync.wait());
     }
     h->gain_runs = 0;
     if (!unity && bytes * (size_t)n_parts > h->own_parts_bytes) {
@@ -1251,7 +1364,19 @@ static int run_groups(const char *who, gal_synth_t *h, const gal_chan_epoch_t *p
             if (rc != GAL_OK) return rc;
         }
     }
-    if (!unity) {
+    if (arr) {
+        // the weight of (epoch, element, part): that of the part's one slot, (0, 0) where it is idle (and for the one part of an empty sky)
+        const int K = arr->n_elem;
+        std::vector<gal_iq_steer_t> w((size_t)E * K * n_parts);  // (value-initialised: zeros)
+        for (int e = 0; e < E; ++e)
+            for (int a = 0; a < K; ++a)
+                for (size_t k = 0; k < groups.size(); ++k) {
+                    const int s = groups[k].slots[0];
+                    if (params[(size_t)e * S + s].prn <= 0) continue;
+                    GAL_TRY(gal_synth_steer_make(gain_q7[(size_t)e * S + s], arr->phase[((size_t)e * K + a) * S + s], &w[((size_t)e * K + a) * n_parts + k]));
+                }
+        GAL_TRY(gal_synth_iq_array(h, parts, n_parts, w.data(), E, K, arr->out_dev));
+    } else if (!unity) {
         std::vector<uint16_t> gp((size_t)E * n_parts);
         for (int e = 0; e < E; ++e)
             for (int k = 0; k < n_parts; ++k) gp[(size_t)e * n_parts + k] = (uint16_t)(groups[k].g[e] < 0 ? 0 : groups[k].g[e]);
@@ -1307,6 +1432,27 @@ int gal_synth_run_scint(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t 
     }
     return run_groups(who, h, params, n_epochs, state_in, gain_q7, n_echo ? slot_of_echo : nullptr, n_echo ? echo_rows : nullptr, n_echo, iq_dev, state_out,
                       scint_rows, first_sample);
+}
+
+int gal_synth_run_array(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_epochs, const gal_chan_state_t *state_in,
+                        const uint16_t *gain_q7, const uint32_t *phase, int32_t n_elem, const gal_iq_scint_t *scint_rows,
+                        uint64_t first_sample, int16_t *const *out_dev, gal_chan_state_t *state_out)
+{
+    const char *who = "gal_synth_run_array";
+    if (!h || !params || !gain_q7 || !phase || !out_dev || n_epochs < 1) return fail(GAL_E_INVAL, "%s: null argument or n_epochs %d (>= 1)", who, n_epochs);
+    if (n_elem < 1 || n_elem > GAL_ARRAY_MAX_ELEM) return fail(GAL_E_INVAL, "%s: n_elem %d (1..%d)", who, n_elem, GAL_ARRAY_MAX_ELEM);
+    const size_t S = (size_t)h->cfg.n_slots, bytes = (size_t)n_epochs * (size_t)h->cfg.samples_per_epoch * 4;
+    for (size_t i = 0; i < (size_t)n_epochs * S; ++i)
+        if (gain_q7[i] > GAL_STEER_GAIN_MAX)
+            return fail(GAL_E_INVAL, "%s: gain %u of slot %zu in epoch %zu (0..%d: +18 dB over unity)", who, gain_q7[i], i % S, i / S, GAL_STEER_GAIN_MAX);
+    GAL_TRY(check_outputs(who, out_dev, n_elem, bytes));  // before the synthesis runs: what gal_synth_iq_array would refuse behind them
+    if (scint_rows) {
+        const uint64_t total = (uint64_t)n_epochs * (uint64_t)h->cfg.samples_per_epoch;
+        if (first_sample >> 62 || (first_sample + total) >> 62) return fail(GAL_E_INVAL, "%s: the batch must end below sample 2^62", who);
+        for (size_t i = 0; i < (size_t)n_epochs * S; ++i) GAL_TRY(gal_synth_scint_check(&scint_rows[i]));
+    }
+    const ArrayRun arr = {phase, n_elem, out_dev};
+    return run_groups(who, h, params, n_epochs, state_in, gain_q7, nullptr, nullptr, 0, out_dev[0], state_out, scint_rows, first_sample, &arr);
 }
 
 int gal_synth_gain_runs(const gal_synth_t *h, int32_t *n_runs)

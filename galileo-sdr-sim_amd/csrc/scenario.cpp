@@ -373,8 +373,8 @@ int gal_scen_set_path_loss(gal_scen_t *s, int32_t enable)
     return GAL_OK;
 }
 
-// gal_scen_next and gal_scen_next_gains (gain_q7 == nullptr: the rows alone)
-static int32_t next_rows(gal_scen_t *s, int32_t max_epochs, gal_chan_epoch_t *rows, uint16_t *gain_q7)
+// gal_scen_next, gal_scen_next_gains and gal_scen_next_azel (gain_q7 == nullptr: no gains; azel == nullptr: no directions)
+static int32_t next_rows(gal_scen_t *s, int32_t max_epochs, gal_chan_epoch_t *rows, uint16_t *gain_q7, double *azel)
 {
     const int S = s->cfg.n_slots;
     int produced = 0;
@@ -383,6 +383,8 @@ static int32_t next_rows(gal_scen_t *s, int32_t max_epochs, gal_chan_epoch_t *ro
         memset(row, 0, sizeof(gal_chan_epoch_t) * S);
         uint16_t *const grow = gain_q7 ? gain_q7 + (size_t)produced * S : nullptr;
         if (grow) memset(grow, 0, sizeof(uint16_t) * S);  // idle slots: 0
+        double *const arow = azel ? azel + (size_t)produced * S * 2 : nullptr;
+        for (int i = 0; arow && i < 2 * S; ++i) arow[i] = 0.0;  // idle slots: 0, 0
         poll_live_position(s);
         const double *xyz = position(s, s->iumd);
         for (int i = 0; i < S; ++i) {
@@ -402,6 +404,7 @@ static int32_t next_rows(gal_scen_t *s, int32_t max_epochs, gal_chan_epoch_t *ro
                 grow[i] = (uint16_t)gal_gain_q7_eval(s->path_loss ? rho.d : GAL_GAIN_REF_DISTANCE_M, rho.azel[1],
                                                      s->have_pattern ? s->pattern_db : nullptr,
                                                      c.prn <= GAL_NUM_PRN ? s->prn_offset_db[c.prn - 1] : 0.0);
+            if (arow) arow[2 * i] = rho.azel[0], arow[2 * i + 1] = rho.azel[1];
 
             // computeCodePhase, src/gal-sig.cpp:308-347
             const double rhorate = (rho.range - c.rho0.range) / kEpochDt;
@@ -473,13 +476,19 @@ static int32_t next_rows(gal_scen_t *s, int32_t max_epochs, gal_chan_epoch_t *ro
 int32_t gal_scen_next(gal_scen_t *s, int32_t max_epochs, gal_chan_epoch_t *rows)
 {
     if (!s || !rows || max_epochs < 0) return scen_fail(GAL_E_INVAL, "gal_scen_next: bad argument");
-    return next_rows(s, max_epochs, rows, nullptr);
+    return next_rows(s, max_epochs, rows, nullptr, nullptr);
 }
 
 int32_t gal_scen_next_gains(gal_scen_t *s, int32_t max_epochs, gal_chan_epoch_t *rows, uint16_t *gain_q7)
 {
     if (!s || !rows || !gain_q7 || max_epochs < 0) return scen_fail(GAL_E_INVAL, "gal_scen_next_gains: bad argument");
-    return next_rows(s, max_epochs, rows, gain_q7);
+    return next_rows(s, max_epochs, rows, gain_q7, nullptr);
+}
+
+int32_t gal_scen_next_azel(gal_scen_t *s, int32_t max_epochs, gal_chan_epoch_t *rows, uint16_t *gain_q7, double *azel)
+{
+    if (!s || !rows || !azel || max_epochs < 0) return scen_fail(GAL_E_INVAL, "gal_scen_next_azel: bad argument");
+    return next_rows(s, max_epochs, rows, gain_q7, azel);
 }
 
 int gal_scen_inav_page(gal_scen_t *s, int32_t svid, int32_t eph_index, int32_t week, double sec,

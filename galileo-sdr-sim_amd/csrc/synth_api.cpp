@@ -429,6 +429,7 @@ int gal_synth_destroy(gal_synth_t *h)
     h->agc.release();
     h->osc.release();
     h->scint.release();
+    h->array.release();
     if (h->d_lut) hipFree(h->d_lut);
     if (h->d_str) hipFree(h->d_str);
     if (h->h_up) hipHostFree(h->h_up);

@@ -208,6 +208,19 @@ struct ScintStage {
     }
 };
 
+// gal_synth_iq_array (iq_array.hip): table = the table of the last call (part pointers [GAL_ENGINE_MAX_CHAN], output pointers
+// [GAL_ARRAY_MAX_ELEM], then the packed weights [n_epochs][n_parts][n_elem][2] words), pinned on the host and on the device; sync = that
+// call's kernel is done
+struct ArrayStage {
+    GrownBuf table;
+    StageSync sync;
+    void release()
+    {
+        table.release();
+        sync.destroy();
+    }
+};
+
 struct gal_synth {
     StagedPlan staged;           // the plan made while a batch was in flight (or being committed)
     bool staged_pending = false;  // ... waits for its commit
@@ -299,6 +312,7 @@ struct gal_synth {
     AgcStage agc;
     OscStage osc;
     ScintStage scint;
+    ArrayStage array;
 };
 
 // The stream the handle works on: the caller's (gal_synth_set_stream), or one of its own, made at first need.

@@ -22,6 +22,7 @@ EXPORTED_SYMBOLS = (
     "gal_scen_set_power",
     "gal_scen_set_path_loss",
     "gal_scen_next_gains",
+    "gal_scen_next_azel",
     "gal_scen_close",
     "gal_scen_inav_page",
     "gal_scen_inav_raw",
@@ -76,6 +77,7 @@ def load_library():
         lib.gal_scen_set_power.argtypes = [vp, vp, vp]
         lib.gal_scen_set_path_loss.argtypes = [vp, ctypes.c_int32]
         lib.gal_scen_next_gains.argtypes = [vp, ctypes.c_int32, vp, vp]
+        lib.gal_scen_next_azel.argtypes = [vp, ctypes.c_int32, vp, vp, vp]
         lib.gal_scen_close.argtypes = [vp]
         lib.gal_scen_eph_gaps.argtypes = [vp]
         lib.gal_scen_live_rejected.argtypes = [vp]
@@ -195,6 +197,18 @@ class Scenario:
         if n < 0:
             raise GalScenError(n, self._lib.gal_scen_last_error().decode())
         return rows[:n], gains[:n]
+
+    def next_azel(self, max_epochs, gains=True):
+        """gal_scen_next_azel: (rows, gain_q7, azel) -- the rows and gains of next_gains() (gains=False: gain_q7 is None, the rows of
+        next()) and azel [n, n_slots, 2]: per row and slot the azimuth (from north over east) and the elevation in radians, 0, 0 on
+        idle slots -- what synth.array_phase and SynthEngine.run_array take."""
+        rows = np.zeros((max_epochs, self.n_slots), dtype=CHAN_EPOCH_DTYPE)
+        g = np.zeros((max_epochs, self.n_slots), dtype=np.uint16) if gains else None
+        azel = np.zeros((max_epochs, self.n_slots, 2), dtype=np.float64)
+        n = self._lib.gal_scen_next_azel(self._h, int(max_epochs), rows.ctypes.data, g.ctypes.data if gains else None, azel.ctypes.data)
+        if n < 0:
+            raise GalScenError(n, self._lib.gal_scen_last_error().decode())
+        return rows[:n], (g[:n] if gains else None), azel[:n]
 
     def all(self):
         return self.next(self.total_epochs)

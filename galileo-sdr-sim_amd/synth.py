@@ -195,6 +195,18 @@ GAL_SCINT_MAX_NODE = 1 << 24
 GAL_SCINT_MAX_JOBS = 64
 
 
+class _Steer(ctypes.Structure):  # gal_iq_steer_t (4 bytes)
+    _fields_ = [("w_re", ctypes.c_int16), ("w_im", ctypes.c_int16)]
+
+
+assert ctypes.sizeof(_Steer) == 4
+# one weight of an array as numpy sees it: steer rows are arrays of this type, [n_epochs, n_elem, n_parts]
+STEER_DTYPE = np.dtype([("w_re", "<i2"), ("w_im", "<i2")])
+assert STEER_DTYPE.itemsize == 4
+GAL_ARRAY_MAX_ELEM = 8
+GAL_STEER_GAIN_MAX = 1023
+
+
 class _Echo(ctypes.Structure):  # gal_iq_echo_t (16 bytes)
     _fields_ = [
         ("gain_q7", ctypes.c_uint16),
@@ -310,6 +322,11 @@ EXPORTED_SYMBOLS = (
     "gal_synth_scint_make",
     "gal_synth_iq_scint",
     "gal_synth_run_scint",
+    "gal_synth_steer_check",
+    "gal_synth_steer_make",
+    "gal_synth_array_phase",
+    "gal_synth_iq_array",
+    "gal_synth_run_array",
     "gal_synth_corr_out_bytes",
     "gal_synth_correlate",
     "gal_tables_e1b",
@@ -447,6 +464,16 @@ def load_library(hooks=False):
     lib.gal_synth_iq_scint.restype = ctypes.c_int
     lib.gal_synth_run_scint.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, vp, ctypes.c_uint64, vp, vp]
     lib.gal_synth_run_scint.restype = ctypes.c_int
+    lib.gal_synth_steer_check.argtypes = [vp, i32, i32, i32]
+    lib.gal_synth_steer_check.restype = ctypes.c_int
+    lib.gal_synth_steer_make.argtypes = [ctypes.c_uint16, ctypes.c_uint32, ctypes.POINTER(_Steer)]
+    lib.gal_synth_steer_make.restype = ctypes.c_int
+    lib.gal_synth_array_phase.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_uint32)]
+    lib.gal_synth_array_phase.restype = ctypes.c_int
+    lib.gal_synth_iq_array.argtypes = [vp, vp, i32, vp, i32, i32, vp]
+    lib.gal_synth_iq_array.restype = ctypes.c_int
+    lib.gal_synth_run_array.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, ctypes.c_uint64, vp, vp]
+    lib.gal_synth_run_array.restype = ctypes.c_int
     lib.gal_synth_corr_out_bytes.argtypes = [ctypes.POINTER(_CorrReq)]
     lib.gal_synth_corr_out_bytes.restype = ctypes.c_size_t
     lib.gal_synth_correlate.argtypes = [vp, vp, i32, ctypes.c_size_t, ctypes.POINTER(_CorrReq), i32, vp]
@@ -759,6 +786,60 @@ def scint_rows(rows, n_epochs, n_slots):
         r = _scint_struct(row)
         out[:, int(slot)] = (r.seed, r.stream, r.node_len, r.a_q12, r.b_q12, 0)
     return out
+
+
+def _steer_table(rows, who):
+    """The weights [n_epochs, n_elem, n_parts] as a contiguous STEER_DTYPE array; an integer array [..., 2] of (w_re, w_im) is packed."""
+    a = np.asarray(rows)
+    if a.dtype != STEER_DTYPE:
+        if a.ndim != 4 or a.shape[3] != 2:
+            raise ValueError("%s: rows must be STEER_DTYPE [n_epochs, n_elem, n_parts] or integers [n_epochs, n_elem, n_parts, 2]" % who)
+        if a.size and (a.min() < -32768 or a.max() > 32767):
+            raise ValueError("%s: a weight does not fit an int16" % who)
+        t = np.zeros(a.shape[:3], dtype=STEER_DTYPE)
+        t["w_re"], t["w_im"] = a[..., 0], a[..., 1]
+        a = t
+    if a.ndim != 3:
+        raise ValueError("%s: rows must have shape [n_epochs, n_elem, n_parts]" % who)
+    return np.ascontiguousarray(a)
+
+
+def steer_check(rows, n_epochs=None, n_elem=None, n_parts=None):
+    """gal_synth_steer_check (no GPU needed): raises GalSynthError unless the weights rows [n_epochs, n_elem, n_parts] are admitted
+    (1 .. 8 elements, 1 .. 64 parts, no component of -32768).  rows None passes a null pointer with the three counts given."""
+    lib = load_library()
+    if rows is None:
+        rc = lib.gal_synth_steer_check(None, int(n_epochs), int(n_elem), int(n_parts))
+    else:
+        t = _steer_table(rows, "steer_check")
+        rc = lib.gal_synth_steer_check(t.ctypes.data if t.size else None, t.shape[0], t.shape[1], t.shape[2])
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+
+
+def steer_make(gain_q7, phase):
+    """gal_synth_steer_make (no GPU needed): the Q12 weight (w_re, w_im) of a part at the Q7 gain gain_q7 (0 .. 1023) turned by `phase`
+    (2^-32 cycles, rounded to the 1024-entry cosine table)."""
+    if not 0 <= int(gain_q7) <= 65535:
+        raise ValueError("steer_make: gain_q7 = %r does not fit a uint16" % (gain_q7,))
+    lib = load_library()
+    w = _Steer()
+    rc = lib.gal_synth_steer_make(int(gain_q7), int(phase) & 0xffffffff, ctypes.byref(w))
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+    return int(w.w_re), int(w.w_im)
+
+
+def array_phase(enu_m, az_rad, el_rad):
+    """gal_synth_array_phase (no GPU needed): the carrier phase, in 2^-32 cycles, of a plane wave from (az_rad from north over east,
+    el_rad) at an element enu_m = (east, north, up) metres from the array's reference point.  enu_m None passes a null pointer."""
+    lib = load_library()
+    v = None if enu_m is None else (ctypes.c_double * 3)(*[float(x) for x in enu_m])
+    ph = ctypes.c_uint32(0)
+    rc = lib.gal_synth_array_phase(v, float(az_rad), float(el_rad), ctypes.byref(ph))
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+    return int(ph.value)
 
 
 def _echo_table(echo_rows, n_epochs, who):
@@ -1125,6 +1206,48 @@ class SynthEngine:
                                                   sof.ctypes.data if sof.size else None, rows.ctypes.data if rows.size else None, rows.shape[1],
                                                   sc.ctypes.data if sc is not None else None, int(first_sample),
                                                   ctypes.c_void_p(int(iq_dev_ptr)), st.ctypes.data))
+        self.n_epochs = p.shape[0]
+        return st
+
+    def iq_array(self, part_ptrs, rows, out_ptrs):
+        """gal_synth_iq_array, enqueued on the handle's stream: the len(out_ptrs) (1 .. 8) element streams out of the parts at the device
+        addresses part_ptrs, each part read once, with the Q12 weights rows [n_epochs, n_elem, n_parts] (STEER_DTYPE, or integers
+        [..., 2]): out a = clamp((sum_k part k x rows[e, a, k] + 2048) >> 12), a complex product.  An output may meet neither a part nor
+        another output.  iq_saturated() is the fence and counts the clamped values."""
+        t = _steer_table(rows, "iq_array")
+        if t.shape[1] != len(out_ptrs) or t.shape[2] != len(part_ptrs):
+            raise ValueError("iq_array: rows must have shape [n_epochs, n_elem=%d, n_parts=%d]" % (len(out_ptrs), len(part_ptrs)))
+        ptrs = (ctypes.c_void_p * max(1, len(part_ptrs)))(*[int(p) for p in part_ptrs])
+        outs = (ctypes.c_void_p * max(1, len(out_ptrs)))(*[int(p) for p in out_ptrs])
+        self._check(self._lib.gal_synth_iq_array(self._h, ptrs, len(part_ptrs), t.ctypes.data if t.size else None, t.shape[0], len(out_ptrs), outs))
+
+    def run_array(self, params, gain_q7, phase, out_ptrs, scint_rows=None, first_sample=0, state_in=None):
+        """gal_synth_run_array: the batch as len(out_ptrs) (1 .. 8) element streams.  gain_q7 [n_epochs, n_slots] (0 .. 1023), phase
+        [n_epochs, n_elem, n_slots] in 2^-32 cycles (array_phase makes one).  Every active slot is a synthesis run of its own
+        (gain_runs() counts them); scint_rows as for run_scint.  The array pass is ENQUEUED when this returns (iq_saturated() is the
+        fence).  Returns state_out."""
+        p = self._params(params)
+        s = self._state(state_in)
+        g = np.asarray(gain_q7)
+        if g.shape != p.shape:
+            raise ValueError("run_array: gain_q7 must have shape [n_epochs, n_slots=%d]" % self.n_slots)
+        if g.size and (g.min() < 0 or g.max() > 65535):
+            raise ValueError("run_array: a gain does not fit a uint16")
+        g = np.ascontiguousarray(g, dtype=np.uint16)
+        ph = np.asarray(phase)
+        if ph.shape != (p.shape[0], len(out_ptrs), self.n_slots):
+            raise ValueError("run_array: phase must have shape [n_epochs, n_elem=%d, n_slots=%d]" % (len(out_ptrs), self.n_slots))
+        ph = np.ascontiguousarray(ph.astype(np.int64) & 0xffffffff, dtype=np.uint32)
+        sc = None
+        if scint_rows is not None:
+            sc = np.ascontiguousarray(scint_rows, dtype=SCINT_DTYPE)
+            if sc.shape != p.shape:
+                raise ValueError("run_array: scint_rows must have shape [n_epochs, n_slots=%d]" % self.n_slots)
+        outs = (ctypes.c_void_p * max(1, len(out_ptrs)))(*[int(q) for q in out_ptrs])
+        st = np.zeros(self.n_slots, dtype=CHAN_STATE_DTYPE)
+        self._check(self._lib.gal_synth_run_array(self._h, p.ctypes.data, p.shape[0], s.ctypes.data if s is not None else None, g.ctypes.data,
+                                                  ph.ctypes.data if ph.size else None, len(out_ptrs), sc.ctypes.data if sc is not None else None,
+                                                  int(first_sample), outs, st.ctypes.data))
         self.n_epochs = p.shape[0]
         return st
 

@@ -76,6 +76,11 @@ int32_t gal_scen_next(gal_scen_t *s, int32_t max_epochs, gal_chan_epoch_t *rows)
 int gal_scen_set_power(gal_scen_t *s, const double *pattern_db, const double *prn_offset_db);
 int gal_scen_set_path_loss(gal_scen_t *s, int32_t enable);
 int32_t gal_scen_next_gains(gal_scen_t *s, int32_t max_epochs, gal_chan_epoch_t *rows, uint16_t *gain_q7);
+/* gal_scen_next_gains (gain_q7 may be NULL: gal_scen_next) -- the same rows, the same progress -- that also hands out the direction of
+ * arrival the row's range computation has found: azel[(e * n_slots + s) * 2] = the azimuth in radians, from north over east, 0 .. 2 pi,
+ * azel[.. + 1] = the elevation in radians; idle slots get 0, 0.  What an antenna array needs (include/galsynth.h:
+ * gal_synth_array_phase, gal_synth_run_array).  GAL_E_INVAL for a null s, rows or azel. */
+int32_t gal_scen_next_azel(gal_scen_t *s, int32_t max_epochs, gal_chan_epoch_t *rows, uint16_t *gain_q7, double *azel);
 int gal_scen_close(gal_scen_t *s);
 /* (satellite, refresh) pairs so far at which a channel kept a stale ephemeris record (strict_eph == 0), and position
  * datagrams dropped because a coordinate was not finite or out of range. */

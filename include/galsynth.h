@@ -901,6 +901,67 @@ int gal_synth_run_scint(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t 
                         const uint16_t *gain_q7, const int32_t *slot_of_echo, const gal_iq_echo_t *echo_rows, int32_t n_echo,
                         const gal_iq_scint_t *scint_rows, uint64_t first_sample, int16_t *iq_dev, gal_chan_state_t *state_out);
 
+/*
+ * Antenna array (not in the reference): K phase-coherent output streams, one per antenna element, out of the
+ * P "parts" of gal_synth_run_gains -- in each of them every part carries the carrier phase its own direction of arrival gives it at
+ * that element.  A FIXED INTEGER FUNCTION of its inputs (tests/array_model.py states it in numpy).
+ *
+ * x_k[n] = complex int16 sample n of part k, as for gal_synth_iq_wsum; N = samples_per_epoch, e = n div N.  (w_re, w_im) = the weight
+ * row of (epoch e, element a, part k), Q12: 4096 = the part at unity, unrotated.  For element a:
+ *   AI = sum_k (x_k.I w_re - x_k.Q w_im)        AQ = sum_k (x_k.I w_im + x_k.Q w_re)
+ *   y_a.I = clamp((AI + 2048) >> 12, -32768, 32767)        likewise Q                    (arithmetic shift: round to nearest, ties up)
+ * A value the clamp changes counts once in the handle's saturation counter.  A and its rounding term fit an int32 where
+ * sum_k (|w_re| + |w_im|) <= 65535 for that (epoch, element): |A| + 2048 <= 32768 x 65535 + 2048 < 2^31 for ANY int16 input; otherwise
+ * the sum is formed in 64 bits and gives the same bits.  With w = (32 g, 0) for a Q7 gain g <= 1023 the output is
+ * clamp((sum_k g x_k + 64) >> 7), because floor((32 S + 2048) / 4096) = floor((S + 64) / 128): K = 1 with such weights is
+ * gal_synth_iq_wsum bit for bit.
+ */
+#define GAL_ARRAY_MAX_ELEM 8
+#define GAL_STEER_GAIN_MAX 1023 /* the largest Q7 gain gal_synth_steer_make turns into a weight: 32 x 1023 = 32736 */
+typedef struct gal_iq_steer {
+    int16_t w_re;  /* Q12, -32767 .. 32767 (-32768 is refused, so that a negated weight fits)                                    */
+    int16_t w_im;  /* likewise                                                                                                */
+} gal_iq_steer_t;  /* 4 bytes */
+/* GAL_OK if the weight rows[(e * n_elem + a) * n_parts + k] are admitted, else GAL_E_INVAL: a null pointer, n_epochs < 1, n_elem
+ * outside 1 .. GAL_ARRAY_MAX_ELEM, n_parts outside 1 .. GAL_ENGINE_MAX_CHAN, a component of -32768.  Host only, needs no GPU. */
+int gal_synth_steer_check(const gal_iq_steer_t *rows, int32_t n_epochs, int32_t n_elem, int32_t n_parts);
+/* The weight of a part at the Q7 gain g = gain_q7 turned by `phase` (2^-32 cycles, rounded -- not truncated -- to the 1024-entry
+ * table); host only, needs no GPU.  Integers only, C = gal_tables_cos1024():
+ *   i    = ((phase + 2^21) >> 22) & 1023
+ *   w_re = (g C[i] + 64) >> 7;  w_im = (g C[(i - 256) & 1023] + 64) >> 7                 (g e^(+j 2 pi i / 1024), Q12)
+ * g = 128, phase = 0 gives (4096, 0).  GAL_E_INVAL for a null `out` or g > 1023 (+18 dB over unity: the weight would leave int16). */
+int gal_synth_steer_make(uint16_t gain_q7, uint32_t phase, gal_iq_steer_t *out);
+/* The carrier phase, in 2^-32 cycles, that a plane wave from azimuth az_rad (from north over east, as the front-end's azel[0]) and
+ * elevation el_rad has at an element displaced by enu_m = (east, north, up) metres from the array's reference point, relative to
+ * that point; host only, needs no GPU.  In double, operation for operation:
+ *   u = (sin az cos el, cos az cos el, sin el)            (the unit vector towards the source)
+ *   cyc = (enu . u) / lambda, lambda = 299792458.0 / 1575420000.0;  *phase = llround((cyc - floor(cyc)) x 2^32) mod 2^32
+ * An element displaced towards the source receives the wavefront earlier: its phase advances.  GAL_E_INVAL for a null pointer or a
+ * value that is not finite. */
+int gal_synth_array_phase(const double enu_m[3], double az_rad, double el_rad, uint32_t *phase);
+/* Enqueue on the handle's stream: the n_elem (1 .. GAL_ARRAY_MAX_ELEM) element streams of the definition above, out of the n_parts
+ * (1 .. GAL_ENGINE_MAX_CHAN) streams parts_dev[k] -- DEVICE memory, n_epochs x samples_per_epoch complex int16 samples each -- with
+ * the weights rows[(e * n_elem + a) * n_parts + k] (HOST memory, copied before the call returns, as are both pointer arrays) into
+ * out_dev[a] (DEVICE, the same size each).  Every part is read once, whatever n_elem is.  The rules of gal_synth_iq_wsum: 16-byte
+ * alignment, GAL_E_STATE for a buffer of the batch in flight, gal_synth_iq_saturated is the fence and the counter; an output that
+ * meets any part OR any other output is refused (parts may overlap each other).  A handle holds one weight table: a call waits (on
+ * the host) for the kernel of the call before it.  GAL_E_INVAL for a null handle or pointer, a misaligned pointer, what
+ * gal_synth_steer_check refuses, an overlap; GAL_E_NOMEM if the table cannot be had. */
+int gal_synth_iq_array(gal_synth_t *h, const int16_t *const *parts_dev, int32_t n_parts, const gal_iq_steer_t *rows, int32_t n_epochs,
+                       int32_t n_elem, int16_t *const *out_dev);
+/* gal_synth_run_scint without echoes and with n_elem outputs: the batch of gal_synth_plan(params, n_epochs, state_in) as the n_elem
+ * element streams out_dev[a] (HOST array of DEVICE pointers, 16-byte aligned, n_epochs x samples_per_epoch x 4 bytes each).  gain_q7 is
+ * HOST [n_epochs][n_slots] as for gal_synth_run_gains, but at most 1023; phase is HOST [n_epochs][n_elem][n_slots], 2^-32 cycles
+ * (gal_synth_array_phase).  EVERY slot that is active in any epoch of the batch is a group (a synthesis run) of its own, so that its
+ * part is x_s itself; scintillation runs in place on the parts first if scint_rows is given (NULL: none); then gal_synth_iq_array is
+ * enqueued with the weight gal_synth_steer_make(gain_q7[e][s], phase[e][a][s]) for slot s, element a in epoch e, and (0, 0) where the
+ * slot is idle in e.  gal_synth_gain_runs counts the runs (an empty sky: one); state_out as for gal_synth_run_gains.  With n_elem = 1
+ * and all phases 0 the output equals gal_synth_run_scint's bit for bit (it costs more runs).  The refusals are those of
+ * gal_synth_run_scint and gal_synth_iq_array, and GAL_E_INVAL for a gain above 1023, with the slot and epoch in the text. */
+int gal_synth_run_array(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_epochs, const gal_chan_state_t *state_in,
+                        const uint16_t *gain_q7, const uint32_t *phase, int32_t n_elem, const gal_iq_scint_t *scint_rows,
+                        uint64_t first_sample, int16_t *const *out_dev, gal_chan_state_t *state_out);
+
 /* Signal tables as the engine uses them (for tests and for the oracle to share DATA, not code). */
 const uint32_t *gal_tables_e1b(void);   /* [50][128] */
 const uint32_t *gal_tables_e1c(void);   /* [50][128] */
