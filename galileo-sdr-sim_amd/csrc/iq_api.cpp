@@ -1266,6 +1266,19 @@ static int run_groups(const char *who, gal_synth_t *h, const gal_chan_epoch_t *p
     bool any_fade = false;
     for (size_t i = 0; scint_rows && i < (size_t)E * S; ++i)
         if (!scint_identity(scint_rows[i])) fades[i % S] = solo[i % S] = 1, any_fade = true;
+    // the end of the maximal run of epochs from e0 on in which slot s keeps one row: a job of gal_synth_iq_scint
+    const auto row_run_end = [&](int s, int e0) {
+        int e1 = e0 + 1;
+        while (e1 < E && !memcmp(&scint_rows[(size_t)e1 * S + s], &scint_rows[(size_t)e0 * S + s], sizeof(gal_iq_scint_t))) ++e1;
+        return e1;
+    };
+    // a job turns its part in place from the run's first sample on, and a pass starts on 16 bytes: refused here, before any run
+    const uint64_t spe = (uint64_t)h->cfg.samples_per_epoch;
+    for (int s = 0; s < S && any_fade; ++s)
+        for (int e0 = 0; fades[s] && e0 < E; e0 = row_run_end(s, e0))
+            if (!scint_identity(scint_rows[(size_t)e0 * S + s]) && ((e0 * spe) & 3))
+                return fail(GAL_E_INVAL, "%s: the row of slot %d changes at epoch %d, %llu samples into the batch (a multiple of 4 only)", who, s, e0,
+                            (unsigned long long)(e0 * spe));
     // ... and, for an array, every slot that is active in any epoch: its part is x_s itself, which the elements' weights turn
     for (size_t i = 0; arr && i < (size_t)E * S; ++i)
         if (params[i].prn > 0) solo[i % S] = 1;
@@ -1294,7 +1307,9 @@ static int run_groups(const char *who, gal_synth_t *h, const gal_chan_epoch_t *p
     bool unity = n_parts == 1 && n_echo == 0 && !any_fade && !arr;  // one part at gain 128 wherever it is not zero: y = x, the run goes straight into iq_dev
     if (!groups.empty())
         for (int e = 0; e < E && unity; ++e) unity = groups[0].g[e] < 0 || groups[0].g[e] == GAL_GAIN_UNITY;
-    const size_t bytes = (size_t)E * (size_t)h->cfg.samples_per_epoch * 4;
+    // a part's bytes, rounded up to the 16 that every pass asks of a buffer's start: the parts lie one behind the other in own_parts, and
+    // a batch whose sample count is no multiple of 4 would put every second one on an address that gal_synth_execute refuses
+    const size_t bytes = ((size_t)E * (size_t)h->cfg.samples_per_epoch * 4 + 15) & ~(size_t)15;
     // the weighted sum of the call before may still read the scratch buffers: wait for it here, whatever stream the handle is on now
     // (on one stream the runs below would order behind it by themselves)
     if (h->gain.sync.pending || h->mp.sync.pending || h->scint.sync.pending || h->array.sync.pending) {
@@ -1338,17 +1353,13 @@ static int run_groups(const char *who, gal_synth_t *h, const gal_chan_epoch_t *p
     }
     if (any_fade) {
         // one job per slot and maximal run of epochs with an equal row, in place on the slot's part; all jobs in one call (of 64)
-        const uint64_t spe = (uint64_t)h->cfg.samples_per_epoch;
         std::vector<gal_scint_job_t> jobs;
         for (int s = 0; s < S; ++s) {
             if (!fades[s]) continue;
             for (int e0 = 0, e1; e0 < E; e0 = e1) {
                 const gal_iq_scint_t &row = scint_rows[(size_t)e0 * S + s];
-                for (e1 = e0 + 1; e1 < E && !memcmp(&scint_rows[(size_t)e1 * S + s], &row, sizeof(row)); ++e1) {}
+                e1 = row_run_end(s, e0);
                 if (scint_identity(row)) continue;
-                if ((e0 * spe) & 3)
-                    return fail(GAL_E_INVAL, "%s: the row of slot %d changes at epoch %d, %llu samples into the batch (a multiple of 4 only)", who, s, e0,
-                                (unsigned long long)(e0 * spe));
                 gal_scint_job_t j;
                 memset(&j, 0, sizeof(j));
                 j.out_dev = (int16_t *)((char *)h->own_parts + bytes * (size_t)group_of[s]) + 2 * e0 * spe;

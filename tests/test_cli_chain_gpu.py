@@ -1,8 +1,9 @@
 """galileo-sdr-sim's run loop on the MI355X, against recorded bytes: every combination of tests/golden/cli_chain_md5.json -- each
-synthesis path (plain, run_gains, run_mpath) and each stage of the output chain with and without the passes in front of it -- runs at
--B 1 (the two output slots and the three row buffers wrap) and at -B 3 (the run ends on a short batch); the two IQ files are equal to
-each other and to the recorded md5, and so are the --monitor and --agc-log files at the same -B.  tools/cli_golden.py chain made the
-file from the binary whose behaviour is kept; nothing expected is computed here."""
+synthesis path (plain, run_gains, run_mpath, run_scint with echoes, run_array with scintillation) and each stage of the output chain
+with and without the passes in front of it -- runs at -B 1 (the two output slots and the three row buffers wrap) and at -B 3 (the
+run ends on a short batch); the two IQ files are equal to each other and to the recorded md5, and so are the --monitor and --agc-log
+files at the same -B.  tools/cli_golden.py chain made the file from the binary whose behaviour is kept; nothing expected is computed
+here."""
 import json
 import os
 import sys

@@ -1,7 +1,7 @@
 """galileo-sdr-sim --array: the refused combinations and files with their messages (before any device work) and, on the MI355X, the
 element files -- the plain run's bytes for elements at the reference point, one satellite's rotation against the model with the
-indices of --array-log and against the geometry, independent noise per element, the same bytes for two batch lengths, and a jammer's
-direction of arrival."""
+indices of --array-log and against the geometry, the full sky with --power-model and --scint against the composed model of every
+element, independent noise per element, the same bytes for two batch lengths, and a jammer's direction of arrival."""
 import hashlib
 import math
 import os
@@ -164,6 +164,56 @@ def test_one_satellite_is_turned_by_its_direction_of_arrival(pkg, sky, tmp_path)
     geo = 360.0 * EAST * math.sin(math.radians(az)) * math.cos(math.radians(el)) / array_model.LAMBDA_E1
     print("PRN %d from az %.2f el %.2f: measured %.4f deg, geometric %.4f deg" % (prn, az, el, got, geo))
     assert abs((got - geo + 180.0) % 360.0 - 180.0) <= 0.2
+
+
+@pytest.mark.gpu
+def test_full_sky_with_power_model_and_scint_is_the_model_of_every_element(pkg, sky, tmp_path):
+    """Three elements, every satellite in view at its path-loss gain, two of them fading: every element file is
+    compose_model.array_model_run over the engine's own runs of every slot alone, with the front-end's gains, the phases index << 22 of
+    --array-log and the scintillation table the test builds from the file's lines -- a weight per satellite, epoch and element.  The
+    same bytes for -B 4 and -B 7; the log holds one line per epoch and PRN in view."""
+    import compose_model
+    import gain_model
+
+    K = 3
+    arr = tmp_path / "a.txt"
+    arr.write_text("0,0,0\n%g,0,0\n0,0.12,0.05\n" % EAST)
+    in_view = [int(p) for p in sky["prn"][0] if p > 0]
+    spec = [(in_view[1], 0.8, 0.02), (in_view[4], 0.5, 0.05)]
+    sc_file = tmp_path / "s.txt"
+    sc_file.write_text("".join("%d,%g,%g\n" % s for s in spec))
+    log = tmp_path / "log.csv"
+    opts = ["--array", str(arr), "--power-model", "--scint", str(sc_file), "--scint-seed", "4"]
+    _ok(["-o", str(tmp_path / "el.ishort"), "-B", "4", "--array-log", str(log)] + opts)
+    _ok(["-o", str(tmp_path / "e7.ishort"), "-B", "7"] + opts)
+    lines = [ln for ln in open(str(log)) if ln.strip()]
+    entries = _log(log)
+    assert len(lines) == len(entries) == int((sky["prn"] > 0).sum())
+    assert set(entries) == {(e, int(p)) for e in range(EPOCHS) for p in sky["prn"][e] if p > 0}
+    sc = pkg.Scenario(NAV, llh=(-6, 51, 100), start=START, duration_s=2, iono_enable=False)
+    sc.set_power(None, None, path_loss=True)
+    rows, gains = sc.next_gains(sc.total_epochs)
+    assert np.array_equal(rows["prn"], sky["prn"]) and len(np.unique(gains[rows["prn"] > 0])) > 6 and gains.max() <= 1023
+    n = 1 + max(int(s) for s in np.argwhere(rows["prn"] > 0)[:, 1])
+    phase = np.zeros((EPOCHS, K, rows.shape[1]), dtype=np.int64)
+    for e in range(EPOCHS):
+        for s in range(n):
+            if rows["prn"][e, s] > 0:
+                idx = entries[(e, int(rows["prn"][e, s]))][2]
+                assert len(idx) == K and idx[0] == 0
+                phase[e, :, s] = np.asarray(idx, dtype=np.int64) << 22
+    assert len(np.unique(phase[:, 1:, :n])) > len(in_view)  # (two seconds move no satellite far: about one index per satellite and element)
+    table = compose_model.cli_scint_rows(pkg, rows, spec, 4, 0, FS)
+    with pkg.SynthEngine(sample_rate=FS, samples_per_epoch=N, n_slots=rows.shape[1], device=0) as eng:
+        alone = np.stack([np.ascontiguousarray(eng.run_host(gain_model.slot_alone(rows, s))[0]).view(np.int16).ravel() for s in range(n)])
+    want, _ = compose_model.array_model_run(alone, rows, gains, phase, table, 0, N, pkg.tables()["cos1024"])
+    for k in range(K):
+        got = _iq(tmp_path / ("el.a%d.ishort" % k))
+        bad = np.flatnonzero(got != want[k])
+        assert got.size == want[k].size and bad.size == 0, "element %d: %d values differ, the first at %d (epoch %d)" % (
+            k, bad.size, bad[0], bad[0] // (2 * N))
+        assert _md5(tmp_path / ("e7.a%d.ishort" % k)) == _md5(tmp_path / ("el.a%d.ishort" % k)), k
+    assert _md5(tmp_path / "el.a0.ishort") != _md5(tmp_path / "el.a1.ishort") != _md5(tmp_path / "el.a2.ishort")
 
 
 @pytest.mark.gpu

@@ -181,8 +181,10 @@ NAV = os.path.join(GOLDEN, "20feb2022.rnx")
 CHAIN_SCEN = ["-l", "-6,51,100", "-t", "2022/02/20,12:00:00", "-d", "0.5", "-U", "1", "-b", "1", "-I", "1", "-P", "0"]
 CHAIN_BATCHES = (1, 3)
 OSC = ["--lo-offset", "1500,2", "--phase-noise", "1e-21"]
-CHAIN_FILES = {"mp.txt": "# PRNs 5 and 9 are in view, 17 is not\n5,300,-6,90\n5,650,-10,0,0.5\n9,200,-3,45\n17,300,-6,0\n"}
-# name, format, options; "monitor" / "agc_log" ask for the side files
+CHAIN_FILES = {"mp.txt": "# PRNs 5 and 9 are in view, 17 is not\n5,300,-6,90\n5,650,-10,0,0.5\n9,200,-3,45\n17,300,-6,0\n",
+               "sc.txt": "# prn,s4,tau0_s: 5 has echoes in mp.txt\n5,0.8,0.02\n9,0.5,0.05\n17,0.9,0.02\n",
+               "arr.txt": "0,0,0\n0.095,0,0\n0,0.12,0.05\n"}
+# name, format, options; "monitor" / "agc_log" ask for the side files; "elements": --array's files out.a<k>.<fmt>, hashed one behind the other
 CHAIN_CASES = [
     {"name": "plain_ishort", "fmt": "ishort", "argv": []},
     {"name": "ibit_alone", "fmt": "ibit", "argv": []},
@@ -195,12 +197,17 @@ CHAIN_CASES = [
     {"name": "osr_cn0_osc_mpath_power_ibyte", "fmt": "ibyte", "argv": ["--oversample", "2", "--cn0", "45", "--multipath", "mp.txt", "--power-model"] + OSC},
     {"name": "power_prn_ishort", "fmt": "ishort", "argv": ["--power-model", "--prn-power", "5:-6,9:3"]},
     {"name": "mpath_alone_monitor_ishort", "fmt": "ishort", "argv": ["--multipath", "mp.txt", "--monitor-every", "2"], "monitor": True},
+    {"name": "scint_mpath_power_ishort", "fmt": "ishort", "argv": ["--scint", "sc.txt", "--multipath", "mp.txt", "--power-model"]},
+    {"name": "array_scint_cn0_ibyte", "fmt": "ibyte", "argv": ["--array", "arr.txt", "--scint", "sc.txt", "--cn0", "45"], "elements": 3},
 ]
 
 
-def _md5(path):
-    with open(path, "rb") as fh:
-        return hashlib.md5(fh.read()).hexdigest()
+def _md5(*paths):
+    h = hashlib.md5()
+    for path in paths:
+        with open(path, "rb") as fh:
+            h.update(fh.read())
+    return h.hexdigest()
 
 
 def run_chain_case(exe, case, batch, files):
@@ -218,7 +225,8 @@ def run_chain_case(exe, case, batch, files):
         r = subprocess.run([exe] + argv, cwd=d, capture_output=True, text=True, timeout=120, stdin=subprocess.DEVNULL)
         if r.returncode != 0:
             raise RuntimeError("%s -B %d: exit %d\n%s" % (case["name"], batch, r.returncode, r.stderr[-2000:]))
-        got = {"iq": _md5(os.path.join(d, out)), "iq_bytes": os.path.getsize(os.path.join(d, out))}
+        outs = [os.path.join(d, "out.a%d.%s" % (k, case["fmt"])) for k in range(case["elements"])] if case.get("elements") else [os.path.join(d, out)]
+        got = {"iq": _md5(*outs), "iq_bytes": sum(os.path.getsize(o) for o in outs)}
         if case.get("monitor"):
             got["monitor"] = _md5(os.path.join(d, "mon.csv"))
             got["monitor_lines"] = len(open(os.path.join(d, "mon.csv")).read().splitlines())
