@@ -13,6 +13,7 @@ import pytest
 import firdec_model
 import interf_model
 import noise_model
+from oracle_binding import oracle_run
 
 pytestmark = pytest.mark.gpu
 
@@ -54,12 +55,15 @@ def _printed_taps(stderr):
 
 @pytest.fixture(scope="module")
 def wide(pkg):
-    """The engine's stream of the scenario at 10.4 MS/s, computed once and left unchanged."""
+    """The engine's stream of the scenario at 10.4 MS/s, computed once and left unchanged.  It is the oracle's, int16 by int16: the
+    mirror chain below rests on the oracle, not on the engine."""
     rows = pkg.Scenario(NAV, llh=(-6, 51, 100), start=START, duration_s=1, iono_enable=False).all()
     assert rows.shape[0] == EPOCHS
     with pkg.SynthEngine(sample_rate=M * FS, samples_per_epoch=M * 260000, n_slots=rows.shape[1], device=0) as eng:
         iq, _, _ = eng.run_host(rows)
     assert iq.size == EPOCHS * M * 520000
+    ref, _ = oracle_run(rows, M * 260000, M * FS)
+    assert np.array_equal(iq, ref)
     iq.setflags(write=False)
     return iq
 

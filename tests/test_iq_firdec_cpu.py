@@ -57,6 +57,26 @@ def test_model_is_every_mth_sample_of_the_merged_filter(M, T):
             assert np.array_equal(np.concatenate([a, b]), got) and sa + sb == sat
 
 
+@pytest.mark.parametrize("M", DECIMS)
+def test_one_unity_tap_is_an_exact_pick_of_every_mth_sample(M):
+    """A decimator of the single tap 16384: (16384 x + 8192) >> 14 = x for every int16, so the output is the input at the kept phase --
+    the samples whose GLOBAL index is a multiple of M: x[0::M] for a stream that starts at 0 -- and nothing saturates, -32768 and
+    32767 included.  The CLI's `--oversample M --fir one_tap.txt` rests on this (tests/test_oversample_cli.py)."""
+    rng = np.random.default_rng(40 + M)
+    n = 50 * M + 7
+    x = rng.integers(-32768, 32768, size=2 * n, dtype=np.int16)
+    x[:4] = [-32768, 32767, 32767, -32768]
+    x[2 * M: 2 * M + 2] = [32767, -32768]
+    xs = x.reshape(-1, 2)
+    for P in (0, 1, M - 1, M, 260000, 2 ** 40 + 3):
+        got, sat = firdec_model.firdec(x, [16384], M, first_sample=P)
+        assert np.array_equal(got.reshape(-1, 2), xs[(-P) % M::M]) and sat == 0, (M, P)
+    # a stream from 0 cut anywhere keeps x[0::M]
+    a, sa = firdec_model.firdec(x[: 2 * (M + 1)], [16384], M)
+    b, sb = firdec_model.firdec(x[2 * (M + 1):], [16384], M, first_sample=M + 1)
+    assert np.array_equal(np.concatenate([a, b]).reshape(-1, 2), xs[::M]) and sa + sb == 0
+
+
 def test_out_samples_against_a_brute_force_count(pkg):
     for M in DECIMS:
         for P in (0, 1, M - 1, M, 2 ** 40 + 3):
