@@ -132,6 +132,7 @@ constexpr int kActRow = 32;         // bytes per epoch in a channel group's acti
 constexpr int kGroupMaxChan = 24;   // channels one k_synth_g launch takes (BOC(1,1); its wide instances: synth_group.hip)
 constexpr int kGroupChunk = 1024;   // k_synth_g: samples per wave iteration = chunk length of its batches (synth_group.hip: SG_CHUNK)
 constexpr int kGroupSyms = 64;      // ... symbol masks per channel and epoch (SG_SYMS)
+constexpr double kGroupLinCycles = 2.0;  // ... carrier cycles its multi-cycle table leaves a chunk plus a group room for (SG_LIN_CYCLES)
 constexpr int kGroupListMin = 1 << 16;  // ... least capacity of the undecided-group list (a 120 s batch lists ~2000 of 19.5 M groups);
                                         // a plan's list holds 0.5 % of its groups + this
 constexpr int kVerifyRotation = 8;  // GAL_CFG_VERIFY_SAMPLED: k_verify re-walks, of both chains, every eighth leg position per batch (default:
@@ -641,7 +642,7 @@ static int plan_impl(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_e
     //             a carrier step of 0 or in [2^-40, 120 / (16 x 511)] cycles per sample -- at most 120 table entries per group (the
     //             table's extension behind a wrap), and a phase that either moves or stands still for good: one that creeps past an
     //             index boundary would have thousands of groups in a row listed for the exact replay
-    std::vector<uint8_t> rec_mode((size_t)E * S, 0), rec_gm((size_t)E * S, 0), rec_gb((size_t)E * S, 0);
+    std::vector<uint8_t> rec_mode((size_t)E * S, 0), rec_gm((size_t)E * S, 0), rec_gb((size_t)E * S, 0), rec_gl((size_t)E * S, 0);
     double cs2_max = 0.0;  // largest code step of the batch, half chips per sample
     if ((int)h->rw_s0.size() != S) { h->rw_s0.assign(S, 0.0); h->rw_g0.assign(S, 0.0); h->rw_e0.assign(S, 0.0); h->rw_rad.assign(S, 0.0); }
     int n_restart = 0;  // records with GAL_CH_RESTART: their page_init goes up in a compact table
@@ -729,6 +730,9 @@ static int plan_impl(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_e
                 if (carr_ok && (bins_ok || !cboc)) {
                     rec_gm[i] = (uint8_t)mode;
                     rec_gb[i] = bins_ok ? 1 : 0;
+                    // the linear carrier start: a chunk and its last group cross at most two carrier cycles (synth_group.hip:
+                    // SG_LIN_CYCLES; 5.0 kHz at 2.6 MS/s) -- its table ends there
+                    rec_gl[i] = (double)(kGroupChunk + 16) * ad <= kGroupLinCycles ? 1 : 0;
                 }
             }
             act_all[(size_t)e * S + n] = (uint8_t)s;
@@ -759,6 +763,13 @@ static int plan_impl(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_e
     for (size_t i = 0; i < (size_t)E * S && !g_search; ++i) g_search = rec_gm[i] == g_mode && !rec_gb[i];
 #ifdef GAL_TEST_HOOKS
     if (getenv("GAL_G_SEARCH") && !cboc) g_search = true;  // (the soak runs every rate through the bisection instances this way)
+#endif
+    // ... and one whose carrier crosses more than two cycles per chunk sends it to the instances with the legacy carrier start
+    bool g_lin = true;
+    for (size_t i = 0; i < (size_t)E * S && g_lin; ++i) g_lin = rec_gm[i] != g_mode || rec_gl[i];
+#ifdef GAL_TEST_HOOKS
+    // GAL_G_LINEAR=0: the legacy start for every batch (A/B runs, tests); the linear one is never forced on a batch outside its range
+    if (const char *env = getenv("GAL_G_LINEAR")) g_lin = g_lin && atoi(env) != 0;
 #endif
     // epochs in which some record is not fit for k_synth_g in that form: the accumulating exact-replay launch behind it costs about
     // what a whole k_synth_g launch costs PER EPOCH IT HAS WORK IN (its blocks run the slow body at this chunk length: measured 1.0 ms
@@ -1017,6 +1028,7 @@ static int plan_impl(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_e
     P.ctr = (int *)(base + o_ctr);
     P.fam = fam_g ? 1 : 0;
     P.rw_search = (fam_g && g_search) ? 1 : 0;
+    P.g_lin = (fam_g && !g_search && !cboc && g_lin) ? 1 : 0;  // (the wide, bisection and CBOC instances keep the legacy start)
     P.gflist = (uint32_t *)(base + o_gflist);
     P.gflist_cap = (int)g_cap;
 #ifdef GAL_TEST_HOOKS
@@ -1122,6 +1134,7 @@ const void *gal_hooks_plan_host_array(const char *name)
     if (!strcmp(name, "family")) return (const void *)(uintptr_t)(1 + P.fam);
     if (!strcmp(name, "groups")) return (const void *)(uintptr_t)(1 + g->n_groups);
     if (!strcmp(name, "search")) return (const void *)(uintptr_t)(1 + P.rw_search);
+    if (!strcmp(name, "linear")) return (const void *)(uintptr_t)(1 + P.g_lin);
     if (!strcmp(name, "form")) return (const void *)(uintptr_t)(1 + P.rw);
     return nullptr;
 }

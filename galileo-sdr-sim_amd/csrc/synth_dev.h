@@ -100,6 +100,8 @@ struct DevPlan {
     uint32_t *gflist;     // k_synth_g -> k_repair_g: the undecided groups, (epoch in range * nchunks + chunk) * 64 + group
     int gflist_cap;
     const uint32_t *str;  // [50][512] half-chip streams: bit 2h = E1B^E1C chip, bit 2h+1 = E1C chip ^ (h & 1)
+    int g_lin;            // k_synth_g: 1 = every carrier of the batch crosses at most two cycles per chunk: the BOC(1,1) bin-table instances
+                          // for up to 12 channels start a group's carrier with one fma on a multi-cycle table (synth_group.hip: SG_LIN_CYCLES)
 };
 
 // by-value geometry of the hot kernel (everything else it reaches through a device copy of DevPlan, so

@@ -16,7 +16,11 @@
 // the fixed-point DDA t = 2^20 + 512 + 2^-26 + 511 p advanced by t += 511 |d| (a double in [2^20, 2^21) is a fixed-point
 // number with 32 fraction bits: the high word is the table address, the low word the fraction of 511 p; a sample whose
 // fraction word is below 2^7, i.e. 511 p within 2^-26 of an integer, is UNDECIDED; the error of t against the sequential
-// phase is below 18 x 2^-33 + 2^-34 < 2^-28).  The BOC(1,1) bin-table instances give the chip phase the same form (SG_FIX below): the
+// phase is below 18 x 2^-33 + 2^-34 < 2^-28.  With the linear start, SG_LIN_CYCLES below, t = fma(16 g, 511 |d|, T_c) and the terms
+// are: the rounding of T_c and of the group's fma, 2^-33 each; the relative 2^-53 of 511 |d| over at most 1008 samples, below 2^-40;
+// the real-valued phase against the sequential one, 1040 x 2^-53 x 511 ~ 2^-34; 15 DDA additions of 2^-33 each -- one rounding of
+// 2^-33 more than the reduced start has, and still < 2^-28 against a band of 2^-26).
+// The BOC(1,1) bin-table instances give the chip phase the same form (SG_FIX below): the
 // loader lane stores y_c + 2^20 (y_c < 8184 + 1008, so the biased phase stays below 2^20 + 9192, inside [2^20, 2^21)), the group's
 // fma rounds to the same 32 fraction bits -- two more roundings of at most 2^-33 each,
 //     Y_g = fma(16 g, s, y_c + 2^20)               |frac word of Y_g - sequential y| <= 2^-31 + 2^-32
@@ -46,17 +50,21 @@
 using namespace galnco;
 using namespace galdev;
 
-// Compiled as three translation units, side by side under `make -j` (Makefile: -DGAL_GTU=0..2), because its instantiations take five
-// minutes in one go: 0 = the instances for up to 12 channels (BOC(1,1) and CBOC), k_repair_g and the launchers; 1 = the wide
-// instances (13-24 channels); 2 = the bisection instances (crowded pattern thresholds).  Without GAL_GTU everything is one unit.
+// Compiled as four translation units, side by side under `make -j` (Makefile: -DGAL_GTU=0..3), because its instantiations take five
+// minutes in one go: 0 = the instances for up to 12 channels (BOC(1,1) and CBOC) with the legacy carrier start, k_repair_g and the
+// launchers; 1 = the wide instances (13-24 channels); 2 = the bisection instances (crowded pattern thresholds); 3 = the BOC(1,1)
+// bin-table instances for up to 12 channels with the LINEAR carrier start (SG_LIN_CYCLES below: the ones an ordinary batch runs).  Without
+// GAL_GTU everything is one unit.
 #if !defined(GAL_GTU)
 #define GAL_GTU_MAIN 1
 #define GAL_GTU_WIDE 1
 #define GAL_GTU_SEARCH 1
+#define GAL_GTU_LIN 1
 #else
 #define GAL_GTU_MAIN (GAL_GTU == 0)
 #define GAL_GTU_WIDE (GAL_GTU == 1)
 #define GAL_GTU_SEARCH (GAL_GTU == 2)
+#define GAL_GTU_LIN (GAL_GTU == 3)
 #endif
 
 #ifndef SG_THREADS
@@ -72,6 +80,16 @@ using namespace galdev;
                           // starts below the code wrap and advances by < 1008 half chips, so no window index ever wraps
 #define SG_MPOS 17      // sign-mask table: positions of the code wrap relative to a window (0: behind it .. 16: in front of it)
 #define SG_LUT_N 1152   // entries per carrier table: 512 (mirrored phase still negative) + 511 + 129 (behind a wrap inside a group)
+// The LINEAR carrier start (template parameter LIN; the BOC(1,1) bin-table instances for up to 12 channels): the table spans every
+// cycle a chunk can cross, so the DDA word of a group needs no reduction mod 1 -- t = fma(16 g, 511 |d|, T_c), T_c = fma(511, p_c,
+// SG_BIAS) stored once per (wave, chunk, channel) by the loader lane.  The table is periodic in the index domain (the phase wraps at
+// 1, so 511 p wraps at 511, exactly): entry i >= 512 holds LUT[(i - 512) mod 511].  p_c in (-1, 1) and a chunk's last group ends
+// 1023 samples behind its first, so with (1024 + 16) |d| <= SG_LIN_CYCLES = 2 the index stays below 512 + 511 x 3 = 2045 (host gate,
+// synth_api.cpp: a batch with a faster carrier runs the legacy instances).  Three FP64 instructions per channel and group less; the
+// two tables cost 7 KB of LDS more, the sign-mask address moves into the record (SgRecLin) and gives 1.5 KB back: the 12-channel
+// instance has 77144 bytes (legacy start: 71512), two blocks of 512 threads per CU still fit the 160 KB.
+#define SG_LUT_LIN_N 2048
+#define SG_LIN_CYCLES 2.0
 #define SG_AMB 128u
 #define SG_BIAS (1049088.0 + 1.4901161193847656250e-08)  // 2^20 + 512 + 2^-26
 #define SG_YBIAS 1048576.0   // 2^20: the bias of the fixed-point chip phase ...
@@ -94,6 +112,19 @@ struct SgRec {
     double s;    // code step in half chips per sample, 2 f_code delt
     double dabs; // |f_carr delt|
 };
+// ... and with the linear carrier start: the DDA word of the chunk's first sample in place of the phase (the step 511 |d| is in
+// s_c511 already), and in the room of the step the sign-mask address of s_sya, so that a group start is two 16-byte reads.
+// The address is biased: a group clamps its half-chip word ic0 itself, med3(ic0, SG_POS_LO, SG_POS_LO + 16), instead of
+// ic0 - SG_POS_LO against 0 and 16 -- the same bytes read, one subtraction less.  v_med3_i32 takes ONE scalar operand on gfx9 (the
+// constant bus), so the upper bound travels with the address: it arrives in a vector register at no instruction's cost.
+struct SgRecLin {
+    double yc;    // as SgRec (+ 2^20: the instances are SG_FIX)
+    double s;
+    double Tc;    // fma(511, pm, SG_BIAS)
+    uint32_t sa;  // LDS byte address of the sign mask of the chunk's first symbol - 4 SG_POS_LO (mod 2^32)
+    int hib;      // SG_POS_LO + 16
+};
+#define SG_POS_LO ((int)(SG_YEXP + (8184u - 16u)))  // the high word of a biased phase whose window ends at the code wrap
 typedef uint32_t sg_u4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(3))) sg_u4 *sg_lds_u4;
 typedef const __attribute__((address_space(3))) int *sg_lds_int;
@@ -125,8 +156,8 @@ __device__ __forceinline__ double sg_f64(const uint32_t lo, const uint32_t hi) {
 // denominator (4.092, 8.184, 16.368 MS/s: two, four, eight samples per half chip; 2.5, 2.728 ...) have thresholds that coincide or lie
 // 1e-6 apart (the Doppler's share of the step) and used to send the whole batch to the exact-replay kernel.  The fraction is known to
 // 2^-31, the undecided band stays 2^-22 around every threshold: a few groups in 10^5 more are listed.
-template <int J0, int CNT, int MODE, int SIG, int BINS, int BPITCH, bool SEARCH>
-__device__ __forceinline__ void sg_part(int (&o)[16], uint32_t &amb, uint64_t &undec, const double g16, const SgRec *rec, const uint32_t *sya,
+template <int J0, int CNT, int MODE, int SIG, int BINS, int BPITCH, bool SEARCH, bool LIN, typename REC>
+__device__ __forceinline__ void sg_part(int (&o)[16], uint32_t &amb, uint64_t &undec, const double g16, const REC *rec, const uint32_t *sya,
                                         const double *s_c511, const uint32_t *s_lutd,
                                         const uint32_t *s_str, const uint2 *s_bin, const uint4 *s_pat, const uint2 *s_bin6,
                                         const uint32_t *s_pat6, const float *s_thr, const int nact)
@@ -159,8 +190,9 @@ __device__ __forceinline__ void sg_part(int (&o)[16], uint32_t &amb, uint64_t &u
         for (int q = 0; q < CNT; ++q) {
             const int j = J0 + q;
             const sg_u4 r0 = ((sg_lds_u4)(uintptr_t)(rec + j))[0], r1 = ((sg_lds_u4)(uintptr_t)(rec + j))[1];
-            const uint32_t sa0 = *(sg_lds_u32)(uintptr_t)(sya + j);
-            const double A = __builtin_fma(g16, sg_f64(r1.x, r1.y), sg_f64(r0.x, r0.y));
+            // (linear start: r0 = (yc, s), r1 = (Tc, biased mask address, upper bound of the clamp))
+            const uint32_t sa0 = LIN ? r1.z : *(sg_lds_u32)(uintptr_t)(sya + j);
+            const double A = LIN ? __builtin_fma(g16, sg_f64(r0.z, r0.w), sg_f64(r0.x, r0.y)) : __builtin_fma(g16, sg_f64(r1.x, r1.y), sg_f64(r0.x, r0.y));
             if constexpr (SG_FIX(SIG, SEARCH)) {
                 // the biased phase: high word = 0x41300000 + half-chip index, low word = the fraction in units of 2^-32
                 ic0[q] = (int)(uint32_t)(d2u(A) >> 32);
@@ -188,9 +220,11 @@ __device__ __forceinline__ void sg_part(int (&o)[16], uint32_t &amb, uint64_t &u
             // up to the code wrap, its successor behind it -- one table row per pair of sign pairs, one entry per position of
             // the wrap relative to the window
             int pos;
-            asm("v_med3_i32 %0, %1, 0, 16" : "=v"(pos) : "v"(ic0[q] - (8184 - 16) - (SG_FIX(SIG, SEARCH) ? (int)SG_YEXP : 0)));
+            if constexpr (LIN) asm("v_med3_i32 %0, %1, %2, %3" : "=v"(pos) : "v"(ic0[q]), "s"(SG_POS_LO), "v"((int)r1.w));
+            else asm("v_med3_i32 %0, %1, 0, 16" : "=v"(pos) : "v"(ic0[q] - (8184 - 16) - (SG_FIX(SIG, SEARCH) ? (int)SG_YEXP : 0)));
             mask[q] = *(sg_lds_u32)(uintptr_t)(sa0 + ((uint32_t)pos << 2));
-            praw[q] = __builtin_fma(g16, sg_f64(r1.z, r1.w), sg_f64(r0.z, r0.w));
+            if constexpr (LIN) praw[q] = sg_f64(r1.x, r1.y);  // T_c
+            else praw[q] = __builtin_fma(g16, sg_f64(r1.z, r1.w), sg_f64(r0.z, r0.w));
         }
         // ---- phase B: threshold compare, pattern masks in flight; the carrier's DDA word meanwhile
         uint4 M[CNT];
@@ -242,8 +276,12 @@ __device__ __forceinline__ void sg_part(int (&o)[16], uint32_t &amb, uint64_t &u
             // thresholds of the first and the last bin, because sample 0's own half chip hangs on the rounding history there
             undec |= __builtin_amdgcn_ballot_w64(!(__builtin_fabsf(f[q] - thr) >= RW_DELTA));
             }
+            if constexpr (LIN) {
+                t[q] = __builtin_fma(g16, c511[q], praw[q]);  // unreduced: the table goes on behind the cycle's end
+            } else {
             const double pg = praw[q] - __builtin_trunc(praw[q]);  // (a mirrored phase that is still negative stays negative)
             t[q] = __builtin_fma(511.0, pg, SG_BIAS);
+            }
         }
         // ---- phase C: window (signs applied), spread
 #pragma unroll
@@ -366,7 +404,8 @@ __device__ __forceinline__ void sg_part(int (&o)[16], uint32_t &amb, uint64_t &u
 }
 
 // ACC: add onto samples already in `iq` (second and later channel groups when more than 12 channels are active)
-template <int NCH, bool ACC, int MODE, int SIG = 0, bool SEARCH = false>
+// LIN: the linear carrier start (SG_LUT_LIN_N above)
+template <int NCH, bool ACC, int MODE, int SIG = 0, bool SEARCH = false, bool LIN = false>
 __global__ __launch_bounds__(SG_THREADS) __attribute__((amdgpu_waves_per_eu(SG_WAVES_PER_EU)))
 void k_synth_g(const DevPlan *__restrict__ Pd, SynGeom G, const uint8_t *__restrict__ act_all, const int *__restrict__ nact_all,
                uint32_t *__restrict__ iq, uint32_t *__restrict__ flist, const int flist_cap)
@@ -375,12 +414,15 @@ void k_synth_g(const DevPlan *__restrict__ Pd, SynGeom G, const uint8_t *__restr
     static_assert(SIG == 0 || NCH <= SG_MAXCH, "the CBOC mode is built for up to 12 positions per launch");
     static_assert(!SEARCH || (SIG == 0 && NCH <= SG_MAXCH), "the threshold search is built for BOC(1,1), up to 12 positions per launch");
     static_assert(!SG_FIX(SIG, SEARCH) || (RW_BINS & (RW_BINS - 1)) == 0, "the fixed-point bin index is the top bits of the fraction word");
+    static_assert(!LIN || (SG_FIX(SIG, SEARCH) && NCH <= SG_MAXCH), "the linear carrier start is built for the BOC(1,1) bin-table instances, up to 12 positions");
     constexpr int MC = NCH <= SG_MAXCH ? SG_MAXCH : SG_MAXCH_WIDE;  // positions the per-wave records are laid out for
+    constexpr int LUT_N = LIN ? SG_LUT_LIN_N : SG_LUT_N;            // entries per carrier table
+    using REC = typename std::conditional<LIN, SgRecLin, SgRec>::type;
     // CBOC keeps two bin tables per channel (chip holds, half-period parity) of 64 bins each, as in k_synth
     constexpr int BINS = SIG ? CB_BINS : RW_BINS, BPITCH = SIG ? CB_BIN_PITCH : RW_BIN_PITCH;
     __shared__ uint32_t s_str[NCH * SG_STR_PITCH];
     __shared__ uint32_t s_mtab[16 * SG_MPOS];  // [sign pair of the first symbol * 4 + of its successor][position of the wrap]
-    __shared__ __attribute__((aligned(8))) int s_lut[2 * SG_LUT_N * (SIG ? 2 : 1)];  // CBOC: 8-byte entries (TA[k], TB[k])
+    __shared__ __attribute__((aligned(8))) int s_lut[2 * LUT_N * (SIG ? 2 : 1)];  // CBOC: 8-byte entries (TA[k], TB[k])
     __shared__ uint2 s_bin[NCH * BPITCH];
     __shared__ uint4 s_pat[NCH * 16];
     __shared__ float s_thr[NCH * 16];
@@ -388,10 +430,10 @@ void k_synth_g(const DevPlan *__restrict__ Pd, SynGeom G, const uint8_t *__restr
     __shared__ uint32_t s_pat6[SIG ? NCH * 16 : 1];
     __shared__ float s_thr6[SIG ? NCH * 16 : 1];
     __shared__ uint32_t s_sym[NCH * SG_SYMS];
-    __shared__ __attribute__((aligned(16))) SgRec s_rec[(SG_THREADS / 64) * 2 * MC];  // [wave][buffer][position]
+    __shared__ __attribute__((aligned(16))) REC s_rec[(SG_THREADS / 64) * 2 * MC];  // [wave][buffer][position]
     __shared__ double s_c511[MC];
     __shared__ uint32_t s_lutd[MC];
-    __shared__ uint32_t s_sya[(SG_THREADS / 64) * 2 * MC];  // ... LDS byte address of the sign mask of the chunk's first symbol
+    __shared__ uint32_t s_sya[LIN ? 1 : (SG_THREADS / 64) * 2 * MC];  // ... (legacy start; LIN: in the record) LDS byte address of the sign mask of the chunk's first symbol
     __shared__ int s_rwbad;
 
     // (s_setprio 1 / 2 here, to keep the verification kernel that runs beside this one out of its issue slots: the kernel ALONE gets
@@ -431,7 +473,7 @@ void k_synth_g(const DevPlan *__restrict__ Pd, SynGeom G, const uint8_t *__restr
         // pos = clamp(first half chip of the window - (8184 - 16), 0, 16): the fields from 16 - pos on lie behind the wrap
         s_mtab[i] = pos == 0 ? mc : pos == 16 ? mn : (mc ^ ((mc ^ mn) & (~0u << (2 * (16 - pos)))));
     }
-    for (int i = tid; i < 2 * SG_LUT_N * (SIG ? 2 : 1); i += nthr) {
+    for (int i = tid; i < 2 * LUT_N * (SIG ? 2 : 1); i += nthr) {
         if constexpr (SIG == 1) {  // int i = (table (plain / conjugate) x SG_LUT_N + entry) x 2 + (0: TA, 1: TB); Pd->lut = [TA 512][TB 512]
             const int ie = i >> 1, tab = ie >= SG_LUT_N, ii = ie - tab * SG_LUT_N;
             int k = ii < 512 ? ii - 511 : ii - 512;
@@ -443,10 +485,14 @@ void k_synth_g(const DevPlan *__restrict__ Pd, SynGeom G, const uint8_t *__restr
         // table (plain / conjugate) x SG_LUT_N + entry i = floor(511 p + 512): i >= 512: LUT[(i - 512) mod 511] (the phase wraps
         // at 1, so 511 p wraps at 511); i < 512 (mirrored phase still negative after a Doppler sign change): (int) truncates
         // towards zero (:509), so entry i holds k = i - 511
-        const int tab = i >= SG_LUT_N, ii = i - tab * SG_LUT_N;
+        const int tab = i >= LUT_N, ii = i - tab * LUT_N;
         int k = ii < 512 ? ii - 511 : ii - 512;
+        if constexpr (LIN) {
+            k = k >= 511 ? k % 511 : k;  // every cycle a chunk can cross
+        } else {
         k = k >= 511 ? k - 511 : k;
         k = k >= 511 ? k - 511 : k;
+        }
         s_lut[i] = p_lut[(tab ? -k : k) & 511];
     }
 #ifdef SG_BALANCED_RANGES
@@ -537,7 +583,7 @@ void k_synth_g(const DevPlan *__restrict__ Pd, SynGeom G, const uint8_t *__restr
         const double d = (tid < NCH && tid < nact) ? p_dstep[ix] : 0.0;
         s_c511[tid] = 511.0 * __builtin_fabs(d);
         s_lutd[tid] = SIG ? (uint32_t)(uintptr_t)(sg_lds_int)s_lut + (((uint32_t)(d2u(d) >> 32) >> 31) ? SG_LUT_N * 8u : 0u) - (0x41300000u << 3)
-                          : (uint32_t)(uintptr_t)(sg_lds_int)s_lut + (((uint32_t)(d2u(d) >> 32) >> 31) ? SG_LUT_N * 4u : 0u) - (0x41300000u << 2);
+                          : (uint32_t)(uintptr_t)(sg_lds_int)s_lut + (((uint32_t)(d2u(d) >> 32) >> 31) ? LUT_N * 4u : 0u) - (0x41300000u << 2);
     }
     // ---- hold patterns (k_synth<.., RW = 1>, rw_phase_a): step A, the 15 thresholds T_u = 1 - frac(u s) of each channel, sorted
     for (int t = tid; t < NCH * 16; t += nthr) {
@@ -703,8 +749,8 @@ void k_synth_g(const DevPlan *__restrict__ Pd, SynGeom G, const uint8_t *__restr
     // epoch start (idle: an all-zero row)
     const uint32_t *const syml = s_sym + jl * SG_SYMS - (onl ? p_ib0[ixl] : 0);
     const uint32_t mtab0 = (uint32_t)(uintptr_t)(sg_lds_u32)s_mtab;
-    SgRec *const recw = s_rec + wv * 2 * MC;
-    uint32_t *const syaw = s_sya + wv * 2 * MC;
+    REC *const recw = s_rec + wv * 2 * MC;
+    uint32_t *const syaw = s_sya + (LIN ? 0 : wv * 2 * MC);
     const int cstep_w = nw;
     int c = __builtin_amdgcn_readfirstlane(c_begin + wv);
     // checkpoint of chunk cc: x (pre-check code phase, chips), p (carrier phase), ibit | flipped << 16
@@ -744,11 +790,22 @@ void k_synth_g(const DevPlan *__restrict__ Pd, SynGeom G, const uint8_t *__restr
         r.s = sl;
         r.dabs = dabsl;
         if (lane < NCH) {
-            recw[buf * MC + lane] = r;
+            if constexpr (!LIN) recw[buf * MC + lane] = r;
             // (idle positions: steps zero, stream row zero, sign pairs zero -- no contribution)
             const uint32_t ks = onl ? (lib & 0xffffu) + 500u * (lib >> 16) + (pend ? 1u : 0u) : 0u;
             const uint32_t pair = syml[ks] * 4u + syml[ks + 1];
-            syaw[buf * MC + lane] = mtab0 + pair * (SG_MPOS * 4u);
+            if constexpr (LIN) {
+                // the DDA word of the chunk's first sample (one rounding, at most 2^-33); the groups add 16 g x 511 |d| to it
+                SgRecLin rl;
+                rl.yc = r.yc;
+                rl.s = r.s;
+                rl.Tc = __builtin_fma(511.0, r.pm, SG_BIAS);
+                rl.sa = mtab0 + pair * (SG_MPOS * 4u) - 4u * (uint32_t)SG_POS_LO;
+                rl.hib = SG_POS_LO + 16;
+                recw[buf * MC + lane] = rl;
+            } else {
+                syaw[buf * MC + lane] = mtab0 + pair * (SG_MPOS * 4u);
+            }
         }
     };
     if (c < c_end) fetch(c);
@@ -779,10 +836,10 @@ void k_synth_g(const DevPlan *__restrict__ Pd, SynGeom G, const uint8_t *__restr
         }
         uint32_t amb = ~0u;
         uint64_t undec = rw_off ? ~0ull : 0ull;
-        const SgRec *rec = recw + buf * MC;
+        const REC *rec = recw + buf * MC;
         const uint32_t *sya = syaw + buf * MC;
         // balanced parts: 5, 6, 7, 9, 10, 11 positions are cut 3+2, 3+3, 4+3, 3+3+3, 4+3+3, 4+4+3
-#define SG_PART(J0, CNT) sg_part<J0, CNT, MODE, SIG, BINS, BPITCH, SEARCH>(o, amb, undec, g16, rec, sya, s_c511, s_lutd, s_str, s_bin, s_pat, s_bin6, s_pat6, s_thr, nact); \
+#define SG_PART(J0, CNT) sg_part<J0, CNT, MODE, SIG, BINS, BPITCH, SEARCH, LIN>(o, amb, undec, g16, rec, sya, s_c511, s_lutd, s_str, s_bin, s_pat, s_bin6, s_pat6, s_thr, nact); \
                          __builtin_amdgcn_sched_barrier(0);
         // (CBOC: parts of at most three -- a part's group start keeps 17 values per position alive, 13 in the BOC(1,1) form)
         if constexpr (SIG == 1 && NCH <= 3) { SG_PART(0, NCH) }
@@ -1031,6 +1088,9 @@ extern "C" int galk_launch_synth_g_wide(const DevPlan *P, const DevPlan *Pd, int
 extern "C" int galk_launch_synth_g_search(const DevPlan *P, const DevPlan *Pd, int nch, int accumulate, int mode, const uint8_t *act, const int *nact,
                                           uint32_t *iq, const SynGeom *G, int grid, hipStream_t st);
 
+extern "C" int galk_launch_synth_g_lin(const DevPlan *P, const DevPlan *Pd, int nch, int accumulate, int mode, const uint8_t *act, const int *nact,
+                                       uint32_t *iq, const SynGeom *G, int grid, int threads, hipStream_t st);
+
 #if GAL_GTU_WIDE
 template <bool ACC, int MODE>
 static int launch_wide_t(const DevPlan *P, const DevPlan *Pd, int nch, const uint8_t *act, const int *nact, uint32_t *iq, const SynGeom &G, int ngrid,
@@ -1083,6 +1143,32 @@ extern "C" int galk_launch_synth_g_search(const DevPlan *P, const DevPlan *Pd, i
 }
 #endif  // GAL_GTU_SEARCH
 
+#if GAL_GTU_LIN
+template <bool ACC, int MODE>
+static int launch_lin_t(const DevPlan *P, const DevPlan *Pd, int nch, const uint8_t *act, const int *nact, uint32_t *iq, const SynGeom &G, int ngrid,
+                        int threads, hipStream_t st)
+{
+    const dim3 grid(ngrid), block(threads);
+#define GAL_LCASE(n) case n: hipLaunchKernelGGL((k_synth_g<n, ACC, MODE, 0, false, true>), grid, block, 0, st, Pd, G, act, nact, iq, P->gflist, P->gflist_cap); return 0;
+    switch (nch) {
+        GAL_LCASE(1) GAL_LCASE(2) GAL_LCASE(3) GAL_LCASE(4) GAL_LCASE(5) GAL_LCASE(6)
+        GAL_LCASE(7) GAL_LCASE(8) GAL_LCASE(9) GAL_LCASE(10) GAL_LCASE(11) GAL_LCASE(12)
+    default: return -1;
+    }
+#undef GAL_LCASE
+}
+extern "C" int galk_launch_synth_g_lin(const DevPlan *P, const DevPlan *Pd, int nch, int accumulate, int mode, const uint8_t *act, const int *nact,
+                                       uint32_t *iq, const SynGeom *G, int grid, int threads, hipStream_t st)
+{
+#define GAL_MCASE(m) case m: return accumulate ? launch_lin_t<true, m>(P, Pd, nch, act, nact, iq, *G, grid, threads, st) : launch_lin_t<false, m>(P, Pd, nch, act, nact, iq, *G, grid, threads, st);
+    switch (mode) {
+        GAL_MCASE(1) GAL_MCASE(2) GAL_MCASE(3) GAL_MCASE(4)
+    default: return -3;
+    }
+#undef GAL_MCASE
+}
+#endif  // GAL_GTU_LIN
+
 #if GAL_GTU_MAIN
 template <bool ACC, int MODE, int SIG>
 static int launch_synth_g_t(const DevPlan *P, const DevPlan *Pd, int nch, const uint8_t *act, const int *nact, uint32_t *iq, int e0,
@@ -1098,6 +1184,9 @@ static int launch_synth_g_t(const DevPlan *P, const DevPlan *Pd, int nch, const 
 #else
     const dim3 grid(sg_grid(P, ne, nch)), block(P->gthreads >= 64 && P->gthreads <= SG_THREADS && (P->gthreads & 63) == 0 ? P->gthreads : 512);
 #endif
+    // every carrier of the batch inside the linear start's range (the plan's gate): the instances with the multi-cycle table
+    if constexpr (SIG == 0)
+        if (P->g_lin) return galk_launch_synth_g_lin(P, Pd, nch, ACC ? 1 : 0, MODE, act, nact, iq, &G, (int)grid.x, (int)block.x, st);
 #define GAL_CASE(n) case n: hipLaunchKernelGGL((k_synth_g<n, ACC, MODE, SIG>), grid, block, 0, st, Pd, G, act, nact, iq, P->gflist, P->gflist_cap); break;
     switch (nch) {  // one instance per channel count, in the CBOC mode too (round 4: 4 / 8 / 12 positions, a 9-SV batch paid for 12)
         GAL_CASE(1) GAL_CASE(2) GAL_CASE(3) GAL_CASE(4) GAL_CASE(5) GAL_CASE(6)
