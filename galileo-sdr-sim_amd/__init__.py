@@ -22,6 +22,7 @@ from .synth import (  # noqa: F401
     GAL_IQ_IBYTE,
     GAL_IQ_ISHORT,
     IQ_FORMATS,
+    REFL_DTYPE,
     SCINT_DTYPE,
     STEER_DTYPE,
     GalSynthError,
@@ -43,6 +44,9 @@ from .synth import (  # noqa: F401
     osc_lo_step,
     osc_make,
     pack_page,
+    refl_check,
+    refl_geom,
+    refl_row,
     scint_check,
     scint_make,
     scint_rows,

@@ -171,7 +171,8 @@ struct RowRing {
     struct Buf {
         std::vector<gal_chan_epoch_t> rows;
         std::vector<uint16_t> gains;  // per-satellite signal power: [epochs][slots] Q7
-        std::vector<double> azel;     // --array: [epochs][slots][2] azimuth and elevation, radians
+        std::vector<double> azel;     // --array, --reflector: [epochs][slots][2] azimuth and elevation, radians
+        bool ahead = false;           // --reflector: row n (one behind the batch) is the next batch's first epoch
         int n = 0;                    // epochs in it; < 0: front-end error, 0: end of the scenario
         bool ready = false;           // under mu: the producer's until ready, the main thread's until it clears it
     } buf[kBufs];
@@ -181,9 +182,45 @@ struct RowRing {
     std::string error;           // under mu, with n < 0
 };
 
+// --reflector: a batch with one epoch of look-ahead behind it, so that the last epoch's rows know the geometry of the epoch that
+// follows (the phase runs from one epoch's start to the next; the file must not depend on -B).  The buffers hold batch_epochs + 1
+// epochs; the look-ahead epoch is kept and opens the next batch.
+struct LookAhead {
+    std::vector<gal_chan_epoch_t> rows;
+    std::vector<uint16_t> gains;
+    std::vector<double> azel;
+    bool have = false, ended = false;
+    int next(gal_scen_t *scen, const Config &c, RowRing::Buf &b)
+    {
+        const size_t S = (size_t)c.sc.n_slots;
+        b.ahead = false;
+        if (ended) return 0;
+        if (!have) {  // the scenario's first epoch
+            const int n = gal_scen_next_azel(scen, 1, b.rows.data(), c.power_on ? b.gains.data() : nullptr, b.azel.data());
+            if (n <= 0) return n;
+        } else {
+            std::copy(rows.begin(), rows.end(), b.rows.begin());
+            std::copy(azel.begin(), azel.end(), b.azel.begin());
+            if (c.power_on) std::copy(gains.begin(), gains.end(), b.gains.begin());
+        }
+        const int m = gal_scen_next_azel(scen, c.batch_epochs, b.rows.data() + S, c.power_on ? b.gains.data() + S : nullptr, b.azel.data() + 2 * S);
+        if (m < 0) return m;
+        if (m < c.batch_epochs) {  // the scenario ends inside this batch: 1 + m epochs, nothing behind them
+            ended = true;
+            return 1 + m;
+        }
+        rows.assign(b.rows.begin() + (size_t)m * S, b.rows.begin() + (size_t)(m + 1) * S);
+        azel.assign(b.azel.begin() + 2 * (size_t)m * S, b.azel.begin() + 2 * (size_t)(m + 1) * S);
+        if (c.power_on) gains.assign(b.gains.begin() + (size_t)m * S, b.gains.begin() + (size_t)(m + 1) * S);
+        have = b.ahead = true;
+        return m;
+    }
+};
+
 void produce_rows(RowRing &ring, gal_scen_t *scen, const Config &c, Clock::time_point t_start)
 {
     long produced_epochs = 0;
+    LookAhead ahead;
     for (int w = 0;; w = (w + 1) % RowRing::kBufs) {
         RowRing::Buf &b = ring.buf[w];
         {
@@ -195,6 +232,7 @@ void produce_rows(RowRing &ring, gal_scen_t *scen, const Config &c, Clock::time_
         // k * 0.1 s after the start, so that position updates are current
         if (c.realtime) std::this_thread::sleep_until(t_start + std::chrono::milliseconds(100) * produced_epochs);
         const int n = g_stop         ? 0
+                      : c.refl_on()  ? ahead.next(scen, c, b)
                       : c.array_on() ? gal_scen_next_azel(scen, c.batch_epochs, b.rows.data(), c.power_on ? b.gains.data() : nullptr, b.azel.data())
                       : c.power_on   ? gal_scen_next_gains(scen, c.batch_epochs, b.rows.data(), b.gains.data())
                                    : gal_scen_next(scen, c.batch_epochs, b.rows.data());
@@ -249,6 +287,7 @@ struct Run {
     std::vector<int32_t> slot_of;        // ... and per echo in view its slot and its line of the file
     std::vector<const EchoSpec *> spec_of;
     std::vector<gal_iq_scint_t> sc_rows;  // --scint: the batch's rows [epochs][slots]
+    std::vector<gal_iq_refl_t> rf_rows;   // --reflector: the rows [epochs][slots with echoes x reflectors] of one call
     gal_corr_req_t mon_shape;  // what every monitor request shares
     MonSummary mon_sum[GAL_NUM_PRN + 1];
     uint64_t agc_logged = 0;  // blocks written to the log
@@ -446,6 +485,64 @@ int synth_mpath(Run &r, const RowRing::Buf &rows, int n, int16_t *d_iq)
                                r.c.sc_on() ? r.sc_rows.data() : nullptr, (uint64_t)r.emitted * (uint64_t)r.cfg.samples_per_epoch, d_iq, r.state.data());
 }
 
+// --reflector: the gains of --power-model and its kin, or unity; every slot that carries an admitted satellite has one echo per
+// reflector, with the rows of gal_synth_refl_geom / _row from the epoch's azimuth and elevation and the next epoch's (the batch's last
+// epoch: the look-ahead row behind it).  The batch is cut into calls where the set of such slots changes, so that a call's table
+// holds exactly reflectors x satellites columns: any cut into whole epochs gives the bytes of one call, and a slot's history line is
+// written in every call in which it carries an echo
+int synth_refl(Run &r, const RowRing::Buf &rows, int n, int16_t *d_iq)
+{
+    const Config &c = r.c;
+    const int S = r.cfg.n_slots, R = (int)c.refls.size();
+    const gal_chan_epoch_t *rec = rows.rows.data();
+    if (c.power_on) {
+        r.mp_gains.assign(rows.gains.begin(), rows.gains.begin() + (size_t)n * S);
+        r.note_gains(rec, r.mp_gains.data(), (size_t)n * S);
+    } else {
+        r.mp_gains.assign((size_t)n * S, (uint16_t)GAL_GAIN_UNITY);
+    }
+    const auto echoes_in = [&](int e, int s) { const int prn = rec[(size_t)e * S + s].prn; return prn >= 1 && prn <= GAL_NUM_PRN && c.refl_prn[prn]; };
+    const auto same_set = [&](int e0, int e1) {
+        for (int s = 0; s < S; ++s)
+            if (echoes_in(e0, s) != echoes_in(e1, s)) return false;
+        return true;
+    };
+    for (int e0 = 0, e1; e0 < n; e0 = e1) {
+        for (e1 = e0 + 1; e1 < n && same_set(e0, e1);) ++e1;
+        r.slot_of.clear();
+        for (int s = 0; s < S; ++s)
+            for (int k = 0; k < R && echoes_in(e0, s); ++k) r.slot_of.push_back(s);
+        const int n_echo = (int)r.slot_of.size();
+        if (n_echo > GAL_ECHO_MAX) {
+            r.fail("--reflector: %d reflectors x %d satellites = %d echoes in epoch %d (%.1f s), more than %d: use --reflector-prn", R, n_echo / R, n_echo,
+                   r.emitted + e0, (r.emitted + e0) * 0.1, GAL_ECHO_MAX);
+            return GAL_E_INVAL;
+        }
+        r.rf_rows.assign((size_t)(e1 - e0) * (n_echo > 0 ? n_echo : 1), gal_iq_refl_t{});
+        for (int e = e0; e < e1; ++e)
+            for (int j = 0; j < n_echo; ++j) {
+                const int s = r.slot_of[j], k = j % R;
+                const size_t i = (size_t)e * S + s, i1 = i + S;  // i1: the same slot one epoch on, inside the batch or the look-ahead row
+                const ReflSpec &f = c.refls[k];
+                double now = -1.0, next = -1.0;
+                int rc = gal_synth_refl_geom(f.kind, f.p, rows.azel[2 * i], rows.azel[2 * i + 1], &now);
+                if (rc == GAL_OK && (e + 1 < n || rows.ahead) && rec[i1].prn == rec[i].prn)
+                    rc = gal_synth_refl_geom(f.kind, f.p, rows.azel[2 * i1], rows.azel[2 * i1 + 1], &next);
+                gal_iq_refl_t &row = r.rf_rows[(size_t)(e - e0) * n_echo + j];
+                if (rc == GAL_OK) rc = gal_synth_refl_row(now, next, f.rel_db, f.phase_deg, c.sample_rate(), r.cfg.samples_per_epoch, r.mp_gains[i], &row);
+                if (rc != GAL_OK) return rc;
+                if (c.refl_log_fp)
+                    fprintf(c.refl_log_fp, "%.1f,%d,%d,%.9f,%u,%u,%u,%u,%d\n", (r.emitted + e) * 0.1, rec[i].prn, k, now, row.delay, row.frac_q12, row.ph0, row.gain_q7,
+                            row.dph);
+            }
+        const int rc = gal_synth_run_refl(r.eng, rec + (size_t)e0 * S, e1 - e0, r.have_state || e0 > 0 ? r.state.data() : nullptr,
+                                          r.mp_gains.data() + (size_t)e0 * S, r.slot_of.data(), r.rf_rows.data(), n_echo,
+                                          d_iq + (size_t)e0 * r.cfg.samples_per_epoch * 2, r.state.data());
+        if (rc != GAL_OK) return rc;
+    }
+    return GAL_OK;
+}
+
 // --array: every active satellite a run of its own, then the array pass into the K element batches that lie one behind the other in
 // d_iq.  The gains are those of --power-model and its kin, or unity; the phases come from the front-end's azimuth and elevation
 int synth_array(Run &r, const RowRing::Buf &rows, int n, int16_t *d_iq)
@@ -599,8 +696,8 @@ int run_loop(Run &r, RowRing &ring, SlotPair &sp, int total, Clock::time_point t
     const Config &c = r.c;
     const bool batch_timing = getenv("GAL_CLI_TIMING") != nullptr;
     const auto ms_since = [](Clock::time_point a) { return std::chrono::duration<double, std::milli>(Clock::now() - a).count(); };
-    const auto synth = c.array_on() ? synth_array : c.parts_on() ? synth_mpath : c.power_on ? synth_gains : synth_plain;
-    const bool finished_inside = c.array_on() || c.parts_on() || c.power_on;  // run_gains / run_mpath return with every group finished
+    const auto synth = c.array_on() ? synth_array : c.refl_on() ? synth_refl : c.parts_on() ? synth_mpath : c.power_on ? synth_gains : synth_plain;
+    const bool finished_inside = c.array_on() || c.refl_on() || c.parts_on() || c.power_on;  // run_gains / run_mpath return with every group finished
     int cur = 0;
     for (int ri = 0; r.emitted < total && !sp.io_error && !g_stop; cur ^= 1, ri = (ri + 1) % RowRing::kBufs) {
         const auto tb0 = Clock::now();
@@ -628,7 +725,7 @@ int run_loop(Run &r, RowRing &ring, SlotPair &sp, int total, Clock::time_point t
             mon = monitor_requests(r, rows.rows.data(), n, b.mon);
         }
         if (synth(r, rows, n, b.d_iq) != GAL_OK) {
-            r.lib_fail();
+            if (r.err.empty()) r.lib_fail();  // (synth_refl has said why itself where the reason is its own)
             break;
         }
         {  // plan() has uploaded the rows: the producer may refill this buffer
@@ -652,6 +749,7 @@ int run_loop(Run &r, RowRing &ring, SlotPair &sp, int total, Clock::time_point t
             fprintf(stderr, "[timing] batch at %7.2f ms: %3d epochs, waited %.2f ms for rows, %.2f for a free slot, %s %.2f\n",
                     std::chrono::duration<double, std::milli>(tb0 - t_start).count(), n, tb_rows, tb_slot - tb_rows,
                     c.array_on() ? "run_array (every satellite's plan + execute + finish, the array pass enqueued)"
+                    : c.refl_on() ? "run_refl (every group's plan + execute + finish, the reflector pass enqueued)"
                     : c.parts_on() ? "run_scint (every group's plan + execute + finish, scintillation and the echo pass enqueued)"
                     : c.power_on ? "run_gains (every group's plan + execute + finish, the sum enqueued)"
                                  : "plan + execute + finish",
@@ -848,6 +946,7 @@ int run(Config &c, gal_scen_t *scen)
     if (c.n_writers < 0) c.n_writers = 0;
     r.K = c.n_elem();
     if (c.array_log_file && !(c.array_log_fp = fopen(c.array_log_file, "w"))) die("ERROR: --array-log %s cannot be written.\n", c.array_log_file);
+    if (c.refl_log_file && !(c.refl_log_fp = fopen(c.refl_log_file, "w"))) die("ERROR: --reflector-log %s cannot be written.\n", c.refl_log_file);
     std::vector<Sink> sinks(r.K);
     for (int k = 0; k < r.K; ++k) {
         std::string path = c.outfile;
@@ -887,9 +986,10 @@ int run(Config &c, gal_scen_t *scen)
     const auto t_start = Clock::now();
     RowRing ring;
     for (auto &b : ring.buf) {
-        b.rows.resize((size_t)c.batch_epochs * c.sc.n_slots);
-        if (c.power_on) b.gains.resize((size_t)c.batch_epochs * c.sc.n_slots);
-        if (c.array_on()) b.azel.resize((size_t)c.batch_epochs * c.sc.n_slots * 2);
+        const size_t epochs = (size_t)c.batch_epochs + (c.refl_on() ? 1 : 0);  // (--reflector: one epoch of look-ahead)
+        b.rows.resize(epochs * c.sc.n_slots);
+        if (c.power_on) b.gains.resize(epochs * c.sc.n_slots);
+        if (c.azel_on()) b.azel.resize(epochs * c.sc.n_slots * 2);
     }
     std::thread producer(produce_rows, std::ref(ring), scen, std::cref(c), t_start);
     r.state.resize(c.sc.n_slots);
@@ -916,6 +1016,10 @@ int run(Config &c, gal_scen_t *scen)
         if (!s.finish()) sp.io_error = true;
     if (c.array_log_fp && fclose(c.array_log_fp) != 0) {
         fprintf(stderr, "ERROR: writing the array log %s failed\n", c.array_log_file);
+        sp.io_error = true;
+    }
+    if (c.refl_log_fp && fclose(c.refl_log_fp) != 0) {
+        fprintf(stderr, "ERROR: writing the reflector log %s failed\n", c.refl_log_file);
         sp.io_error = true;
     }
     stage("run (= Process time)");

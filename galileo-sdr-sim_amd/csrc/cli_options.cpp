@@ -419,8 +419,9 @@ struct Args {
                *oversample = nullptr, *multipath = nullptr, *agc = nullptr, *agc_block = nullptr, *agc_window = nullptr, *agc_init = nullptr,
                *agc_log = nullptr, *i2bit_thr = nullptr, *antenna = nullptr, *cn0 = nullptr, *noise_seed = nullptr, *noise_stream = nullptr,
                *signal_gain = nullptr, *lo_offset = nullptr, *phase_noise = nullptr, *osc_seed = nullptr, *osc_stream = nullptr,
-               *scint = nullptr, *scint_seed = nullptr, *scint_site = nullptr, *array = nullptr, *array_log = nullptr;
-    std::vector<const char *> prn_power, jam, jam_dir;
+               *scint = nullptr, *scint_seed = nullptr, *scint_site = nullptr, *array = nullptr, *array_log = nullptr, *reflector_prn = nullptr,
+               *reflector_log = nullptr;
+    std::vector<const char *> prn_power, jam, jam_dir, reflector;
     long agc_window_n = 8;
     double agc_target = 0.0, agc_init_rms = -1.0;  // (0 / < 0: the defaults, known once shift and sigma are)
     double sig_peak = 4100.0;                      // the largest |x| of the signal sum: 4100 in the reference's scenarios
@@ -428,7 +429,7 @@ struct Args {
 };
 
 enum { OPT_STRICT = 1000, OPT_SITES, OPT_WRITERS, OPT_GPUS, OPT_PER_GPU, OPT_EXACT, OPT_SHIFT_TOE, OPT_REF_T, OPT_JAM, OPT_POWER_MODEL, OPT_PRN_POWER, OPT_AGC,
-       OPT_JAM_DIR, OPT_STRING };  // OPT_STRING + k: the k-th row whose argument is only kept (Args::*dest)
+       OPT_JAM_DIR, OPT_REFLECTOR, OPT_STRING };  // OPT_STRING + k: the k-th row whose argument is only kept (Args::*dest)
 constexpr int NO = no_argument, ARG = required_argument, MAYBE = optional_argument;
 struct OptRow {
     const char *name;  // one letter: a short option (its id is the letter)
@@ -461,6 +462,8 @@ const OptRow kOptions[] = {
     {"scint", ARG, OPT_STRING + 22, true, &Args::scint}, {"scint-seed", ARG, OPT_STRING + 23, true, &Args::scint_seed},
     {"scint-site", ARG, OPT_STRING + 24, false, &Args::scint_site}, {"array", ARG, OPT_STRING + 25, false, &Args::array},
     {"array-log", ARG, OPT_STRING + 26, false, &Args::array_log}, {"jam-dir", ARG, OPT_JAM_DIR, false, nullptr},
+    {"reflector", ARG, OPT_REFLECTOR, true, nullptr}, {"reflector-prn", ARG, OPT_STRING + 27, true, &Args::reflector_prn},
+    {"reflector-log", ARG, OPT_STRING + 28, false, &Args::reflector_log},
 };
 
 // the command line into Args and the Config's plain fields; every option with to_children also into c->child_args
@@ -538,6 +541,7 @@ void parse_args(int argc, char *argv[], Args *a, Config *c)
         case OPT_PER_GPU: c->sites_per_gpu = atoi(optarg); break;
         case OPT_JAM: a->jam.push_back(optarg); break;
         case OPT_JAM_DIR: a->jam_dir.push_back(optarg); break;
+        case OPT_REFLECTOR: a->reflector.push_back(optarg); break;
         case OPT_POWER_MODEL: a->power_model = true; break;
         case OPT_PRN_POWER: a->prn_power.push_back(optarg); break;
         case OPT_AGC: a->agc_given = true; break;
@@ -649,6 +653,7 @@ void cfg_array(const Args &a, Config &c)
         return;
     }
     if (a.multipath) die("ERROR: --array does not go with --multipath: an echo needs a direction of arrival of its own.\n");
+    if (!a.reflector.empty()) die("ERROR: --reflector does not go with --array: an echo needs a direction of arrival of its own.\n");
     if (a.lo_offset || a.phase_noise) die("ERROR: --array does not go with --lo-offset / --phase-noise: the oscillator keeps one state per engine, an array needs one per element.\n");
     if (a.fir || a.fir_lowpass) die("ERROR: --array does not go with --fir / --fir-lowpass: the filter keeps one history per engine, an array needs one per element.\n");
     if (a.oversample) die("ERROR: --array does not go with --oversample: the decimator keeps one history per engine, an array needs one per element.\n");
@@ -680,6 +685,74 @@ void cfg_array(const Args &a, Config &c)
             k < a.jam_dir.size() ? "" : " (no --jam-dir: the zenith)");
 }
 
+// --reflector, --reflector-prn, --reflector-log: the planes, the satellites that see them, and what does not go with them yet.  Returns
+// the sum of the reflectors' amplitudes: a satellite can reach 1 + that sum times its own amplitude
+double cfg_reflectors(const Args &a, Config &c)
+{
+    const double kD2R = 3.14159265358979323846 / 180.0;
+    if (a.reflector.empty()) {
+        if (a.reflector_prn || a.reflector_log) die("ERROR: --reflector-prn and --reflector-log need --reflector.\n");
+        return 0.0;
+    }
+    if (a.multipath) die("ERROR: --reflector does not go with --multipath: both fill the one echo table of a batch.\n");
+    if (a.scint) die("ERROR: --reflector does not go with --scint: the scintillated part is not handed to the reflector pass yet.\n");
+    if (a.array) die("ERROR: --reflector does not go with --array: an echo needs a direction of arrival of its own.\n");
+    if (a.reflector.size() > (size_t)kReflMax) die("ERROR: --reflector may be given %d times at most.\n", kReflMax);
+    double sum = 0.0;
+    for (const char *text : a.reflector) {
+        ReflSpec r = {};
+        double v[4] = {0, 0, 0, 0};
+        char tail = 0;
+        int got = 0;
+        r.phase_deg = 180.0;
+        if (strncmp(text, "ground,", 7) == 0) {
+            r.kind = GAL_REFL_GROUND;
+            got = sscanf(text + 7, "%lf , %lf , %lf %c", &v[0], &v[1], &v[2], &tail);
+            if (got < 2 || got > 3) die("ERROR: --reflector '%s' is not ground,h_m,rel_db[,phase_deg].\n", text);
+            r.p[0] = v[0], r.rel_db = v[1];
+            if (got == 3) r.phase_deg = v[2];
+        } else if (strncmp(text, "wall,", 5) == 0) {
+            r.kind = GAL_REFL_WALL;
+            got = sscanf(text + 5, "%lf , %lf , %lf , %lf %c", &v[0], &v[1], &v[2], &v[3], &tail);
+            if (got < 3 || got > 4) die("ERROR: --reflector '%s' is not wall,dist_m,az_deg,rel_db[,phase_deg].\n", text);
+            r.p[0] = v[0], r.p[1] = v[1] * kD2R, r.rel_db = v[2];
+            if (got == 4) r.phase_deg = v[3];
+        } else {
+            die("ERROR: --reflector '%s' is neither ground,h_m,rel_db[,phase_deg] nor wall,dist_m,az_deg,rel_db[,phase_deg].\n", text);
+        }
+        // the library's own refusals, on a satellite at the zenith: a plane that is not finite or lies on the wrong side, an amplitude above 2
+        double x = 0.0;
+        gal_iq_refl_t row;
+        if (!std::isfinite(r.phase_deg) || gal_synth_refl_geom(r.kind, r.p, 0.0, 90.0 * kD2R, &x) != GAL_OK ||
+            gal_synth_refl_row(0.0, 0.0, r.rel_db, r.phase_deg, 2.6e6, 1, 0, &row) != GAL_OK)
+            die("ERROR: --reflector %s: %s\n", text, std::isfinite(r.phase_deg) ? gal_synth_last_error() : "the phase is not finite");
+        sum += pow(10.0, r.rel_db / 20.0);
+        c.refls.push_back(r);
+    }
+    for (int p = 1; p <= GAL_NUM_PRN; ++p) c.refl_prn[p] = a.reflector_prn == nullptr;
+    for (const char *s = a.reflector_prn; s && *s;) {
+        char *end = nullptr;
+        const long p = strtol(s, &end, 10);
+        if (end == s || p < 1 || p > GAL_NUM_PRN || (*end && *end != ',')) die("ERROR: --reflector-prn '%s' is not prn[,prn...] (PRN 1..%d).\n", a.reflector_prn, GAL_NUM_PRN);
+        c.refl_prn[p] = true;
+        s = *end ? end + 1 : end;
+    }
+    if (a.reflector_prn && !*a.reflector_prn) die("ERROR: --reflector-prn '' is not prn[,prn...] (PRN 1..%d).\n", GAL_NUM_PRN);
+    if (a.reflector_log && (!*a.reflector_log || strcmp(a.reflector_log, "-") == 0)) die("ERROR: --reflector-log needs a file name.\n");
+    c.refl_log_file = a.reflector_log;
+    for (size_t k = 0; k < c.refls.size(); ++k) {
+        const ReflSpec &r = c.refls[k];
+        if (r.kind == GAL_REFL_GROUND)
+            say(c, "Reflector %zu: ground, antenna height %.3f m, amplitude %.4f (%.2f dB), reflection phase %.2f deg\n", k, r.p[0], pow(10.0, r.rel_db / 20.0), r.rel_db, r.phase_deg);
+        else
+            say(c, "Reflector %zu: wall at %.3f m towards azimuth %.2f deg, amplitude %.4f (%.2f dB), reflection phase %.2f deg\n", k, r.p[0], r.p[1] / kD2R,
+                pow(10.0, r.rel_db / 20.0), r.rel_db, r.phase_deg);
+    }
+    say(c, "Reflectors: %zu; a satellite reaches up to %.3f times its own amplitude; at most %d echoes (reflectors x satellites) per epoch\n", c.refls.size(),
+        1.0 + sum, GAL_ECHO_MAX);
+    return sum;
+}
+
 // per-satellite signal power, --multipath and --oversample: what scales the headroom's signal term, and the rate the passes run at
 void cfg_signals(Args &a, Config &c)
 {
@@ -702,7 +775,7 @@ void cfg_signals(Args &a, Config &c)
             a.antenna ? a.antenna : "isotropic", a.prn_power.size(), a.prn_power.size() == 1 ? "" : "s", power_peak, 20.0 * log10(power_peak));
     }
     // a satellite with echoes can reach 1 + sum alpha times its own amplitude: the largest such sum
-    double echo_peak = 1.0, echo_sum[GAL_NUM_PRN + 1] = {0};
+    double echo_peak = 1.0 + cfg_reflectors(a, c), echo_sum[GAL_NUM_PRN + 1] = {0};
     if (a.multipath) {
         if (!load_multipath(a.multipath, &c.echoes, &why)) die("ERROR: --multipath %s: %s.\n", a.multipath, why.c_str());
         for (const EchoSpec &e : c.echoes) {

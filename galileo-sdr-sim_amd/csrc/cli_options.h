@@ -35,6 +35,14 @@ struct ArrayElem {
     double enu[3];
 };
 
+// --reflector ground,h_m,rel_db[,phase_deg] | wall,dist_m,az_deg,rel_db[,phase_deg]: a reflecting plane (gal_synth_refl_geom)
+struct ReflSpec {
+    int kind;     // GAL_REFL_GROUND, GAL_REFL_WALL
+    double p[2];  // height | distance, azimuth of the wall in radians
+    double rel_db, phase_deg;
+};
+constexpr int kReflMax = 4;  // --reflector may be given this often
+
 struct Config {
     gal_scen_cfg_t sc;  // (nav_file / motion_file point into navfile / umfile: set by main, once the Config has its place)
     std::string navfile, outfile, umfile, sitesfile;
@@ -55,6 +63,10 @@ struct Config {
     double jam_az[GAL_INTERF_MAX], jam_el[GAL_INTERF_MAX];  // --jam-dir, radians; without one the zenith
     const char *array_log_file = nullptr;
     FILE *array_log_fp = nullptr;
+    std::vector<ReflSpec> refls;          // --reflector: the batch goes through gal_synth_run_refl
+    bool refl_prn[GAL_NUM_PRN + 1] = {};  // --reflector-prn: the satellites that have the echoes; without it all
+    const char *refl_log_file = nullptr;
+    FILE *refl_log_fp = nullptr;
     bool noise_on = false;         // --cn0
     gal_iq_noise_t noise;          // (without --cn0 it still carries the signal gain of the --jam sources)
     int n_jam = 0;
@@ -78,13 +90,15 @@ struct Config {
     bool mp_on() const { return !echoes.empty(); }
     bool sc_on() const { return !scints.empty(); }
     bool array_on() const { return !array.empty(); }
+    bool refl_on() const { return !refls.empty(); }
+    bool azel_on() const { return array_on() || refl_on(); }  // the front-end hands out azimuth and elevation
     int n_elem() const { return array_on() ? (int)array.size() : 1; }
     bool parts_on() const { return mp_on() || sc_on(); }  // the batch goes through gal_synth_run_scint (echoes, scintillation or both)
     bool mix_on() const { return noise_on || n_jam > 0; }  // a pass over the final int16 batch in front of the format
     int agc_param() const { return iq_format == GAL_IQ_IBYTE ? iq_shift : iq_format == GAL_IQ_I2BIT ? i2bit_thr : 0; }
     // bytes of n samples in the output format: the AGC has its own count (i2bit is a format of the AGC call only)
     size_t out_bytes(size_t n) const { return agc_on ? gal_synth_agc_out_bytes(iq_format, n) : gal_synth_iq_bytes(iq_format, n); }
-    bool any_pass() const { return mix_on() || power_on || parts_on() || array_on() || fir_on() || agc_on || osc_on; }
+    bool any_pass() const { return mix_on() || power_on || parts_on() || refl_on() || array_on() || fir_on() || agc_on || osc_on; }
     // what the copies read was enqueued on the engine's stream: they wait for an event behind it
     bool chain_on_engine_stream() const { return iq_format != GAL_IQ_ISHORT || any_pass(); }
     // the run ends with the saturation report.  Not the predicate above: ibit alone clamps nothing

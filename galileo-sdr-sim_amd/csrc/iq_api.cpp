@@ -35,6 +35,9 @@ hipError_t galk_launch_iq_scint(const void *jobs_dev, int n_jobs, uint64_t max_n
 hipError_t galk_launch_iq_echo(const int16_t *const *parts_dev, const int16_t *const *hist_in_dev, int16_t *const *hist_out_dev, const int *gain_dev,
                                const void *rows_dev, const int *part_of_dev, int n_parts, int n_echo, int n_epochs, int samples_per_epoch, int wide,
                                int16_t *out, unsigned long long *sat, hipStream_t st);
+hipError_t galk_launch_iq_refl(const int16_t *const *parts_dev, const int16_t *const *hist_in_dev, int16_t *const *hist_out_dev, const int *gain_dev,
+                               const void *rows_dev, const int *part_of_dev, int n_parts, int n_echo, int n_epochs, int samples_per_epoch, int wide,
+                               int16_t *out, unsigned long long *sat, hipStream_t st);
 hipError_t galk_launch_iq_wsum(const int16_t *const *parts_dev, const int *gain_dev, int n_parts, int n_epochs, int samples_per_epoch, int wide,
                                int16_t *out, unsigned long long *sat, hipStream_t st);
 hipError_t galk_launch_iq_array(const int16_t *const *parts_dev, int16_t *const *outs_dev, const uint32_t *wts_dev, int n_parts, int n_elem,
@@ -439,15 +442,20 @@ int gal_synth_mpath_reset(gal_synth_t *h)
     return GAL_OK;
 }
 
-int gal_synth_iq_mpath(gal_synth_t *h, const int16_t *const *parts_dev, int32_t n_parts, const int32_t *hist_id, const uint16_t *gain_q7,
-                       int32_t n_epochs, const int32_t *part_of_echo, const gal_iq_echo_t *echo_rows, int32_t n_echo, int16_t *out_dev)
+// gal_synth_iq_mpath (refl false: the rows are gal_iq_echo_t, which a gal_iq_refl_t with frac_q12 = 0 equals byte for byte; k_iq_echo)
+// and gal_synth_iq_refl (refl true; k_iq_refl) over the one table and the one set of history lines of h->mp
+static int echo_pass(const char *who, bool refl, gal_synth_t *h, const int16_t *const *parts_dev, int32_t n_parts, const int32_t *hist_id,
+                     const uint16_t *gain_q7, int32_t n_epochs, const int32_t *part_of_echo, const gal_iq_refl_t *echo_rows, int32_t n_echo,
+                     int16_t *out_dev)
 {
-    const char *who = "gal_synth_iq_mpath";
+    static_assert(sizeof(gal_iq_refl_t) == sizeof(gal_iq_echo_t) && offsetof(gal_iq_refl_t, frac_q12) == offsetof(gal_iq_echo_t, reserved),
+                  "an echo row is a reflector row with frac_q12 = 0");
     if (!h) return fail(GAL_E_INVAL, "null handle");
     if (!parts_dev || !gain_q7 || n_parts < 1 || n_parts > GAL_ENGINE_MAX_CHAN || n_epochs < 1)
         return fail(GAL_E_INVAL, "%s: null argument, n_parts %d (1..%d) or n_epochs %d (>= 1)", who, n_parts, GAL_ENGINE_MAX_CHAN, n_epochs);
     GAL_TRY(check_aligned(who, out_dev));
-    int rc = gal_synth_mpath_check(echo_rows, n_echo, n_epochs, part_of_echo, n_parts);
+    int rc = refl ? gal_synth_refl_check(echo_rows, n_echo, n_epochs, part_of_echo, n_parts)
+                  : gal_synth_mpath_check((const gal_iq_echo_t *)echo_rows, n_echo, n_epochs, part_of_echo, n_parts);
     if (rc) return rc;
     const size_t bytes = (size_t)n_epochs * (size_t)h->cfg.samples_per_epoch * 4;
     GAL_TRY(check_parts(who, h, parts_dev, n_parts, out_dev, bytes));
@@ -509,12 +517,103 @@ int gal_synth_iq_mpath(gal_synth_t *h, const int16_t *const *parts_dev, int32_t 
         memcpy(h->mp.table.host + o_pof, part_of_echo, sizeof(int) * (size_t)n_echo);
     }
     HIP_TRY(hipMemcpyAsync(h->mp.table.dev, h->mp.table.host, need, hipMemcpyHostToDevice, st));
-    HIP_TRY(galk_launch_iq_echo((const int16_t *const *)h->mp.table.dev, (const int16_t *const *)(h->mp.table.dev + o_hin), (int16_t *const *)(h->mp.table.dev + o_hout),
-                                (const int *)(h->mp.table.dev + o_gain), h->mp.table.dev + o_rows, (const int *)(h->mp.table.dev + o_pof), n_parts, n_echo, n_epochs,
-                                h->cfg.samples_per_epoch, row_max > 65535 ? 1 : 0, out_dev, h->d_iq_sat, st));
+    const auto launch = refl ? galk_launch_iq_refl : galk_launch_iq_echo;
+    HIP_TRY(launch((const int16_t *const *)h->mp.table.dev, (const int16_t *const *)(h->mp.table.dev + o_hin), (int16_t *const *)(h->mp.table.dev + o_hout),
+                   (const int *)(h->mp.table.dev + o_gain), h->mp.table.dev + o_rows, (const int *)(h->mp.table.dev + o_pof), n_parts, n_echo, n_epochs,
+                   h->cfg.samples_per_epoch, row_max > 65535 ? 1 : 0, out_dev, h->d_iq_sat, st));
     for (int k = 0; k < n_parts; ++k)
         if (id[k] >= 0) h->mp.cur[id[k]] ^= 1;
     HIP_TRY(h->mp.sync.mark(st));
+    return GAL_OK;
+}
+
+int gal_synth_iq_mpath(gal_synth_t *h, const int16_t *const *parts_dev, int32_t n_parts, const int32_t *hist_id, const uint16_t *gain_q7,
+                       int32_t n_epochs, const int32_t *part_of_echo, const gal_iq_echo_t *echo_rows, int32_t n_echo, int16_t *out_dev)
+{
+    return echo_pass("gal_synth_iq_mpath", false, h, parts_dev, n_parts, hist_id, gain_q7, n_epochs, part_of_echo, (const gal_iq_refl_t *)echo_rows,
+                     n_echo, out_dev);
+}
+
+// ---- geometric reflectors (iq_refl.hip) ---------------------------------------------------------------------------------------------
+int gal_synth_refl_check(const gal_iq_refl_t *refl_rows, int32_t n_echo, int32_t n_epochs, const int32_t *part_of_echo, int32_t n_parts)
+{
+    const char *who = "gal_synth_refl_check";
+    if (n_echo < 0 || n_echo > GAL_ECHO_MAX) return fail(GAL_E_INVAL, "%s: %d echoes (0..%d)", who, n_echo, GAL_ECHO_MAX);
+    if (n_epochs < 1 || n_parts < 1 || n_parts > GAL_ENGINE_MAX_CHAN)
+        return fail(GAL_E_INVAL, "%s: n_epochs %d (>= 1) or n_parts %d (1..%d)", who, n_epochs, n_parts, GAL_ENGINE_MAX_CHAN);
+    if (n_echo == 0) return GAL_OK;
+    if (!refl_rows || !part_of_echo) return fail(GAL_E_INVAL, "%s: null argument", who);
+    for (int r = 0; r < n_echo; ++r)
+        if (part_of_echo[r] < 0 || part_of_echo[r] >= n_parts)
+            return fail(GAL_E_INVAL, "%s: echo %d on part %d (0..%d)", who, r, part_of_echo[r], n_parts - 1);
+    for (int e = 0; e < n_epochs; ++e)
+        for (int r = 0; r < n_echo; ++r) {
+            const gal_iq_refl_t &q = refl_rows[(size_t)e * n_echo + r];
+            if (q.gain_q7 > GAL_GAIN_MAX) return fail(GAL_E_INVAL, "%s: gain %u of epoch %d, echo %d (0..%d)", who, q.gain_q7, e, r, GAL_GAIN_MAX);
+            if (q.frac_q12 > 4095) return fail(GAL_E_INVAL, "%s: frac_q12 %u of epoch %d, echo %d (0..4095)", who, q.frac_q12, e, r);
+            if (q.delay + (q.frac_q12 > 0 ? 1 : 0) > GAL_ECHO_MAX_DELAY)
+                return fail(GAL_E_INVAL, "%s: delay %u + %u/4096 of epoch %d, echo %d (the oldest sample read may lie %d samples back)", who, q.delay,
+                            q.frac_q12, e, r, GAL_ECHO_MAX_DELAY);
+            if (q.reserved != 0) return fail(GAL_E_INVAL, "%s: reserved = %u in epoch %d, echo %d (must be 0)", who, q.reserved, e, r);
+        }
+    return GAL_OK;
+}
+
+int gal_synth_iq_refl(gal_synth_t *h, const int16_t *const *parts_dev, int32_t n_parts, const int32_t *hist_id, const uint16_t *gain_q7,
+                      int32_t n_epochs, const int32_t *part_of_echo, const gal_iq_refl_t *refl_rows, int32_t n_echo, int16_t *out_dev)
+{
+    return echo_pass("gal_synth_iq_refl", true, h, parts_dev, n_parts, hist_id, gain_q7, n_epochs, part_of_echo, refl_rows, n_echo, out_dev);
+}
+
+int gal_synth_refl_geom(int32_t kind, const double *p, double az_rad, double el_rad, double *excess_m)
+{
+    const char *who = "gal_synth_refl_geom";
+    if (!p || !excess_m) return fail(GAL_E_INVAL, "%s: null argument", who);
+    if (kind != GAL_REFL_GROUND && kind != GAL_REFL_WALL) return fail(GAL_E_INVAL, "%s: kind %d (GAL_REFL_GROUND, GAL_REFL_WALL)", who, kind);
+    if (!std::isfinite(az_rad) || !std::isfinite(el_rad) || !std::isfinite(p[0]) || p[0] < 0.0 || (kind == GAL_REFL_WALL && !std::isfinite(p[1])))
+        return fail(GAL_E_INVAL, "%s: the angles and the plane must be finite, its height or distance %g m >= 0", who, p[0]);
+    if (kind == GAL_REFL_GROUND) {
+        *excess_m = el_rad > 0.0 ? 2.0 * p[0] * sin(el_rad) : -1.0;
+    } else {
+        const double x = -2.0 * p[0] * cos(el_rad) * cos(az_rad - p[1]);
+        *excess_m = x > 0.0 ? x : -1.0;
+    }
+    return GAL_OK;
+}
+
+// P(x) of include/galsynth.h: the carrier phase of an echo with the excess path x, in 2^-32 cycles
+static uint32_t refl_phase(double excess_m, double refl_phase_deg)
+{
+    const double lambda = 299792458.0 / 1575420000.0;
+    const double cyc = -excess_m / lambda + refl_phase_deg / 360.0;
+    return (uint32_t)(llround((cyc - floor(cyc)) * 4294967296.0) & 0xffffffffll);
+}
+
+int gal_synth_refl_row(double excess_now_m, double excess_next_m, double rel_db, double refl_phase_deg, double sample_rate,
+                       int32_t samples_per_epoch, uint16_t slot_gain_q7, gal_iq_refl_t *row)
+{
+    const char *who = "gal_synth_refl_row";
+    if (!row) return fail(GAL_E_INVAL, "%s: null argument", who);
+    if (!std::isfinite(excess_now_m) || !std::isfinite(excess_next_m) || !std::isfinite(rel_db) || !std::isfinite(refl_phase_deg) ||
+        !std::isfinite(sample_rate) || sample_rate <= 0.0 || samples_per_epoch < 1 || slot_gain_q7 > GAL_GAIN_MAX)
+        return fail(GAL_E_INVAL, "%s: the paths %g and %g m, %g dB, %g deg and the rate %g Hz (> 0) must be finite, samples_per_epoch %d >= 1, gain %u in 0..%d",
+                    who, excess_now_m, excess_next_m, rel_db, refl_phase_deg, sample_rate, samples_per_epoch, slot_gain_q7, GAL_GAIN_MAX);
+    const double alpha = 4096.0 * pow(10.0, rel_db / 20.0);
+    if (!(alpha <= 8192.0)) return fail(GAL_E_INVAL, "%s: %g dB is an amplitude of %g, more than 2 (+6.02 dB)", who, rel_db, alpha / 4096.0);
+    memset(row, 0, sizeof(*row));
+    if (excess_now_m < 0.0) return GAL_OK;  // no echo in this epoch
+    const double t = excess_now_m / 299792458.0 * sample_rate;
+    if (!(t < GAL_ECHO_MAX_DELAY + 1.0)) return fail(GAL_E_INVAL, "%s: a delay of %g samples, more than %d", who, t, GAL_ECHO_MAX_DELAY);
+    long long D = (long long)floor(t), F = llround((t - (double)D) * 4096.0);
+    if (F == 4096) D += 1, F = 0;
+    if (D + (F > 0 ? 1 : 0) > GAL_ECHO_MAX_DELAY) return fail(GAL_E_INVAL, "%s: a delay of %g samples, more than %d", who, t, GAL_ECHO_MAX_DELAY);
+    const uint32_t A = ((uint32_t)slot_gain_q7 * (uint32_t)llround(alpha) + 2048u) >> 12;
+    row->gain_q7 = (uint16_t)std::min<uint32_t>(A, GAL_GAIN_MAX);
+    row->delay = (uint16_t)D;
+    row->frac_q12 = (uint16_t)F;
+    row->ph0 = refl_phase(excess_now_m, refl_phase_deg);
+    if (excess_next_m >= 0.0)
+        row->dph = (int32_t)llround((double)(int32_t)(refl_phase(excess_next_m, refl_phase_deg) - row->ph0) / (double)samples_per_epoch);
     return GAL_OK;
 }
 
@@ -1231,12 +1330,14 @@ struct ArrayRun {
     int16_t *const *out_dev;
 };
 
-// gal_synth_run_gains (n_echo = 0), gal_synth_run_mpath, gal_synth_run_scint (scint_rows != null) and gal_synth_run_array (arr != null,
-// iq_dev = its first output): the slot groups, one synthesis run per group, the scintillation of the parts that have one, then the
-// weighted sum, the echo pass or the array pass
+// gal_synth_run_gains (n_echo = 0), gal_synth_run_mpath, gal_synth_run_refl (refl_rows != null in the place of echo_rows),
+// gal_synth_run_scint (scint_rows != null) and gal_synth_run_array (arr != null, iq_dev = its first output): the slot groups, one
+// synthesis run per group, the scintillation of the parts that have one, then the weighted sum, the echo or reflector pass or the
+// array pass
 static int run_groups(const char *who, gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_epochs, const gal_chan_state_t *state_in,
                       const uint16_t *gain_q7, const int32_t *slot_of_echo, const gal_iq_echo_t *echo_rows, int32_t n_echo, int16_t *iq_dev,
-                      gal_chan_state_t *state_out, const gal_iq_scint_t *scint_rows = nullptr, uint64_t first_sample = 0, const ArrayRun *arr = nullptr)
+                      gal_chan_state_t *state_out, const gal_iq_scint_t *scint_rows = nullptr, uint64_t first_sample = 0, const ArrayRun *arr = nullptr,
+                      const gal_iq_refl_t *refl_rows = nullptr)
 {
     if (!h || !params || !gain_q7 || !iq_dev || n_epochs < 1) return fail(GAL_E_INVAL, "%s: null argument or n_epochs %d (>= 1)", who, n_epochs);
     if ((uintptr_t)iq_dev & 15) return fail(GAL_E_INVAL, "%s: iq_dev must be 16-byte aligned", who);
@@ -1397,7 +1498,8 @@ static int run_groups(const char *who, gal_synth_t *h, const gal_chan_epoch_t *p
             for (int k = 0; k < n_parts; ++k)
                 if (groups[k].solo && has_echo[groups[k].slots[0]]) hist_id[k] = groups[k].slots[0];
             for (int r = 0; r < n_echo; ++r) part_of[r] = group_of[slot_of_echo[r]];
-            rc = gal_synth_iq_mpath(h, parts, n_parts, hist_id.data(), gp.data(), E, part_of.data(), echo_rows, n_echo, iq_dev);
+            rc = refl_rows ? gal_synth_iq_refl(h, parts, n_parts, hist_id.data(), gp.data(), E, part_of.data(), refl_rows, n_echo, iq_dev)
+                           : gal_synth_iq_mpath(h, parts, n_parts, hist_id.data(), gp.data(), E, part_of.data(), echo_rows, n_echo, iq_dev);
         } else {
             rc = gal_synth_iq_wsum(h, parts, n_parts, gp.data(), E, iq_dev);
         }
@@ -1424,6 +1526,18 @@ int gal_synth_run_mpath(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t 
     const int rc = gal_synth_mpath_check(echo_rows, n_echo, n_epochs, slot_of_echo, h->cfg.n_slots);
     if (rc) return rc;
     return run_groups(who, h, params, n_epochs, state_in, gain_q7, slot_of_echo, echo_rows, n_echo, iq_dev, state_out);
+}
+
+int gal_synth_run_refl(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_epochs, const gal_chan_state_t *state_in,
+                       const uint16_t *gain_q7, const int32_t *slot_of_echo, const gal_iq_refl_t *refl_rows, int32_t n_echo, int16_t *iq_dev,
+                       gal_chan_state_t *state_out)
+{
+    const char *who = "gal_synth_run_refl";
+    if (n_echo == 0) return run_groups(who, h, params, n_epochs, state_in, gain_q7, nullptr, nullptr, 0, iq_dev, state_out);
+    if (!h) return fail(GAL_E_INVAL, "%s: null handle", who);
+    if (h->cfg.n_slots > GAL_ECHO_LINES) return fail(GAL_E_INVAL, "%s: %d slots, more than the %d history lines", who, h->cfg.n_slots, GAL_ECHO_LINES);
+    GAL_TRY(gal_synth_refl_check(refl_rows, n_echo, n_epochs, slot_of_echo, h->cfg.n_slots));
+    return run_groups(who, h, params, n_epochs, state_in, gain_q7, slot_of_echo, nullptr, n_echo, iq_dev, state_out, nullptr, 0, nullptr, refl_rows);
 }
 
 int gal_synth_run_scint(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_epochs, const gal_chan_state_t *state_in,

@@ -100,6 +100,18 @@ __device__ __forceinline__ const int16_t *load_cos_table()
     __syncthreads();
     return (const int16_t *)cw;
 }
+
+// echoes (iq_echo.hip, iq_refl.hip): the complex value (uI, uQ), |u| <= 32768 per rail, turned by the table phase `ph` and scaled by A,
+// added to (wI, wQ).  |uI c - uQ s| <= 2 x 32768 x 4096 = 2^28: the products before the shift fit an int32, |r| <= 65536
+template <class acc_t>
+__device__ __forceinline__ void mac_rot(acc_t &wI, acc_t &wQ, int uI, int uQ, uint32_t ph, int A, const int16_t *cosl)
+{
+    const uint32_t i = ph >> 22;
+    const int c = cosl[i], s = cosl[(i - 256u) & 1023u];
+    const int rI = (uI * c - uQ * s + 2048) >> 12, rQ = (uI * s + uQ * c + 2048) >> 12;
+    wI += (acc_t)A * (acc_t)rI;
+    wQ += (acc_t)A * (acc_t)rQ;
+}
 #endif
 
 // ---- the formats' values -------------------------------------------------------------------------------------------------------

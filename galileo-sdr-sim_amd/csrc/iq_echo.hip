@@ -49,12 +49,7 @@ static_assert(sizeof(EchoRow) == sizeof(gal_iq_echo_t), "the kernel reads gal_iq
 template <class acc_t>
 __device__ __forceinline__ void mac_echo(acc_t &wI, acc_t &wQ, int u, uint32_t ph, int A, const int16_t *cosl)
 {
-    const uint32_t i = ph >> 22;
-    const int c = cosl[i], s = cosl[(i - 256u) & 1023u];
-    const int uI = (int16_t)u, uQ = u >> 16;
-    const int rI = (uI * c - uQ * s + 2048) >> 12, rQ = (uI * s + uQ * c + 2048) >> 12;
-    wI += (acc_t)A * (acc_t)rI;
-    wQ += (acc_t)A * (acc_t)rQ;
+    mac_rot(wI, wQ, (int)(int16_t)u, u >> 16, ph, A, cosl);
 }
 
 // parts[k]: n_epochs * N complex samples, 16-byte aligned, none overlapping `out`; hist[k]: the kHist samples in front of part k (null
@@ -165,6 +160,14 @@ __global__ __launch_bounds__(kThreads) void k_echo_hist(const int16_t *const *__
 
 }  // namespace
 
+// the new history lines after a call of n complex samples (k_echo_hist): what galk_launch_iq_echo and galk_launch_iq_refl (iq_refl.hip) end with
+extern "C" hipError_t galk_launch_echo_hist(const int16_t *const *parts_dev, const int16_t *const *hist_in_dev, int16_t *const *hist_out_dev,
+                                            int n_parts, uint64_t n, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_echo_hist, dim3((unsigned)n_parts), dim3(kThreads), 0, st, parts_dev, hist_in_dev, hist_out_dev, n);
+    return hipGetLastError();
+}
+
 // tab_dev: the call's device table -- n_parts part pointers, hist_in and hist_out pointers at [GAL_ENGINE_MAX_CHAN] each (in that
 // order), then the gains [n_epochs][n_parts] int32, the echo rows [n_epochs][n_echo] and part_of_echo [n_echo] at the given pointers.
 // wide != 0: the int64 instance.  Arguments are checked by the caller (iq_api.cpp: gal_synth_iq_mpath).
@@ -183,7 +186,5 @@ extern "C" hipError_t galk_launch_iq_echo(const int16_t *const *parts_dev, const
                            part_of_dev, n_parts, n_echo, n_epochs, (uint32_t)samples_per_epoch, out, sat);
     hipError_t rc = hipGetLastError();
     if (rc != hipSuccess) return rc;
-    hipLaunchKernelGGL(k_echo_hist, dim3((unsigned)n_parts), dim3(kThreads), 0, st, parts_dev, hist_in_dev, hist_out_dev,
-                       (uint64_t)n_epochs * (uint64_t)samples_per_epoch);
-    return hipGetLastError();
+    return galk_launch_echo_hist(parts_dev, hist_in_dev, hist_out_dev, n_parts, (uint64_t)n_epochs * (uint64_t)samples_per_epoch, st);
 }

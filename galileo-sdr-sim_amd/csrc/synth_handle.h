@@ -179,8 +179,8 @@ struct GainStage {
     }
 };
 
-// gal_synth_iq_mpath (iq_echo.hip): d_hist = GAL_ECHO_LINES history lines x 2 buffers of GAL_ECHO_MAX_DELAY complex samples (a call
-// reads buffer cur[id] of a line it names and writes the other); table = the table of the last call (part, history-in and history-out
+// gal_synth_iq_mpath (iq_echo.hip) and gal_synth_iq_refl (iq_refl.hip), which share all of it: d_hist = GAL_ECHO_LINES history lines
+// x 2 buffers of GAL_ECHO_MAX_DELAY complex samples (a call reads buffer cur[id] of a line it names and writes the other); table = the table of the last call (part, history-in and history-out
 // pointers, gains, echo rows, part indices), pinned on the host and on the device; sync = that call's kernels are done
 struct MpathStage {
     uint32_t *d_hist = nullptr;

@@ -226,6 +226,25 @@ GAL_ECHO_MAX_DELAY = 1024
 GAL_ECHO_LINES = 64
 
 
+class _Refl(ctypes.Structure):  # gal_iq_refl_t (16 bytes)
+    _fields_ = [
+        ("gain_q7", ctypes.c_uint16),
+        ("delay", ctypes.c_uint16),
+        ("ph0", ctypes.c_uint32),
+        ("dph", ctypes.c_int32),
+        ("frac_q12", ctypes.c_uint16),
+        ("reserved", ctypes.c_uint16),
+    ]
+
+
+assert ctypes.sizeof(_Refl) == 16
+# one row of a reflector table: refl_rows are arrays of this type, [n_epochs, n_echo]; with frac_q12 = 0 its bytes are an ECHO_DTYPE row
+REFL_DTYPE = np.dtype([("gain_q7", "<u2"), ("delay", "<u2"), ("ph0", "<u4"), ("dph", "<i4"), ("frac_q12", "<u2"), ("reserved", "<u2")])
+assert REFL_DTYPE.itemsize == 16
+GAL_REFL_GROUND = 0
+GAL_REFL_WALL = 1
+
+
 class _MpathEcho(ctypes.Structure):  # gal_mpath_echo_t (16 bytes)
     _fields_ = [("delay", ctypes.c_uint32), ("alpha_q12", ctypes.c_uint32), ("ph0", ctypes.c_uint32), ("dph", ctypes.c_int32)]
 
@@ -298,6 +317,11 @@ EXPORTED_SYMBOLS = (
     "gal_synth_run_mpath",
     "gal_synth_mpath_make",
     "gal_synth_mpath_row",
+    "gal_synth_refl_check",
+    "gal_synth_iq_refl",
+    "gal_synth_run_refl",
+    "gal_synth_refl_geom",
+    "gal_synth_refl_row",
     "gal_synth_fir_check",
     "gal_synth_fir_lowpass",
     "gal_synth_fir_set",
@@ -416,6 +440,16 @@ def load_library(hooks=False):
     lib.gal_synth_mpath_make.restype = ctypes.c_int
     lib.gal_synth_mpath_row.argtypes = [ctypes.POINTER(_MpathEcho), ctypes.c_uint16, ctypes.c_uint64, i32, ctypes.POINTER(_Echo)]
     lib.gal_synth_mpath_row.restype = ctypes.c_int
+    lib.gal_synth_refl_check.argtypes = [vp, i32, i32, vp, i32]
+    lib.gal_synth_refl_check.restype = ctypes.c_int
+    lib.gal_synth_iq_refl.argtypes = [vp, ctypes.POINTER(vp), i32, vp, vp, i32, vp, vp, i32, vp]
+    lib.gal_synth_iq_refl.restype = ctypes.c_int
+    lib.gal_synth_run_refl.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp]
+    lib.gal_synth_run_refl.restype = ctypes.c_int
+    lib.gal_synth_refl_geom.argtypes = [i32, ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_double)]
+    lib.gal_synth_refl_geom.restype = ctypes.c_int
+    lib.gal_synth_refl_row.argtypes = [ctypes.c_double] * 5 + [i32, ctypes.c_uint16, ctypes.POINTER(_Refl)]
+    lib.gal_synth_refl_row.restype = ctypes.c_int
     lib.gal_synth_fir_check.argtypes = [vp, i32]
     lib.gal_synth_fir_check.restype = ctypes.c_int
     lib.gal_synth_fir_lowpass.argtypes = [ctypes.c_double, ctypes.c_double, i32, vp]
@@ -842,11 +876,11 @@ def array_phase(enu_m, az_rad, el_rad):
     return int(ph.value)
 
 
-def _echo_table(echo_rows, n_epochs, who):
-    """echo_rows -> a contiguous ECHO_DTYPE array [n_epochs, n_echo] (None or an empty one: no echoes)."""
+def _echo_table(echo_rows, n_epochs, who, dtype=ECHO_DTYPE):
+    """echo_rows -> a contiguous ECHO_DTYPE (REFL_DTYPE) array [n_epochs, n_echo] (None or an empty one: no echoes)."""
     if echo_rows is None:
-        return np.zeros((n_epochs, 0), dtype=ECHO_DTYPE)
-    r = np.ascontiguousarray(echo_rows, dtype=ECHO_DTYPE)
+        return np.zeros((n_epochs, 0), dtype=dtype)
+    r = np.ascontiguousarray(echo_rows, dtype=dtype)
     if r.ndim != 2 or r.shape[0] != n_epochs:
         raise ValueError("%s: echo_rows must have shape [n_epochs=%d, n_echo]" % (who, n_epochs))
     return r
@@ -894,6 +928,48 @@ def mpath_rows(echo, slot_gain_q7, first_epoch, samples_per_epoch):
             raise GalSynthError(rc, lib.gal_synth_last_error().decode())
         out[e] = (row.gain_q7, row.delay, row.ph0, row.dph, row.reserved)
     return out
+
+
+def refl_check(refl_rows, part_of_echo, n_parts):
+    """gal_synth_refl_check (no GPU needed): raises GalSynthError(GAL_E_INVAL) for a reflector table [n_epochs, n_echo] (REFL_DTYPE) or
+    part indices that the reflector pass would refuse."""
+    lib = load_library()
+    r = np.ascontiguousarray(refl_rows, dtype=REFL_DTYPE)
+    if r.ndim != 2:
+        raise ValueError("refl_check: refl_rows must have shape [n_epochs, n_echo]")
+    pof = np.ascontiguousarray(part_of_echo, dtype=np.int32)
+    if pof.shape != (r.shape[1],):
+        raise ValueError("refl_check: part_of_echo must have n_echo = %d entries" % r.shape[1])
+    rc = lib.gal_synth_refl_check(r.ctypes.data, r.shape[1], r.shape[0], pof.ctypes.data, int(n_parts))
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+
+
+def refl_geom(kind, p, az_rad, el_rad):
+    """gal_synth_refl_geom (no GPU needed): the excess path in metres of the reflection off a plane -- kind GAL_REFL_GROUND with
+    p = (height,), GAL_REFL_WALL with p = (distance, azimuth of the wall in rad) -- for a satellite at (az_rad, el_rad); -1.0 where the
+    geometry gives no echo."""
+    lib = load_library()
+    v = (ctypes.c_double * 2)(*([float(x) for x in p] + [0.0, 0.0])[:2])
+    x = ctypes.c_double()
+    rc = lib.gal_synth_refl_geom(int(kind), v, float(az_rad), float(el_rad), ctypes.byref(x))
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+    return float(x.value)
+
+
+def refl_row(excess_now_m, excess_next_m, rel_db, refl_phase_deg=180.0, sample_rate=2.6e6, samples_per_epoch=260000, slot_gain_q7=128):
+    """gal_synth_refl_row (no GPU needed): the row (a REFL_DTYPE scalar) of one epoch from the excess path at its start and at the next
+    epoch's; a negative excess_now_m (no echo) gives the zero row."""
+    lib = load_library()
+    if not 0 <= int(slot_gain_q7) <= 65535:
+        raise ValueError("refl_row: the gain does not fit a uint16")
+    row = _Refl()
+    rc = lib.gal_synth_refl_row(float(excess_now_m), float(excess_next_m), float(rel_db), float(refl_phase_deg), float(sample_rate),
+                                int(samples_per_epoch), int(slot_gain_q7), ctypes.byref(row))
+    if rc != 0:
+        raise GalSynthError(rc, lib.gal_synth_last_error().decode())
+    return np.array((row.gain_q7, row.delay, row.ph0, row.dph, row.frac_q12, row.reserved), dtype=REFL_DTYPE)
 
 
 def _corr_struct(req):
@@ -1124,23 +1200,32 @@ class SynthEngine:
         parts part_of_echo [n_echo].  hist_id: per part the history line (0 .. 63) that carries its last 1024 samples from call to call,
         -1 for none; None names line k for part k.  Any cut of a stream into calls of whole epochs gives the same bytes.
         iq_saturated() is the fence and counts the clamped values."""
+        self._echo_pass("iq_mpath", self._lib.gal_synth_iq_mpath, ECHO_DTYPE, part_ptrs, gain_q7, out_ptr, part_of_echo, echo_rows, hist_id)
+
+    def iq_refl(self, part_ptrs, gain_q7, out_ptr, part_of_echo=(), refl_rows=None, hist_id=None):
+        """gal_synth_iq_refl, enqueued on the handle's stream: iq_mpath with rows of REFL_DTYPE, whose frac_q12 adds a fraction of a
+        sample to the delay (linear interpolation between two samples).  The history lines are iq_mpath's."""
+        self._echo_pass("iq_refl", self._lib.gal_synth_iq_refl, REFL_DTYPE, part_ptrs, gain_q7, out_ptr, part_of_echo, refl_rows, hist_id)
+
+    def _echo_pass(self, who, fn, dtype, part_ptrs, gain_q7, out_ptr, part_of_echo, echo_rows, hist_id):
+        """iq_mpath and iq_refl: `fn` over rows of `dtype`."""
         g = np.asarray(gain_q7)
         if g.ndim != 2 or g.shape[1] != len(part_ptrs):
-            raise ValueError("iq_mpath: gain_q7 must have shape [n_epochs, n_parts=%d]" % len(part_ptrs))
+            raise ValueError("%s: gain_q7 must have shape [n_epochs, n_parts=%d]" % (who, len(part_ptrs)))
         if g.size and (g.min() < 0 or g.max() > 65535):
-            raise ValueError("iq_mpath: a gain does not fit a uint16")
+            raise ValueError("%s: a gain does not fit a uint16" % who)
         g = np.ascontiguousarray(g, dtype=np.uint16)
-        rows = _echo_table(echo_rows, g.shape[0], "iq_mpath")
+        rows = _echo_table(echo_rows, g.shape[0], who, dtype)
         pof = np.ascontiguousarray(part_of_echo, dtype=np.int32).ravel()
         if pof.size != rows.shape[1]:
-            raise ValueError("iq_mpath: part_of_echo must have n_echo = %d entries" % rows.shape[1])
+            raise ValueError("%s: part_of_echo must have n_echo = %d entries" % (who, rows.shape[1]))
         hid = None if hist_id is None else np.ascontiguousarray(hist_id, dtype=np.int32).ravel()
         if hid is not None and hid.size != len(part_ptrs):
-            raise ValueError("iq_mpath: hist_id must have n_parts = %d entries" % len(part_ptrs))
+            raise ValueError("%s: hist_id must have n_parts = %d entries" % (who, len(part_ptrs)))
         ptrs = (ctypes.c_void_p * max(1, len(part_ptrs)))(*[int(p) for p in part_ptrs])
-        self._check(self._lib.gal_synth_iq_mpath(self._h, ptrs, len(part_ptrs), hid.ctypes.data if hid is not None else None, g.ctypes.data,
-                                                 g.shape[0], pof.ctypes.data if pof.size else None, rows.ctypes.data if rows.size else None,
-                                                 rows.shape[1], ctypes.c_void_p(int(out_ptr))))
+        self._check(fn(self._h, ptrs, len(part_ptrs), hid.ctypes.data if hid is not None else None, g.ctypes.data, g.shape[0],
+                       pof.ctypes.data if pof.size else None, rows.ctypes.data if rows.size else None, rows.shape[1],
+                       ctypes.c_void_p(int(out_ptr))))
 
     def mpath_reset(self):
         """gal_synth_mpath_reset: zero every history line of iq_mpath / run_mpath (enqueued): the next call starts its streams."""
@@ -1150,22 +1235,30 @@ class SynthEngine:
         """gal_synth_run_mpath: run_gains with the echoes echo_rows [n_epochs, n_echo] (ECHO_DTYPE) of the channel slots slot_of_echo
         [n_echo] -- every such slot is a synthesis run of its own, and its history follows the slot from batch to batch.  No echoes:
         run_gains.  The echo pass is ENQUEUED when this returns (iq_saturated() is the fence).  Returns state_out."""
+        return self._run_echo("run_mpath", self._lib.gal_synth_run_mpath, ECHO_DTYPE, params, gain_q7, iq_dev_ptr, slot_of_echo, echo_rows, state_in)
+
+    def run_refl(self, params, gain_q7, iq_dev_ptr, slot_of_echo=(), refl_rows=None, state_in=None):
+        """gal_synth_run_refl: run_mpath with rows of REFL_DTYPE and the reflector pass in the place of the echo pass.  Returns state_out."""
+        return self._run_echo("run_refl", self._lib.gal_synth_run_refl, REFL_DTYPE, params, gain_q7, iq_dev_ptr, slot_of_echo, refl_rows, state_in)
+
+    def _run_echo(self, who, fn, dtype, params, gain_q7, iq_dev_ptr, slot_of_echo, echo_rows, state_in):
+        """run_mpath and run_refl: `fn` over rows of `dtype`."""
         p = self._params(params)
         s = self._state(state_in)
         g = np.asarray(gain_q7)
         if g.shape != p.shape:
-            raise ValueError("run_mpath: gain_q7 must have shape [n_epochs, n_slots=%d]" % self.n_slots)
+            raise ValueError("%s: gain_q7 must have shape [n_epochs, n_slots=%d]" % (who, self.n_slots))
         if g.size and (g.min() < 0 or g.max() > 65535):
-            raise ValueError("run_mpath: a gain does not fit a uint16")
+            raise ValueError("%s: a gain does not fit a uint16" % who)
         g = np.ascontiguousarray(g, dtype=np.uint16)
-        rows = _echo_table(echo_rows, p.shape[0], "run_mpath")
+        rows = _echo_table(echo_rows, p.shape[0], who, dtype)
         sof = np.ascontiguousarray(slot_of_echo, dtype=np.int32).ravel()
         if sof.size != rows.shape[1]:
-            raise ValueError("run_mpath: slot_of_echo must have n_echo = %d entries" % rows.shape[1])
+            raise ValueError("%s: slot_of_echo must have n_echo = %d entries" % (who, rows.shape[1]))
         st = np.zeros(self.n_slots, dtype=CHAN_STATE_DTYPE)
-        self._check(self._lib.gal_synth_run_mpath(self._h, p.ctypes.data, p.shape[0], s.ctypes.data if s is not None else None, g.ctypes.data,
-                                                  sof.ctypes.data if sof.size else None, rows.ctypes.data if rows.size else None, rows.shape[1],
-                                                  ctypes.c_void_p(int(iq_dev_ptr)), st.ctypes.data))
+        self._check(fn(self._h, p.ctypes.data, p.shape[0], s.ctypes.data if s is not None else None, g.ctypes.data,
+                       sof.ctypes.data if sof.size else None, rows.ctypes.data if rows.size else None, rows.shape[1],
+                       ctypes.c_void_p(int(iq_dev_ptr)), st.ctypes.data))
         self.n_epochs = p.shape[0]
         return st
 

@@ -764,6 +764,73 @@ int gal_synth_mpath_make(double delay_s, double rel_db, double phase_deg, double
 int gal_synth_mpath_row(const gal_mpath_echo_t *echo, uint16_t slot_gain_q7, uint64_t epoch, int32_t samples_per_epoch, gal_iq_echo_t *row);
 
 /*
+ * Geometric reflectors (not in the reference): the echo pass above with a delay of D + F / 4096 samples, and the
+ * geometry that fills its rows from the satellite's azimuth and elevation -- a ground bounce, a wall --, so that an echo's delay, its
+ * carrier phase and the rate at which that phase turns all follow from ONE excess path.  A FIXED INTEGER FUNCTION of its inputs
+ * (tests/refl_model.py states it in numpy).
+ *
+ * Everything is as for gal_synth_iq_mpath but the row, gal_iq_refl_t, which carries F = frac_q12 (0 .. 4095) as well, and the delayed
+ * value: for the output sample n, with the row of the OUTPUT sample's epoch,
+ *   a = x_p[n - D],  b = x_p[n - D - 1]                    (history as for gal_synth_iq_mpath)
+ *   u = a + ((F (b - a) + 2048) >> 12)                     (per rail, arithmetic shift; with F = 0, u = a and b is not read)
+ * and u takes the place of x_p[n - D] in the rotation, the sum, the rounding, the clamp and the saturation count.  u lies between a
+ * and b inclusive, so |u| <= 32768 and the int32 / int64 rule (sum_k g + 2 sum_r A <= 65535) is unchanged; |F (b - a)| < 2^28.
+ * Range: D + (F > 0 ? 1 : 0) <= GAL_ECHO_MAX_DELAY -- D = 1024 only with F = 0.  With F = 0 in every row the output is
+ * gal_synth_iq_mpath bit for bit (such a row IS a gal_iq_echo_t), with n_echo = 0 gal_synth_iq_wsum.  Linear interpolation because
+ * the synthesised chips are rectangular and sample-held: the correlation of such a stream with the code is piecewise linear between
+ * whole-sample lags, and a two-tap interpolation moves it by exactly the fraction.
+ *
+ * The pass shares the handle's GAL_ECHO_LINES history lines with gal_synth_iq_mpath: the same hist_id rules, the same "any cut into
+ * calls of whole epochs gives the bytes of one call", also where calls of the two passes alternate on one handle;
+ * gal_synth_mpath_reset zeroes the lines for both.
+ */
+typedef struct gal_iq_refl {
+    uint16_t gain_q7;   /* A: 0 .. GAL_GAIN_MAX, 128 = the part at unity                                                       */
+    uint16_t delay;     /* D: whole samples, 0 .. GAL_ECHO_MAX_DELAY (GAL_ECHO_MAX_DELAY - 1 where frac_q12 > 0)               */
+    uint32_t ph0;       /* phase at the epoch's first sample, 2^-32 cycles                                                     */
+    int32_t  dph;       /* phase step per sample, 2^-32 cycles                                                                 */
+    uint16_t frac_q12;  /* F: the delay's fraction in 1/4096 sample, 0 .. 4095                                                 */
+    uint16_t reserved;  /* 0                                                                                                   */
+} gal_iq_refl_t;        /* 16 bytes */
+/* gal_synth_mpath_check for rows of gal_iq_refl_t: it refuses what that refuses, frac_q12 > 4095 and a delay of GAL_ECHO_MAX_DELAY
+ * with frac_q12 > 0.  Host only, needs no GPU. */
+int gal_synth_refl_check(const gal_iq_refl_t *refl_rows, int32_t n_echo, int32_t n_epochs, const int32_t *part_of_echo, int32_t n_parts);
+/* gal_synth_iq_mpath with rows of gal_iq_refl_t: the same arguments, rules, history lines and refusals (gal_synth_refl_check in the
+ * place of gal_synth_mpath_check). */
+int gal_synth_iq_refl(gal_synth_t *h, const int16_t *const *parts_dev, int32_t n_parts, const int32_t *hist_id, const uint16_t *gain_q7,
+                      int32_t n_epochs, const int32_t *part_of_echo, const gal_iq_refl_t *refl_rows, int32_t n_echo, int16_t *out_dev);
+/* gal_synth_run_mpath with rows of gal_iq_refl_t and gal_synth_iq_refl in the place of gal_synth_iq_mpath: every slot with an echo is
+ * a group of its own, its history line is its slot index, n_echo = 0 is gal_synth_run_gains, gal_synth_gain_runs counts the runs. */
+int gal_synth_run_refl(gal_synth_t *h, const gal_chan_epoch_t *params, int32_t n_epochs, const gal_chan_state_t *state_in,
+                       const uint16_t *gain_q7, const int32_t *slot_of_echo, const gal_iq_refl_t *refl_rows, int32_t n_echo,
+                       int16_t *iq_dev, gal_chan_state_t *state_out);
+/* The excess path, in metres, of the reflection off one plane for a satellite at (az_rad from north over east, el_rad); host only,
+ * needs no GPU.  In double, operation for operation:
+ *   GAL_REFL_GROUND, p[0] = h, the antenna's height over a horizontal plane (>= 0):  excess = 2 h sin(el), an echo where el > 0
+ *   GAL_REFL_WALL, p[0] = d (>= 0), p[1] = a_w: a vertical plane at the distance d in the direction of the azimuth a_w (rad):
+ *                                                excess = -2 d cos(el) cos(az - a_w), an echo where excess > 0 (the satellite
+ *                                                stands on the side away from the wall)
+ * Where there is no echo, *excess_m = -1 and the return value is still GAL_OK: gal_synth_refl_row makes that a row of gain 0.
+ * GAL_E_INVAL for a null pointer, another kind, an argument that is not finite, h < 0 or d < 0. */
+#define GAL_REFL_GROUND 0
+#define GAL_REFL_WALL 1
+int gal_synth_refl_geom(int32_t kind, const double *p, double az_rad, double el_rad, double *excess_m);
+/* The row of one epoch of N = samples_per_epoch samples from the excess path at the epoch's first sample (excess_now_m) and at the
+ * next epoch's (excess_next_m), for a direct signal at the gain slot_gain_q7; host only.  In double, operation for operation, with
+ * c = 299792458.0 and lambda = c / 1575420000.0 (that of gal_synth_array_phase):
+ *   t       = excess_now_m / c x sample_rate;  D = floor(t);  F = llround((t - D) x 4096), and F = 4096 is D + 1, F = 0
+ *   cyc(x)  = -x / lambda + refl_phase_deg / 360;  P(x) = llround((cyc - floor(cyc)) x 2^32) mod 2^32
+ *   ph0     = P(excess_now_m)
+ *   dph     = llround((double)(int32_t)(P(excess_next_m) - ph0) / N)      (the wrapped signed difference: ph0 + N dph meets the
+ *                                                                          next epoch's ph0 to within N / 2 units of 2^-32 cycle)
+ *   gain_q7 = min(GAL_GAIN_MAX, (slot_gain_q7 x llround(4096 x 10^(rel_db / 20)) + 2048) >> 12)    (as gal_synth_mpath_row)
+ * excess_now_m < 0 (no echo in this epoch): the row is all zeros.  excess_next_m < 0 (none in the next): dph = 0.  GAL_E_INVAL for a
+ * null row, an argument that is not finite, sample_rate <= 0, N < 1, a slot gain above GAL_GAIN_MAX, an amplitude above 2 (+6.02 dB)
+ * and a delay outside the range of gal_iq_refl_t. */
+int gal_synth_refl_row(double excess_now_m, double excess_next_m, double rel_db, double refl_phase_deg, double sample_rate,
+                       int32_t samples_per_epoch, uint16_t slot_gain_q7, gal_iq_refl_t *row);
+
+/*
  * Receiver oscillator (not in the reference, whose receiver has a perfect clock): a carrier offset, a linear
  * drift and white-FM phase noise of the local oscillator, i.e. ONE rotation common to everything that enters the mixer -- all
  * satellites, their echoes, the interference sources, the noise floor.  A FIXED INTEGER FUNCTION of (parameters, index of the sample
