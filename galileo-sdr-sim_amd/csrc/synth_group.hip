@@ -98,6 +98,13 @@ using namespace galdev;
 // the chip side of a group start in fixed point: the BOC(1,1) instances that look their pattern up in the bin table.  The bisection
 // instances (which compare with the float row s_thr) and CBOC (which also needs 6 A) keep the float form.
 #define SG_FIX(SIG, SEARCH) ((SIG) == 0 && !(SEARCH))
+// the per-position constants of an epoch in SCALAR registers: the same instances, for up to 12 positions (both carrier starts).  Every
+// wave fetches the DDA's step 511 |d| and the table base of its block's positions once, behind the table build (s_c511, s_lutd through
+// v_readfirstlane), and holds them across the chunk loop -- 3 SGPRs per position, 36 at most; the three instructions that consume
+// them (the linear start's fma, the DDA's v_add_f64, the address's v_lshl_add_u32) take them as their ONE scalar operand, and are
+// written as asm for it: left to itself the compiler copies the steps into 24 vector registers for the whole loop.  The wide,
+// bisection and CBOC instances read both from LDS at every part's start, into vector registers, as before.
+#define SG_SCAL(SIG, SEARCH, NCH) (SG_FIX(SIG, SEARCH) && (NCH) <= SG_MAXCH)
 #define SG_MAXCH 12     // channel positions of the instances for up to 12 channels (two blocks of 512 threads per CU) ...
 #define SG_MAXCH_WIDE 24  // ... and of the wide instances, 13 .. 24 positions in ONE launch (round 6: 24 stream rows = 56 KB of 133 KB
                           // of LDS, one block of 1024 threads per CU -- the same four waves per SIMD; rounds 3-5 ran such a batch as two
@@ -105,7 +112,8 @@ using namespace galdev;
 
 // What a group start needs of its channel and chunk, wave-uniform: written once per wave iteration by a LOADER lane (lane j < NCH
 // fetches channel j's checkpoint of the NEXT chunk while the wave works on the current one) into the wave's own LDS slots, read
-// back by every lane as one-address reads.  No scalar registers, nothing loop-invariant for the compiler to hoist into them.
+// back by every lane as one-address reads.  (What is constant over the whole BLOCK -- the DDA's step and the table base of a
+// position -- is not in the record: SG_SCAL above.)
 struct SgRec {
     double yc;   // code phase of the chunk's first sample (pre-check, :491), in half chips: 2 x (SG_FIX instances: + 2^20)
     double pm;   // carrier phase there, MIRRORED: times the sign of the epoch's step (k_synth: ChanState::p)
@@ -156,23 +164,30 @@ __device__ __forceinline__ double sg_f64(const uint32_t lo, const uint32_t hi) {
 // denominator (4.092, 8.184, 16.368 MS/s: two, four, eight samples per half chip; 2.5, 2.728 ...) have thresholds that coincide or lie
 // 1e-6 apart (the Doppler's share of the step) and used to send the whole batch to the exact-replay kernel.  The fraction is known to
 // 2^-31, the undecided band stays 2^-22 around every threshold: a few groups in 10^5 more are listed.
-template <int J0, int CNT, int MODE, int SIG, int BINS, int BPITCH, bool SEARCH, bool LIN, typename REC>
+// SCAL: the step 511 |d| and the table base of position j are the wave-uniform kc511[j], klutd[j] (scalar registers: SG_SCAL)
+template <int J0, int CNT, int MODE, int SIG, int BINS, int BPITCH, bool SEARCH, bool LIN, bool SCAL, typename REC>
 __device__ __forceinline__ void sg_part(int (&o)[16], uint32_t &amb, uint64_t &undec, const double g16, const REC *rec, const uint32_t *sya,
-                                        const double *s_c511, const uint32_t *s_lutd,
+                                        const double *s_c511, const uint32_t *s_lutd, const double *kc511, const uint32_t *klutd,
                                         const uint32_t *s_str, const uint2 *s_bin, const uint4 *s_pat, const uint2 *s_bin6,
                                         const uint32_t *s_pat6, const float *s_thr, const int nact)
 {
     uint32_t X[CNT];
     [[maybe_unused]] uint32_t XB[CNT];
     double t[CNT];
-    // the DDA's step 511 |d| and the table base of the part's positions: wave-uniform and constant over the epoch, but read
-    // from LDS for every group -- kept in registers for all twelve positions they would cost 36 of them
+    // the DDA's step 511 |d| and the table base of the part's positions: wave-uniform and constant over the epoch.  SCAL: the
+    // wave's scalar registers hold them.  Otherwise read from LDS for every group -- kept in VECTOR registers for all twelve
+    // positions they would cost 36 of them
     double c511[CNT];
     uint32_t lutd[CNT];
 #pragma unroll
     for (int q = 0; q < CNT; ++q) {
+        if constexpr (SCAL) {
+            c511[q] = kc511[J0 + q];
+            lutd[q] = klutd[J0 + q];
+        } else {
         c511[q] = ((const volatile __attribute__((address_space(3))) double *)(uintptr_t)s_c511)[J0 + q];
         lutd[q] = ((const volatile __attribute__((address_space(3))) uint32_t *)(uintptr_t)s_lutd)[J0 + q];
+        }
     }
     {
         // ---- phase A: the wave's records; approximate pre-check code phase at the group start; bin entry, stream words and
@@ -276,7 +291,9 @@ __device__ __forceinline__ void sg_part(int (&o)[16], uint32_t &amb, uint64_t &u
             // thresholds of the first and the last bin, because sample 0's own half chip hangs on the rounding history there
             undec |= __builtin_amdgcn_ballot_w64(!(__builtin_fabsf(f[q] - thr) >= RW_DELTA));
             }
-            if constexpr (LIN) {
+            if constexpr (LIN && SCAL) {
+                asm("v_fma_f64 %0, %1, %2, %3" : "=v"(t[q]) : "v"(g16), "s"(c511[q]), "v"(praw[q]));  // (the same fma, the step a scalar)
+            } else if constexpr (LIN) {
                 t[q] = __builtin_fma(g16, c511[q], praw[q]);  // unreduced: the table goes on behind the cycle's end
             } else {
             const double pg = praw[q] - __builtin_trunc(praw[q]);  // (a mirrored phase that is still negative stays negative)
@@ -356,12 +373,16 @@ __device__ __forceinline__ void sg_part(int (&o)[16], uint32_t &amb, uint64_t &u
             uint32_t a_;                                                                                                  \
             asm volatile("v_lshl_add_u32 %1, %2, 3, %3\n\tds_read_b64 %0, %1"                                             \
                          : "=&v"(e[u][q]), "=&v"(a_) : "v"((uint32_t)(d2u(t[q]) >> 32)), "v"(lutd[q]) : "memory");        \
+        } else if constexpr (SCAL) {                                                                                      \
+            asm volatile("v_lshl_add_u32 %0, %1, 2, %2\n\tds_read_b32 %0, %0"                                             \
+                         : "=&v"(e[u][q]) : "v"((uint32_t)(d2u(t[q]) >> 32)), "s"(lutd[q]) : "memory");                   \
         } else {                                                                                                          \
             asm volatile("v_lshl_add_u32 %0, %1, 2, %2\n\tds_read_b32 %0, %0"                                             \
                          : "=&v"(e[u][q]) : "v"((uint32_t)(d2u(t[q]) >> 32)), "v"(lutd[q]) : "memory");                   \
         }                                                                                                                 \
         lw[u][q] = (uint32_t)d2u(t[q]);                                                                                   \
-        t[q] = t[q] + c511[q];                                                                                            \
+        if constexpr (SCAL) asm("v_add_f64 %0, %1, %2" : "=v"(t[q]) : "v"(t[q]), "s"(c511[q]));                           \
+        else t[q] = t[q] + c511[q];                                                                                       \
     }
 // the reads of sample u have landed once no more than the CNT issued behind them are outstanding (none behind the last sample's);
 // the operands tie the multiply-adds of this sample (e), the running minimum of the fraction words (amb) and the multiply-adds of
@@ -417,6 +438,7 @@ void k_synth_g(const DevPlan *__restrict__ Pd, SynGeom G, const uint8_t *__restr
     static_assert(!LIN || (SG_FIX(SIG, SEARCH) && NCH <= SG_MAXCH), "the linear carrier start is built for the BOC(1,1) bin-table instances, up to 12 positions");
     constexpr int MC = NCH <= SG_MAXCH ? SG_MAXCH : SG_MAXCH_WIDE;  // positions the per-wave records are laid out for
     constexpr int LUT_N = LIN ? SG_LUT_LIN_N : SG_LUT_N;            // entries per carrier table
+    constexpr bool SCAL = SG_SCAL(SIG, SEARCH, NCH);                // the positions' step and table base in scalar registers
     using REC = typename std::conditional<LIN, SgRecLin, SgRec>::type;
     // CBOC keeps two bin tables per channel (chip holds, half-period parity) of 64 bins each, as in k_synth
     constexpr int BINS = SIG ? CB_BINS : RW_BINS, BPITCH = SIG ? CB_BIN_PITCH : RW_BIN_PITCH;
@@ -729,6 +751,16 @@ void k_synth_g(const DevPlan *__restrict__ Pd, SynGeom G, const uint8_t *__restr
     }
     __syncthreads();
     const bool rw_off = __builtin_amdgcn_readfirstlane(s_rwbad) != 0;
+    // ---- (SCAL) s_c511 and s_lutd of every position, once per block and wave: they stay in scalar registers until the block ends
+    [[maybe_unused]] double kc511[SCAL ? NCH : 1];
+    [[maybe_unused]] uint32_t klutd[SCAL ? NCH : 1];
+    if constexpr (SCAL) {
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            kc511[j] = uniform_f64(s_c511[j]);
+            klutd[j] = __builtin_amdgcn_readfirstlane(s_lutd[j]);
+        }
+    }
 
     // ---- the segment's chunks: wave w of the block takes chunks c_begin + w, + nw, ...
     const int lane = tid & 63;
@@ -839,7 +871,7 @@ void k_synth_g(const DevPlan *__restrict__ Pd, SynGeom G, const uint8_t *__restr
         const REC *rec = recw + buf * MC;
         const uint32_t *sya = syaw + buf * MC;
         // balanced parts: 5, 6, 7, 9, 10, 11 positions are cut 3+2, 3+3, 4+3, 3+3+3, 4+3+3, 4+4+3
-#define SG_PART(J0, CNT) sg_part<J0, CNT, MODE, SIG, BINS, BPITCH, SEARCH, LIN>(o, amb, undec, g16, rec, sya, s_c511, s_lutd, s_str, s_bin, s_pat, s_bin6, s_pat6, s_thr, nact); \
+#define SG_PART(J0, CNT) sg_part<J0, CNT, MODE, SIG, BINS, BPITCH, SEARCH, LIN, SCAL>(o, amb, undec, g16, rec, sya, s_c511, s_lutd, kc511, klutd, s_str, s_bin, s_pat, s_bin6, s_pat6, s_thr, nact); \
                          __builtin_amdgcn_sched_barrier(0);
         // (CBOC: parts of at most three -- a part's group start keeps 17 values per position alive, 13 in the BOC(1,1) form)
         if constexpr (SIG == 1 && NCH <= 3) { SG_PART(0, NCH) }
