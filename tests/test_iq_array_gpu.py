@@ -9,6 +9,7 @@ import pytest
 
 import array_model
 import gain_model
+import launch_model
 
 pytestmark = pytest.mark.gpu
 
@@ -82,7 +83,7 @@ def _weights(rng, n_epochs, n_elem, n_parts, row_sum):
 
 
 @pytest.mark.parametrize("wide", [False, True])
-@pytest.mark.parametrize("n_elem", [1, 2, 5, 8])
+@pytest.mark.parametrize("n_elem", [1, 2, 3, 4, 5, 6, 7, 8])
 @pytest.mark.parametrize("n_parts", [1, 2, 3, 4, 5, 63, 64])
 def test_part_and_element_counts(pkg, n_parts, n_elem, wide):
     """The part loop takes two parts per trip and the last one alone; every element count is an instance of its own.  Inside the int32
@@ -136,6 +137,46 @@ def test_launch_geometry(pkg, spe, n_epochs):
     w = _weights(rng, n_epochs, 2, 2, 65535)
     with pkg.SynthEngine(samples_per_epoch=spe, n_slots=16, device=0) as eng:
         _check(eng, parts, w, spe)
+
+
+# (geometry of tests/launch_model.py, parts, elements, the int64 instance): 5 parts are two whole two-part trips and the single one
+STRIDE_CASES = (("rows_and_lanes_stride", 3, 3, False), ("rows_and_lanes_stride", 3, 3, True), ("uneven_x_stride", 5, 8, False),
+                ("uneven_x_stride", 5, 4, True))
+
+
+def stride_case(name, n_parts, n_elem, wide):
+    """The inputs of test_stride_loops (tests/test_iq_launch_geometry_cpu.py asserts what they must be): every (epoch, element) has
+    weights of its own.  Inside the int32 bound one (epoch, element) sums to 65535 itself, on parts of +-3000.  wide: full-range parts
+    with the rails pinned at the start of every epoch under weights of a few hundred, so that most values stay inside the clamp, and
+    whole-range weights in one element of every 97th epoch, all parts in phase in two of them: those clamp."""
+    spe, n_epochs = launch_model.GEOMETRIES[name]
+    rng = np.random.default_rng(spe + n_elem + wide)
+    if wide:
+        parts = _edge_parts(rng, n_parts, n_epochs, spe)
+        w = rng.integers(-400, 401, size=(n_epochs, n_elem, n_parts, 2))
+        for e in range(0, n_epochs, 97):
+            w[e, e % n_elem] = rng.integers(-32767, 32768, size=(n_parts, 2))
+        w[0, 0, :, :] = 32767
+        w[97, 97 % n_elem, :, :] = -32767
+    else:
+        parts = _parts(rng, n_parts, n_epochs, spe)
+        w = _weights(rng, n_epochs, n_elem, n_parts, 65535)
+        e = n_epochs - 2  # (in rows_and_lanes_stride an epoch of the blocks' second y trip)
+        w[e, n_elem - 1] = 0
+        w[e, n_elem - 1, 0] = (32767, -32767)
+        w[e, n_elem - 1, n_parts - 1] = (0, 1)
+    return spe, parts, w
+
+
+@pytest.mark.parametrize("name,n_parts,n_elem,wide", STRIDE_CASES)
+def test_stride_loops(pkg, name, n_parts, n_elem, wide):
+    """Lanes that take a second vector (i += stride, where cap < need) and blocks that take a second epoch (e += gridDim.y), with K
+    output streams behind one index, in both widths."""
+    spe, parts, w = stride_case(name, n_parts, n_elem, wide)
+    assert array_model.needs_int64(w) == wide
+    with pkg.SynthEngine(samples_per_epoch=spe, n_slots=16, device=0) as eng:
+        sat = _check(eng, parts, w, spe)
+        assert not wide or 0 < sat < n_elem * parts.shape[1]
 
 
 @pytest.mark.parametrize("n_parts", [1, 3, 12])

@@ -246,17 +246,7 @@ def test_bad_arguments_and_call_order(pkg, batch):
 #   cap  = 2048 / by
 #   bx   = min(need, cap), at least 1         lane t of block x takes the epoch's whole vectors x 256 + t, + bx 256, + 2 bx 256, ...
 # The up to three samples in front of an epoch's first whole vector and behind its last are taken by block x = 0, one per lane.
-K_BLOCKS, K_LANES = 2048, 256
-
-
-def _launch(spe, n_epochs):
-    by = min(n_epochs, K_BLOCKS)
-    need, cap = (spe // 4 + K_LANES - 1) // K_LANES, K_BLOCKS // by
-    bx = max(1, min(need, cap))
-    a = np.arange(n_epochs, dtype=np.int64) * spe
-    vec = (a + spe) // 4 - (a + 3) // 4  # whole vectors of every epoch
-    return {"by": by, "bx": bx, "need": need, "cap": cap, "y_trips": -(-n_epochs // by), "vec": vec, "x_stride": bx * K_LANES,
-            "x_trips": -(-vec // (bx * K_LANES))}
+from launch_model import launch as _launch  # noqa: E402  (the restatement above, shared with the echo, reflector and array tests)
 
 
 def _edge_parts(rng, n_parts, n_epochs, spe):

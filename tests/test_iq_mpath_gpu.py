@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import gain_model
+import launch_model
 import mpath_model
 from oracle_binding import oracle_run
 
@@ -221,6 +222,49 @@ def test_more_epochs_than_grid_rows(pkg, cos1024):
     rows = _random_rows(rng, n_epochs, 5)
     with pkg.SynthEngine(samples_per_epoch=spe, n_slots=16, device=0) as eng:
         _check(eng, mpath_model.Lines(cos1024), spe, parts, gains, [0, 1, 2, 2, 0], rows)
+
+
+def stride_case(name):
+    """The inputs of test_stride_loops (tests/test_iq_launch_geometry_cpu.py asserts what they must be): 3 full-range parts, 8 echoes on
+    the first and the last part whose delays every epoch draws from DELAYS and whose phase steps span the int32 range; gains small
+    enough that most values stay inside the clamp (a clamped value hides its arithmetic) and some do not.  `wide_gains` are the
+    gains with ONE row beyond 65535 (epoch `e_wide`): the int64 instance for the whole call.  `second` is a short call behind the long
+    one whose echoes read the lines that the long call left."""
+    spe, n_epochs = launch_model.GEOMETRIES[name]
+    rng = np.random.default_rng(spe + n_epochs)
+    parts = _edge_parts(rng, 3, n_epochs, spe)
+    gains = rng.integers(0, 121, size=(n_epochs, 3))
+    rows = _random_rows(rng, n_epochs, 8, 60)
+    rows["dph"] = rng.integers(-(1 << 31), 1 << 31, size=rows.shape)
+    e_wide = n_epochs // 2
+    wide_gains = gains.copy()
+    wide_gains[e_wide] = (32767, 32767, 2)
+    rows2 = _random_rows(rng, 3, 8, 60)
+    rows2["delay"][0] = (1024, 1023, 255, 5, 4, 3, 1, 0)
+    second = (_edge_parts(rng, 3, 3, spe), rng.integers(0, 121, size=(3, 3)), rows2)
+    return {"spe": spe, "n_epochs": n_epochs, "parts": parts, "gains": gains, "wide_gains": wide_gains, "e_wide": e_wide, "rows": rows,
+            "pof": [0, 2, 2, 0, 2, 0, 0, 2], "second": second}
+
+
+@pytest.mark.parametrize("name", list(launch_model.GEOMETRIES))
+def test_stride_loops(pkg, cos1024, name):
+    """Lanes that take a second vector (i += stride, where cap < need) and blocks that take a second epoch (e += gridDim.y): the phase
+    m0 = 4 i - a and the delayed vector q of the second trip, against the model, in both instances.  Every long call is followed by a
+    short one on the same handle that reads the lines the long call left."""
+    case = stride_case(name)
+    spe, parts = case["spe"], case["parts"]
+    narrow, wide = launch_model.long_call_model(mpath_model.mpath, case, cos1024)
+    with pkg.SynthEngine(samples_per_epoch=spe, n_slots=16, device=0) as eng:
+        for gains, (want, want_sat) in ((case["gains"], narrow), (case["wide_gains"], wide)):
+            assert mpath_model.needs_int64(gains, case["rows"]) == (gains is case["wide_gains"])
+            eng.mpath_reset()
+            got, sat = _call(eng, parts, gains, case["pof"], case["rows"])
+            _same(got, want, spe)
+            assert sat == want_sat and 0 < sat < parts.shape[1]
+            lines = mpath_model.Lines(cos1024)
+            lines.lines[:3] = parts[:, -2 * mpath_model.H:]  # what a call of more than 1024 samples leaves
+            p2, g2, r2 = case["second"]
+            _check(eng, lines, spe, p2, g2, case["pof"], r2)
 
 
 def test_table_regrows_between_calls(pkg, cos1024):

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import gain_model
+import launch_model
 import mpath_model
 import refl_model
 from oracle_binding import oracle_run
@@ -168,6 +169,171 @@ def test_frac_0_is_iq_mpath_on_the_same_handle_and_the_passes_share_a_line(pkg, 
         assert sat == want_sat
 
 
+def _edge_parts(rng, n_parts, n_epochs, spe):
+    """Random full-range int16; the first 8 values of every epoch +32767 on all parts at once, the next 8 -32768."""
+    x = rng.integers(-32768, 32768, size=(n_parts, n_epochs, 2 * spe), dtype=np.int16)
+    x[:, :, :8] = 32767
+    x[:, :, 8:16] = -32768
+    return x.reshape(n_parts, -1)
+
+
+def stride_case(name):
+    """The inputs of test_stride_loops (tests/test_iq_launch_geometry_cpu.py asserts what they must be): those of the echo file's
+    stride_case with reflector rows -- 8 echoes per epoch drawn from DELAYS, F > 0 and F = 0 side by side -- and both ends of the
+    range, D = 1023 with F = 4095 and D = 1024 with F = 0, forced into epoch 10 and into the last epoch (in rows_and_lanes_stride one
+    that a block takes on its second y trip, and that begins on a vector: the one lane of its second x trip reads the epoch's first
+    samples)."""
+    spe, n_epochs = launch_model.GEOMETRIES[name]
+    rng = np.random.default_rng(spe + n_epochs + 1)
+    parts = _edge_parts(rng, 3, n_epochs, spe)
+    gains = rng.integers(0, 121, size=(n_epochs, 3))
+    rows = _random_rows(rng, n_epochs, 8, 60)
+    rows["dph"] = rng.integers(-(1 << 31), 1 << 31, size=rows.shape)
+    for e in (10, n_epochs - 1):
+        rows["delay"][e, :2], rows["frac_q12"][e, :2] = (1023, 1024), (4095, 0)
+    e_wide = n_epochs // 2
+    wide_gains = gains.copy()
+    wide_gains[e_wide] = (32767, 32767, 2)
+    rows2 = _random_rows(rng, 3, 8, 60)
+    rows2["delay"][0], rows2["frac_q12"][0] = (1024, 1023, 1023, 255, 4, 3, 1, 0), (0, 4095, 0, 1000, 2048, 1, 4095, 7)
+    second = (_edge_parts(rng, 3, 3, spe), rng.integers(0, 121, size=(3, 3)), rows2)
+    return {"spe": spe, "n_epochs": n_epochs, "parts": parts, "gains": gains, "wide_gains": wide_gains, "e_wide": e_wide, "rows": rows,
+            "pof": [0, 2, 2, 0, 2, 0, 0, 2], "second": second}
+
+
+@pytest.mark.parametrize("name", list(launch_model.GEOMETRIES))
+def test_stride_loops(pkg, cos1024, name):
+    """Lanes that take a second vector (i += stride, where cap < need) and blocks that take a second epoch (e += gridDim.y): the phase
+    m0 = 4 i - a and the delayed vectors q, q + 1 of the second trip, against the model, in both instances.  Every long call is
+    followed by a short one on the same handle that reads the lines the long call left."""
+    case = stride_case(name)
+    spe, parts = case["spe"], case["parts"]
+    narrow, wide = launch_model.long_call_model(refl_model.refl, case, cos1024)
+    with pkg.SynthEngine(samples_per_epoch=spe, n_slots=16, device=0) as eng:
+        for gains, (want, want_sat) in ((case["gains"], narrow), (case["wide_gains"], wide)):
+            assert refl_model.needs_int64(gains, case["rows"]) == (gains is case["wide_gains"])
+            eng.mpath_reset()
+            got, sat = _call(eng, parts, gains, case["pof"], case["rows"])
+            _same(got, want, spe)
+            assert sat == want_sat and 0 < sat < parts.shape[1]
+            lines = refl_model.Lines(cos1024)
+            lines.lines[:3] = parts[:, -2 * refl_model.H:]  # what a call of more than 1024 samples leaves
+            p2, g2, r2 = case["second"]
+            _check(eng, lines, spe, p2, g2, case["pof"], r2)
+
+
+PART_COUNTS = (4, 5, 6, 7, 8, 63, 64)
+
+
+def part_counts_case(n_parts, wide):
+    """The inputs of test_part_counts: three echoes on the first and on the LAST part (two on one part) at (D, F) = (1, 4095), (1023, 1)
+    and (4, 2048), permuted from epoch to epoch; full-range parts under gains small enough that most values stay inside the clamp, so
+    that a part taken with its neighbour's gain shows in the bytes.  wide: epoch 1 beyond 65535, the int64 instance for the call."""
+    spe, n_epochs = 1030, 3
+    rng = np.random.default_rng(2300 + n_parts)
+    parts = _edge_parts(rng, n_parts, n_epochs, spe)
+    gains = rng.integers(1, max(3, int(200 / n_parts ** 0.5)) + 1, size=(n_epochs, n_parts))
+    rows = _random_rows(rng, n_epochs, 3, 60)
+    df = ((1, 4095), (1023, 1), (4, 2048))
+    for e in range(n_epochs):
+        for r in range(3):
+            rows["delay"][e, r], rows["frac_q12"][e, r] = df[(r + e) % 3]
+    if wide:
+        gains[1] = rng.integers(20000, 32768, size=n_parts)
+        rows["gain_q7"][1] = 32767
+    return spe, parts, gains, [0, n_parts - 1, n_parts - 1], rows
+
+
+@pytest.mark.parametrize("wide", [False, True])
+@pytest.mark.parametrize("n_parts", PART_COUNTS)
+def test_part_counts(pkg, cos1024, n_parts, wide):
+    """The part loop takes four parts per trip and the rest one by one: 1, 2, 15 and 16 whole trips with every remainder.  Some values
+    clamp, and the count must be the model's.  A second call on the reversed parts: the delays read the first call's samples."""
+    assert {k // 4 for k in PART_COUNTS} == {1, 2, 15, 16} and {k % 4 for k in PART_COUNTS} == {0, 1, 2, 3}
+    spe, parts, gains, pof, rows = part_counts_case(n_parts, wide)
+    assert refl_model.needs_int64(gains, rows) == wide
+    with pkg.SynthEngine(samples_per_epoch=spe, n_slots=16, device=0) as eng:
+        lines = refl_model.Lines(cos1024)
+        sat = _check(eng, lines, spe, parts, gains, pof, rows)
+        assert 0 < sat < parts.shape[1]
+        _check(eng, lines, spe, parts[::-1], gains, pof, rows)
+
+
+def echoes32_case(wide):
+    """The inputs of test_32_echoes: GAL_ECHO_MAX = 32 echoes on 3 parts, all of DELAYS in every second epoch and a random pick in the
+    others, at gains inside the int32 bound (3 x 300 + 2 x 32 x 59 < 65535) or, wide, beyond it."""
+    spe, n_epochs = 261, 8
+    rng = np.random.default_rng(2400 + wide)
+    parts = _parts(rng, 3, n_epochs, spe)
+    gains = rng.integers(0, 300, size=(n_epochs, 3))
+    if wide:
+        parts //= 10  # (most values stay inside the clamp under the larger gains too)
+    rows = _random_rows(rng, n_epochs, 32, 2100 if wide else 60)
+    d = np.asarray(DELAYS + DELAYS[:10])
+    rows["delay"][::2], rows["frac_q12"][::2] = d[:, 0], d[:, 1]
+    pof = rng.integers(0, 3, size=32)
+    pof[-1] = 2
+    return spe, parts, gains, pof, rows
+
+
+def test_32_echoes(pkg, cos1024):
+    """The largest echo count there is, twice on one handle (the second call reads the first one's lines), then again with gains that
+    need the int64 instance."""
+    with pkg.SynthEngine(samples_per_epoch=261, n_slots=16, device=0) as eng:
+        lines = refl_model.Lines(cos1024)
+        for wide in (False, True):
+            spe, parts, gains, pof, rows = echoes32_case(wide)
+            assert rows.shape[1] == refl_model.GAL_ECHO_MAX and refl_model.needs_int64(gains, rows) == wide
+            assert {(int(D), int(F)) for D, F in zip(rows["delay"].ravel(), rows["frac_q12"].ravel())} == set(DELAYS)
+            for _ in range(2):
+                _check(eng, lines, spe, parts, gains, pof, rows)
+
+
+PHASE_STEPS = (-(1 << 31), -(1 << 31) + 1, -1, 1, (1 << 31) - 1)  # and a random one
+
+
+def test_phase_steps(pkg, cos1024):
+    """Steps next to +-2^31 and +-1 with 26001-sample epochs: m dph wraps thousands of times inside an epoch, and the kernel's
+    m0 * dph (uint32) must be the model's product mod 2^32.  F > 0 on four of the six echoes."""
+    spe, n_epochs = 26001, 3
+    rng = np.random.default_rng(25)
+    parts = _parts(rng, 2, n_epochs, spe)
+    gains = rng.integers(0, 300, size=(n_epochs, 2))
+    rows = _random_rows(rng, n_epochs, 6)
+    steps = np.asarray(PHASE_STEPS + (int(rng.integers(-(1 << 31), 1 << 31)),))
+    for e in range(n_epochs):
+        rows["dph"][e] = np.roll(steps, e)
+    rows["frac_q12"][:, :4] = rng.integers(1, 4096, size=(n_epochs, 4))
+    rows["delay"][:, :4] = np.minimum(rows["delay"][:, :4], 1023)
+    rows["frac_q12"][:, 4:] = 0
+    assert (spe - 1) * ((1 << 31) - 1) >> 32 > 10000
+    with pkg.SynthEngine(samples_per_epoch=spe, n_slots=16, device=0) as eng:
+        _check(eng, refl_model.Lines(cos1024), spe, parts, gains, [0, 1, 1, 0, 1, 0], rows)
+
+
+def test_hist_id_names_the_line(pkg, cos1024):
+    """Lines are named per call: permuted between calls, left out (-1) and taken up again, the last line (63).  Reflector rows with
+    F > 0; in the middle one call of gal_synth_iq_mpath, whose part 0 reads line 63, which the reflector pass wrote as its part 2."""
+    spe, n_epochs = 333, 2
+    rng = np.random.default_rng(26)
+    with pkg.SynthEngine(samples_per_epoch=spe, n_slots=16, device=0) as eng:
+        lines = refl_model.Lines(cos1024)
+        for ids, pof, echo in (([5, 9, -1], [0, 1, 1], False), ([9, 5, 63], [0, 1, 2], False), ([63, -1, 9], [0, 2, 0], True),
+                               ([-1, 63, 5], [2, 1, 1], False), (None, [0, 1, 2], False), ([2, 1, 0], [0, 1, 2], False)):
+            rows = _random_rows(rng, n_epochs, 3)
+            rows["delay"] = rng.choice((1023, 1022, 700, 4), size=rows.shape)
+            rows["frac_q12"] = 0 if echo else rng.integers(1, 4096, size=rows.shape)
+            parts, gains = _parts(rng, 3, n_epochs, spe), rng.integers(0, 300, size=(n_epochs, 3))
+            if not echo:
+                _check(eng, lines, spe, parts, gains, pof, rows, ids)
+                continue
+            erows = mpath_model.rows(n_epochs, 3, rows["gain_q7"], rows["delay"] + 1, rows["ph0"], rows["dph"])  # 1024 among them
+            got, sat = _call(eng, parts, gains, pof, erows, ids, echo=True)
+            want, want_sat = lines.call(parts, gains, spe, pof, erows, ids)
+            _same(got, want, spe)
+            assert sat == want_sat
+
+
 CUTS = (1, 5, 2, 8, 3, 9, 1, 21)  # epochs per call, of 100 samples: 5000 samples in all
 
 
@@ -304,3 +470,42 @@ def test_run_refl_over_two_batches(pkg, cos1024, batch):
         with pytest.raises(pkg.GalSynthError) as e:
             eng.run_refl(p, g, out.data_ptr(), sof, bad)
         assert "delay 1024 +" in str(e.value)
+
+
+@pytest.fixture(scope="module")
+def batch6(pkg):
+    """3 epochs of 2600 samples, 6 satellites: more slot groups than the four-parts-per-trip body of k_iq_refl takes in one trip.
+    Shared, left unchanged: the records, the oracle's end state of the full run, and the oracle's output of every slot alone."""
+    p = pkg.workloads.make_synthetic(n_epochs=3, n_chan=6, n_slots=16, samples_per_epoch=N, seed=82)
+    _, full_st = oracle_run(p, N, FS)
+    alone = np.stack([oracle_run(gain_model.slot_alone(p, s), N, FS)[0] for s in range(6)])
+    for a in (p, full_st, alone):
+        a.setflags(write=False)
+    return p, full_st, alone
+
+
+def test_run_refl_with_six_groups(pkg, cos1024, batch6):
+    """Echoes on five of six slots, two of them on slot 1; slot 4 has none.  Every slot with an echo is a run of its own and slot 4 is
+    the one run of the rest: six runs per batch, six parts for k_iq_refl -- one trip of four and two single
+    ones.  Two batches with the state carried over: the bytes and the count of the model over the oracle's per-slot streams in ONE
+    call, the end states of the full run."""
+    p, full_st, alone = batch6
+    assert (p["prn"][:, :6] > 0).all() and not (p["prn"][:, 6:] > 0).any()
+    rng = np.random.default_rng(27)
+    g = rng.integers(1, 700, size=p.shape)
+    sof = [0, 1, 1, 2, 3, 5]
+    rows = _random_rows(rng, 3, len(sof), 300)
+    rows["delay"][0], rows["frac_q12"][0] = (1023, 1024, 0, 3, 4, 255), (4095, 0, 1, 2048, 4095, 1000)  # the first batch reads zeros
+    want, want_sat, _ = refl_model.refl(alone, g[:, :6], N, sof, rows, cos1024)
+    plain, _ = gain_model.wsum(alone, g[:, :6], N)
+    assert np.count_nonzero(want != plain) > 0.5 * want.size
+    with pkg.SynthEngine(samples_per_epoch=N, n_slots=16, device=0) as eng:
+        a, st_a, sat_a = _run(eng, p[:2], g[:2], sof, rows[:2])
+        assert eng.gain_runs() == 5 + 1
+        b, st_b, sat_b = _run(eng, p[2:], g[2:], sof, rows[2:], st_a)
+        assert eng.gain_runs() == 5 + 1
+        _same(np.concatenate([a, b]), want, N)
+        assert sat_a + sat_b == want_sat
+        act = full_st["prn"] > 0
+        assert np.array_equal(st_b["prn"], full_st["prn"])
+        assert np.array_equal(st_b["carr_phase"][act].view(np.uint64), full_st["carr_phase"][act].view(np.uint64))
