@@ -1,6 +1,6 @@
 """The receiver oscillator on the MI355X: k_osc_tilesum, k_osc_scan and k_iq_osc against the numpy model (tests/osc_model.py) -- bytes
 and saturation count equal -- at the edges of a vector, a wave, a tile and the grid, in place and out of place, with and without phase
-noise; the stream in cuts; the wrap arithmetic at the largest parameters; full-scale input; gal_synth_osc_set; the refusals; and one
+noise; three trips of the grid-stride loop, the scan with every lane full and the stream behind such a call; the stream in cuts; the wrap arithmetic at the largest parameters; full-scale input; gal_synth_osc_set; the refusals; and one
 satellite of the oracle's stream through a +2 kHz oscillator and the correlator bank."""
 import ctypes
 
@@ -10,6 +10,7 @@ import pytest
 import corr_model
 import osc_model
 from oracle_binding import oracle_run
+from tile_launch_model import OSC_GEOMETRIES
 
 pytestmark = pytest.mark.gpu
 
@@ -95,6 +96,47 @@ def test_the_grid_stride_loop_runs_twice(pkg, o):
         got, sat = _call(eng, x, True)
     assert np.array_equal(got, want), _differ(got, want)
     assert sat == want_sat
+
+
+@pytest.fixture(scope="module")
+def long_input():
+    """Input for the longest geometry of tile_launch_model.OSC_GEOMETRIES and the two short calls behind it."""
+    n = max(n for n, _ in OSC_GEOMETRIES.values()) + SHORT_BEHIND[0] + SHORT_BEHIND[1]
+    x = _input(np.random.default_rng(11), n)
+    x.setflags(write=False)
+    return x
+
+
+SHORT_BEHIND = (5, T + 1)  # the calls directly behind a long one: less than a vector more than one, and a tile and a sample
+LONG_CASES = [("third_trip", DET), ("third_trip", NOISY), ("full_scan", NOISY)]
+
+
+@pytest.mark.parametrize("name,o", LONG_CASES, ids=["third_trip-S0", "third_trip-S>0", "full_scan-S>0"])
+def test_three_trips_and_the_stream_behind_them(pkg, long_input, name, o):
+    """The geometries of tests/tile_launch_model.py (tests/test_iq_launch_geometry_cpu.py asserts what each is for): a block's third
+    trip writes the LDS set its first trip read (k_osc_tilesum, k_iq_osc<true>); the scan with five tiles per lane and empty lanes
+    behind, and with six in every lane so that the last lane forms the state word from its own tiles.  In place, bit for bit, count
+    and guard.  Directly behind the long call, with no osc_set in between, two short calls go on with the stream: they start from the
+    state word that the long scan wrote.  With S = 0 (one launch, no LDS in the loop) the per-tile A and W at tiles beyond 2^22
+    samples."""
+    n, first = OSC_GEOMETRIES[name]
+    o = osc_model.osc(**o)
+    x = long_input[:2 * n]
+    want, want_sat, zz = osc_model.rotate(x, o, first, first)
+    with pkg.SynthEngine(samples_per_epoch=N, n_slots=16, device=0) as eng:
+        eng.osc_set(o, first)
+        got, sat = _call(eng, x, True)
+        assert np.array_equal(got, want), "%s: %s" % (name, _differ(got, want))
+        assert sat == want_sat
+        at = n
+        for m in SHORT_BEHIND:
+            xs = long_input[2 * at:2 * (at + m)]
+            want, want_sat, zz = osc_model.rotate(xs, o, first, first + at, zz)
+            got, sat = _call(eng, xs, False)
+            assert np.array_equal(got, want), "%s, %d samples behind sample %d: %s" % (name, m, at, _differ(got, want))
+            assert sat == want_sat
+            at += m
+    assert (zz != 0) == (o["s"] != 0)
 
 
 @pytest.mark.parametrize("first", FIRSTS)

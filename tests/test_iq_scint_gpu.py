@@ -1,7 +1,8 @@
 """Per-satellite ionospheric scintillation on the MI355X: k_iq_scint against the numpy model (tests/scint_model.py) -- bytes and
 saturation count equal -- at the edges of a vector, a node interval, a tile and the grid, in place and out of place, many jobs in one
-launch; the stream in cuts; full-scale input; the identity; the refusals; gal_synth_run_scint against the model over the oracle's
-per-slot streams; and one fading satellite through the correlator bank."""
+launch; three and four trips of the grid-stride loop at node lengths up to 2^24 and at the CLI's split; the stream in cuts; full-scale
+input; the identity; the refusals; gal_synth_run_scint against the model over the oracle's per-slot streams; and one fading satellite
+through the correlator bank."""
 import ctypes
 
 import numpy as np
@@ -10,6 +11,7 @@ import pytest
 import gain_model
 import scint_model
 from oracle_binding import oracle_run
+from tile_launch_model import SCINT_GEOMETRIES
 
 pytestmark = pytest.mark.gpu
 
@@ -119,8 +121,75 @@ def test_the_grid_stride_loop_runs_twice(pkg, stream):
     specs.append((stream[:2 * n], 2 ** 40 + 1, dict(RICE, node_len=67), True))
     with pkg.SynthEngine(samples_per_epoch=N, n_slots=16, device=0) as eng:
         _check(eng, specs)
-        # ... and one job alone over more tiles than the grid has blocks is beyond a test of seconds: MAX_BLOCKS tiles are the CLI's batch
+        # one job alone gets a block per tile.  (Three and four trips, at node lengths from 67 to 2^24 and at the CLI's 170 blocks per
+        # job, are test_many_trips_* below.  What stays untested is n_jobs = 1 with more than MAX_BLOCKS tiles: a second trip at
+        # bx = MAX_BLOCKS, a stride of 2^21 samples, needs more than 2.1 M samples in one job.)
         _check(eng, [(stream[:2 * (3 * T + 1)], 5, dict(RICE, node_len=1000), True)])
+
+
+@pytest.fixture(scope="module")
+def long_stream():
+    """Input for the longest job of tile_launch_model.SCINT_GEOMETRIES; job k of a call reads it from its value 8 k on."""
+    n = max(n for _, jobs in SCINT_GEOMETRIES.values() for n, _, _ in jobs)
+    x = _input(np.random.default_rng(6), n + 4 * 64)
+    x.setflags(write=False)
+    return x
+
+
+def _specs(name, long_stream, rows, in_place):
+    """The named geometry's jobs as _check takes them: rows[L] (rows[L][k] where there are several jobs of one L) is the row without
+    its node_len, in_place the set of job indices that run in place.  Every job has an input of its own."""
+    n_jobs, jobs = SCINT_GEOMETRIES[name]
+    specs = []
+    for k, (n, first, L) in enumerate(jobs):
+        r = rows[L][k] if isinstance(rows[L], list) else rows[L]
+        specs.append((long_stream[8 * k:8 * k + 2 * n], first, dict(r, node_len=L), k in in_place))
+    return specs
+
+
+def test_many_trips_at_many_node_lengths(pkg, long_stream):
+    """64 jobs, 32 blocks each: five jobs of 98 tiles take three and four trips at L = 1025 (a whole tile between two nodes), 40 000
+    (above the stride: sj = 0, three nodes inside vectors), 162 500 (--scint at tau0 = 0.5 s: m0 grows for two steps before the correction
+    fires), 2^24 (the largest: one node, five samples into the job) and 67.  tests/test_iq_launch_geometry_cpu.py asserts that the
+    geometry has all of that, and on which steps the correction of (j0, m0) fires."""
+    rows = {64: RICE, 1025: RICE, 40000: RAYLEIGH, 162500: dict(RICE, seed=77, stream=0x10B),
+            1 << 24: dict(a_q12=0, b_q12=4096, seed=12, stream=0x40B), 67: RICE}
+    specs = _specs("node_lens_at_four_trips", long_stream, rows, in_place={60, 62})
+    assert [s[2]["node_len"] for s in specs[59:]] == [1025, 40000, 162500, 1 << 24, 67] and [s[3] for s in specs[59:]].count(True) == 2
+    with pkg.SynthEngine(samples_per_epoch=N, n_slots=16, device=0) as eng:
+        _check(eng, specs)
+    # the factor moves inside every long job; at L = 2^24 a sample's step is 1 / 4096 of the nodes' difference at best, so there the three
+    # nodes themselves must differ (seed 12 was chosen for that): a tile that took its neighbour's pair of nodes would show
+    for x, first, row, _ in specs[59:]:
+        r, L = scint_model.row(**row), row["node_len"]
+        if L < 1 << 24:
+            zI, zQ = scint_model.factor(r, first, x.size // 2)
+            assert np.ptp(zI) > 8 and np.ptp(zQ) > 8, L
+        else:
+            ZI, ZQ = scint_model.nodes(r, first // L, 3)
+            assert min(np.abs(np.diff(ZI)).min(), np.abs(np.diff(ZQ)).min()) > 600
+
+
+def test_many_trips_at_the_default_batchs_split(pkg, long_stream):
+    """Twelve jobs -- the scintillating satellites of the default batch -- get 170 blocks each; at L = 162 500 the stride is (1, 11580)
+    nodes and samples.  345 tiles and three samples per job: three trips.  Rician and Rayleigh rows in turn, every job with its own
+    seed, stream, input and first sample."""
+    rows = {162500: [dict(RAYLEIGH if k & 1 else RICE, seed=1000 + k, stream=(k << 8) | 11) for k in range(12)]}
+    specs = _specs("cli_split", long_stream, rows, in_place={1, 2, 5, 8, 11})
+    assert len(specs) == 12 and len({(s[2]["seed"], s[2]["stream"], s[1]) for s in specs}) == 12
+    with pkg.SynthEngine(samples_per_epoch=N, n_slots=16, device=0) as eng:
+        _check(eng, specs)
+
+
+def test_b0_at_four_trips(pkg, long_stream):
+    """B = 0 (z = A: no draws, no sums, one barrier fewer per trip) over 98 tiles on 32 blocks, beside 63 jobs that draw; A = 3000 is
+    not the identity."""
+    rows = {64: RICE, 67: dict(a_q12=3000, b_q12=0, seed=9, stream=1)}
+    specs = _specs("b0_at_four_trips", long_stream, rows, in_place={63})
+    with pkg.SynthEngine(samples_per_epoch=N, n_slots=16, device=0) as eng:
+        _check(eng, specs)
+    x, first, row, _ = specs[63]
+    assert not np.array_equal(scint_model.apply(x[:64], scint_model.row(**row), first)[0], x[:64])
 
 
 def test_three_jobs_of_different_lengths_rows_and_seeds_in_one_call(pkg, stream):
