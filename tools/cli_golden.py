@@ -5,7 +5,8 @@
   tools/cli_golden.py chain        the run loop     -> tests/golden/cli_chain_md5.json  (needs the MI355X)
 
 Both are run at the commit whose behaviour is to be kept; tests/test_cli_transcript.py and tests/test_cli_chain_gpu.py only read the
-two files and compare for equality.  The case lists live here, and the fixtures carry them along (argument vectors, input files)."""
+two files and compare for equality.  The case lists live here, and the fixtures carry them along (argument vectors, input files).
+tests/test_cli_chain_model_gpu.py takes the chain's scenario, cases and runner (run_chain_files) from here and computes the bytes."""
 import hashlib
 import json
 import os
@@ -199,19 +200,24 @@ CHAIN_CASES = [
     {"name": "mpath_alone_monitor_ishort", "fmt": "ishort", "argv": ["--multipath", "mp.txt", "--monitor-every", "2"], "monitor": True},
     {"name": "scint_mpath_power_ishort", "fmt": "ishort", "argv": ["--scint", "sc.txt", "--multipath", "mp.txt", "--power-model"]},
     {"name": "array_scint_cn0_ibyte", "fmt": "ibyte", "argv": ["--array", "arr.txt", "--scint", "sc.txt", "--cn0", "45"], "elements": 3},
+    {"name": "refl_cn0_osc_ibyte", "fmt": "ibyte", "argv": ["--reflector", "ground,2,-6", "--reflector", "wall,100,90,-3", "--cn0", "45"] + OSC},
 ]
 
 
-def _md5(*paths):
+def _md5(*blobs):
     h = hashlib.md5()
-    for path in paths:
-        with open(path, "rb") as fh:
-            h.update(fh.read())
+    for blob in blobs:
+        h.update(blob)
     return h.hexdigest()
 
 
-def run_chain_case(exe, case, batch, files):
-    """One run; returns the md5 of the IQ file and of the side files asked for."""
+def _read(path):
+    with open(path, "rb") as fh:
+        return fh.read()
+
+
+def run_chain_files(exe, case, batch, files):
+    """One run; returns what it wrote: "iq" (the bytes of the IQ file, or of every element's), the side files asked for, "stderr"."""
     with tempfile.TemporaryDirectory() as d:
         for name, text in files.items():
             with open(os.path.join(d, name), "w") as fh:
@@ -226,12 +232,23 @@ def run_chain_case(exe, case, batch, files):
         if r.returncode != 0:
             raise RuntimeError("%s -B %d: exit %d\n%s" % (case["name"], batch, r.returncode, r.stderr[-2000:]))
         outs = [os.path.join(d, "out.a%d.%s" % (k, case["fmt"])) for k in range(case["elements"])] if case.get("elements") else [os.path.join(d, out)]
-        got = {"iq": _md5(*outs), "iq_bytes": sum(os.path.getsize(o) for o in outs)}
+        wrote = {"iq": [_read(o) for o in outs], "stderr": r.stderr}
         if case.get("monitor"):
-            got["monitor"] = _md5(os.path.join(d, "mon.csv"))
-            got["monitor_lines"] = len(open(os.path.join(d, "mon.csv")).read().splitlines())
+            wrote["monitor"] = _read(os.path.join(d, "mon.csv"))
         if case.get("agc_log"):
-            got["agc_log"] = _md5(os.path.join(d, "agc.csv"))
+            wrote["agc_log"] = _read(os.path.join(d, "agc.csv"))
+    return wrote
+
+
+def run_chain_case(exe, case, batch, files):
+    """One run; returns the md5 of the IQ file and of the side files asked for."""
+    wrote = run_chain_files(exe, case, batch, files)
+    got = {"iq": _md5(*wrote["iq"]), "iq_bytes": sum(len(b) for b in wrote["iq"])}
+    if case.get("monitor"):
+        got["monitor"] = _md5(wrote["monitor"])
+        got["monitor_lines"] = len(wrote["monitor"].decode().splitlines())
+    if case.get("agc_log"):
+        got["agc_log"] = _md5(wrote["agc_log"])
     return got
 
 
