@@ -13,8 +13,13 @@ pytestmark = pytest.mark.gpu
 def _compare(pkg, params, n_samp, rate=2.6e6, state_in=None, **eng_kw):
     n_slots = params.shape[1]
     with pkg.SynthEngine(sample_rate=rate, samples_per_epoch=n_samp, n_slots=n_slots, device=0, **eng_kw) as eng:
-        iq, st, stats = eng.run_host(params, state_in)
-    ref_iq, ref_st = oracle_run(params, n_samp, rate, state_in)
+        return _compare_on(eng, params, n_samp, rate, state_in)
+
+
+def _compare_on(eng, params, n_samp, rate=2.6e6, state_in=None, cboc=False):
+    """_compare's run and checks on an engine the caller keeps (many batches through one handle); cboc: against the oracle's CBOC loop."""
+    iq, st, stats = eng.run_host(params, state_in)
+    ref_iq, ref_st = oracle_run(params, n_samp, rate, state_in, cboc=cboc)
     assert stats["chain_mismatch"] == 0
     nbad = int(np.count_nonzero(iq != ref_iq))
     assert nbad == 0, "%d of %d int16 values differ (first at %d)" % (nbad, iq.size, int(np.flatnonzero(iq != ref_iq)[0]))
