@@ -44,6 +44,7 @@ from .synth import (  # noqa: F401
     osc_lo_step,
     osc_make,
     pack_page,
+    psd_segments,
     refl_check,
     refl_geom,
     refl_row,

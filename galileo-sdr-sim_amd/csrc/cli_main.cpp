@@ -36,6 +36,9 @@
 // --monitor <file> (not in the reference): the built-in receiver check -- every --monitor-every'th epoch (default 10) the first 25 code
 // periods of every active channel are despread, in the buffer as it is written (behind noise and format), with the planned replica
 // (gal_synth_correlate); one CSV line per (epoch, PRN) with the measured C/N0 and where the peak lies.  Read-only: the IQ is the same.
+// --spectrum <file> (not in the reference): the other half of the self-check -- every --spectrum-every'th epoch (default 10) the Welch
+// power spectrum of the epoch's 260 000 output samples, in the buffer as it is written (gal_synth_iq_psd: an exact integer transform;
+// DESIGN.md section 24); one CSV line per reported epoch and the run's total.  Read-only: the IQ is the same.
 //
 // Pipeline: a producer thread runs the host front-end (libgalscen: orbits, ranges, I/NAV pages) up to two batches
 // ahead -> the main thread plans and executes each batch on the GPU and, after gal_synth_finish(), enqueues the copy
@@ -56,6 +59,7 @@
 #include <signal.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -137,6 +141,51 @@ void monitor_flush(MonBatch &mb, FILE *fp, double sample_rate, const gal_corr_re
     mb.pending = false;
 }
 
+// ---- --spectrum ---------------------------------------------------------------------------------------------------
+struct SpecBatch {  // the reported epochs of one batch: per epoch N uint64 sums
+    std::vector<int> epoch;  // index in the whole run
+    std::vector<int32_t> n_seg;
+    unsigned long long *dev = nullptr, *host = nullptr;
+    void *d_line = nullptr;  // ibit: an epoch that begins 8 bytes off the 16-byte grid is copied here first
+    bool pending = false;
+};
+typedef unsigned __int128 u128;
+struct SpecTotal {
+    std::vector<u128> p;  // natural bin order
+    uint64_t n_seg = 0;
+    int n_epochs = 0;
+};
+
+void print_u128(FILE *fp, u128 v)
+{
+    char buf[48];
+    int i = sizeof(buf);
+    buf[--i] = 0;
+    do buf[--i] = (char)('0' + (int)(v % 10)), v /= 10;
+    while (v);
+    fputs(buf + i, fp);
+}
+
+// the lines of a batch whose sums have arrived (the stream has been waited for): frequency order, -fs / 2 first
+void spectrum_flush(SpecBatch &sb, FILE *fp, int N, SpecTotal &tot)
+{
+    for (size_t i = 0; i < sb.epoch.size(); ++i) {
+        const unsigned long long *p = sb.host + i * (size_t)N;
+        fprintf(fp, "%.1f,%d", sb.epoch[i] * 0.1, sb.n_seg[i]);
+        for (int k = 0; k < N; ++k) {
+            const int b = (k + N / 2) & (N - 1);
+            fprintf(fp, ",%llu", p[b]);
+            tot.p[b] += p[b];
+        }
+        fputc('\n', fp);
+        tot.n_seg += (uint64_t)sb.n_seg[i];
+        ++tot.n_epochs;
+    }
+    sb.epoch.clear();
+    sb.n_seg.clear();
+    sb.pending = false;
+}
+
 // ---- what the three threads share -----------------------------------------------------------------------------------------------------
 struct AgcLog {  // --agc-log: the gains of the blocks that start in a batch
     uint32_t *dev = nullptr, *host = nullptr;
@@ -152,7 +201,8 @@ struct BatchSlot {
     void *d_out = nullptr;
     hipEvent_t converted = nullptr;  // the chain has run (Config::chain_on_engine_stream)
     Slot out;                        // pinned; `full` and `bytes` are the writer's hand-over, under SlotPair::mu
-    MonBatch mon;                    // the main thread's alone, as is agc_log
+    MonBatch mon;                    // the main thread's alone, as are spec and agc_log
+    SpecBatch spec;
     AgcLog agc_log;
 };
 
@@ -290,6 +340,7 @@ struct Run {
     std::vector<gal_iq_refl_t> rf_rows;   // --reflector: the rows [epochs][slots with echoes x reflectors] of one call
     gal_corr_req_t mon_shape;  // what every monitor request shares
     MonSummary mon_sum[GAL_NUM_PRN + 1];
+    SpecTotal spec_total;
     uint64_t agc_logged = 0;  // blocks written to the log
     std::string err;          // why the loop was left; reported once, behind it
 
@@ -350,6 +401,14 @@ bool alloc_slots(const Run &r, SlotPair &sp)
         for (BatchSlot &b : sp.s)
             if (hipMalloc((void **)&b.mon.dev, mon_bytes) != hipSuccess || hipHostMalloc((void **)&b.mon.host, mon_bytes, hipHostMallocDefault) != hipSuccess)
                 return false;
+    // --spectrum: per batch slot the sums of its reported epochs, on the device and pinned on the host
+    if (c.spectrum_fp) {
+        const size_t spec_bytes = ((size_t)(c.batch_epochs + c.spectrum_every - 1) / c.spectrum_every + 1) * (sizeof(unsigned long long) << c.spectrum.log2_n);
+        for (BatchSlot &b : sp.s)
+            if (hipMalloc((void **)&b.spec.dev, spec_bytes) != hipSuccess || hipHostMalloc((void **)&b.spec.host, spec_bytes, hipHostMallocDefault) != hipSuccess ||
+                (c.iq_format == GAL_IQ_IBIT && hipMalloc(&b.spec.d_line, r.epoch_bytes + 16) != hipSuccess))
+                return false;
+    }
     // --agc-log: per batch slot the gains of the blocks that start in it, on the device and pinned on the host
     const size_t g_bytes = ((size_t)c.batch_epochs * kOutSamplesPerEpoch / (size_t)c.agc_block + 2) * sizeof(uint32_t);
     if (c.agc_log_fp)
@@ -420,6 +479,33 @@ bool enqueue_monitor(Run &r, BatchSlot &b, const MonRequests &m)
                               r.stream) != hipSuccess)
         return r.fail("monitor: %s", ok ? "copy of the sums failed" : gal_synth_last_error());
     b.mon.pending = true;
+    return true;
+}
+
+// --spectrum: behind the conversion, on the same stream, in the buffer the copies read: one call per reported epoch, always the whole
+// epoch, so that the file does not depend on -B
+bool enqueue_spectrum(Run &r, BatchSlot &b, int n)
+{
+    const Config &c = r.c;
+    SpecBatch &sb = b.spec;
+    const size_t N = (size_t)1 << c.spectrum.log2_n;
+    for (int e = 0; e < n; ++e) {
+        if ((r.emitted + e) % c.spectrum_every) continue;
+        const void *src = (const char *)b.d_out + c.out_bytes((size_t)e * kOutSamplesPerEpoch);
+        if ((uintptr_t)src & 15) {  // (ibit, an odd epoch of the batch: 65 000 bytes per epoch)
+            if (hipMemcpyAsync(sb.d_line, src, r.epoch_bytes, hipMemcpyDeviceToDevice, r.stream) != hipSuccess) return r.fail("spectrum: copy of the epoch failed");
+            src = sb.d_line;
+        }
+        int32_t n_seg = 0;
+        if (gal_synth_iq_psd(r.eng, src, c.iq_format, (size_t)kOutSamplesPerEpoch, &c.spectrum, (uint64_t *)(sb.dev + sb.epoch.size() * N), &n_seg) != GAL_OK)
+            return r.fail("spectrum: %s", gal_synth_last_error());
+        sb.epoch.push_back(r.emitted + e);
+        sb.n_seg.push_back(n_seg);
+    }
+    if (sb.epoch.empty()) return true;
+    if (hipMemcpyAsync(sb.host, sb.dev, sb.epoch.size() * N * sizeof(unsigned long long), hipMemcpyDeviceToHost, r.stream) != hipSuccess)
+        return r.fail("spectrum: copy of the sums failed");
+    sb.pending = true;
     return true;
 }
 
@@ -686,6 +772,7 @@ bool finish_batch(Run &r, BatchSlot &b, int n, const MonRequests &mon)
          hipStreamWaitEvent(r.copy_stream[1], b.converted, 0) != hipSuccess))
         return r.fail("event after the IQ conversion failed");
     if (c.monitor_fp && !mon.reqs.empty() && !enqueue_monitor(r, b, mon)) return false;
+    if (c.spectrum_fp && !enqueue_spectrum(r, b, n)) return false;
     return enqueue_copies(r, b, n);
 }
 
@@ -744,6 +831,7 @@ int run_loop(Run &r, RowRing &ring, SlotPair &sp, int total, Clock::time_point t
         BatchSlot &prev = sp.s[cur ^ 1];
         if (c.monitor_fp && prev.mon.pending) monitor_flush(prev.mon, c.monitor_fp, kOutRate, r.mon_shape, r.mon_sum);
         if (c.agc_log_fp && prev.agc_log.pending) r.agc_log_flush(prev.agc_log);
+        if (c.spectrum_fp && prev.spec.pending) spectrum_flush(prev.spec, c.spectrum_fp, 1 << c.spectrum.log2_n, r.spec_total);
         const double tb_synth = ms_since(tb0);
         if (batch_timing)
             fprintf(stderr, "[timing] batch at %7.2f ms: %3d epochs, waited %.2f ms for rows, %.2f for a free slot, %s %.2f\n",
@@ -767,6 +855,58 @@ int run_loop(Run &r, RowRing &ring, SlotPair &sp, int total, Clock::time_point t
     }
     if (!r.err.empty()) fprintf(stderr, "\nERROR: %s\n", r.err.c_str());
     return cur;
+}
+
+// --spectrum: the last batches' lines, the total (sums in 128-bit integers, printed in decimal), the summary on stderr; false: the
+// file is not whole
+bool spectrum_report(Run &r, SlotPair &sp, int older)
+{
+    const Config &c = r.c;
+    const int N = 1 << c.spectrum.log2_n;
+    SpecTotal &t = r.spec_total;
+    bool ok = hipStreamSynchronize(r.stream) == hipSuccess;
+    for (int i = 0; i < 2 && ok; ++i)  // (the older batch first)
+        if (sp.s[older ^ i].spec.pending) spectrum_flush(sp.s[older ^ i].spec, c.spectrum_fp, N, t);
+    fprintf(c.spectrum_fp, "total,%llu", (unsigned long long)t.n_seg);
+    for (int k = 0; k < N; ++k) {
+        fputc(',', c.spectrum_fp);
+        print_u128(c.spectrum_fp, t.p[(k + N / 2) & (N - 1)]);
+    }
+    fputc('\n', c.spectrum_fp);
+    if (fclose(c.spectrum_fp) != 0) {
+        fprintf(stderr, "ERROR: writing the spectrum file %s failed\n", c.spectrum_file);
+        ok = false;
+    }
+    for (BatchSlot &b : sp.s) {
+        hipFree(b.spec.dev);
+        hipHostFree(b.spec.host);
+        if (b.spec.d_line) hipFree(b.spec.d_line);
+    }
+    fprintf(stderr, "Spectrum (%s): %d epochs, %llu segments of %d, %s window\n", c.spectrum_file, t.n_epochs, (unsigned long long)t.n_seg, N,
+            c.spectrum.window ? "Hann" : "rectangular");
+    if (!t.n_seg) return ok;
+    // in frequency order: the peak, the median, and the band that holds 99 % of the power (0.5 % cut off at either end)
+    std::vector<long double> f((size_t)N);
+    long double sum = 0.0L;
+    int peak = 0;
+    for (int k = 0; k < N; ++k) {
+        f[k] = (long double)t.p[(k + N / 2) & (N - 1)];
+        sum += f[k];
+        if (f[k] > f[peak]) peak = k;
+    }
+    std::vector<long double> sorted(f);
+    std::sort(sorted.begin(), sorted.end());
+    const long double median = 0.5L * (sorted[N / 2 - 1] + sorted[N / 2]);
+    int lo = 0, hi = N - 1;
+    long double cut = 0.0L;
+    while (lo < hi && cut + f[lo] <= 0.005L * sum) cut += f[lo++];
+    cut = 0.0L;
+    while (hi > lo && cut + f[hi] <= 0.005L * sum) cut += f[hi--];
+    const double bin_hz = kOutRate / N;
+    fprintf(stderr, "  peak at %+.1f Hz (bin %+d), %.2f dB over the median bin; 99 %% of the power within %.1f Hz (%+.1f .. %+.1f Hz)\n", (peak - N / 2) * bin_hz,
+            peak - N / 2, median > 0.0L ? 10.0 * log10((double)(f[peak] / median)) : INFINITY, (hi - lo + 1) * bin_hz, (lo - N / 2 - 0.5) * bin_hz,
+            (hi - N / 2 + 0.5) * bin_hz);
+    return ok;
 }
 
 // behind "Done!": the side files' last lines and summaries, the notes, the saturation report.  Returns the exit code so far
@@ -811,6 +951,7 @@ int report(Run &r, SlotPair &sp, gal_scen_t *scen, int older)
             hipHostFree(b.agc_log.host);
         }
     }
+    if (c.spectrum_fp) rc = spectrum_report(r, sp, older) ? rc : 1;
     if (gal_scen_eph_gaps(scen) > 0)
         fprintf(stderr, "NOTE: %d (satellite, refresh) pairs ran on a stale ephemeris record (see the warning above)\n", gal_scen_eph_gaps(scen));
     if (c.power_on) {
@@ -975,6 +1116,7 @@ int run(Config &c, gal_scen_t *scen)
     // gal_corr_cn0 reads the period length off the shape: the nominal code step (a request's own differs by its code Doppler, a few
     // 1e-6: 1e-5 dB).  Left at 0 it made every C/N0 of the CSV "nan"
     r.mon_shape.code_dph = (uint64_t)llround(2.0 * 1.023e6 / kOutRate * 4294967296.0);
+    if (c.spectrum_fp) r.spec_total.p.assign((size_t)1 << c.spectrum.log2_n, 0);
     SlotPair sp;
     if (!alloc_slots(r, sp)) die("ERROR: buffer allocation failed\n");
     stage("device + pinned buffers");

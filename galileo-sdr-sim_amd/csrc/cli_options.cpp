@@ -420,7 +420,7 @@ struct Args {
                *agc_log = nullptr, *i2bit_thr = nullptr, *antenna = nullptr, *cn0 = nullptr, *noise_seed = nullptr, *noise_stream = nullptr,
                *signal_gain = nullptr, *lo_offset = nullptr, *phase_noise = nullptr, *osc_seed = nullptr, *osc_stream = nullptr,
                *scint = nullptr, *scint_seed = nullptr, *scint_site = nullptr, *array = nullptr, *array_log = nullptr, *reflector_prn = nullptr,
-               *reflector_log = nullptr;
+               *reflector_log = nullptr, *spectrum = nullptr, *spectrum_every = nullptr, *spectrum_size = nullptr, *spectrum_window = nullptr;
     std::vector<const char *> prn_power, jam, jam_dir, reflector;
     long agc_window_n = 8;
     double agc_target = 0.0, agc_init_rms = -1.0;  // (0 / < 0: the defaults, known once shift and sigma are)
@@ -464,6 +464,8 @@ const OptRow kOptions[] = {
     {"array-log", ARG, OPT_STRING + 26, false, &Args::array_log}, {"jam-dir", ARG, OPT_JAM_DIR, false, nullptr},
     {"reflector", ARG, OPT_REFLECTOR, true, nullptr}, {"reflector-prn", ARG, OPT_STRING + 27, true, &Args::reflector_prn},
     {"reflector-log", ARG, OPT_STRING + 28, false, &Args::reflector_log},
+    {"spectrum", ARG, OPT_STRING + 29, false, &Args::spectrum}, {"spectrum-every", ARG, OPT_STRING + 30, false, &Args::spectrum_every},
+    {"spectrum-size", ARG, OPT_STRING + 31, false, &Args::spectrum_size}, {"spectrum-window", ARG, OPT_STRING + 32, false, &Args::spectrum_window},
 };
 
 // the command line into Args and the Config's plain fields; every option with to_children also into c->child_args
@@ -899,6 +901,57 @@ void cfg_mix(Args &a, Config &c)
     }
 }
 
+// --spectrum: the sum of win^2, which turns the sums into a power density (header line of the CSV)
+uint64_t spectrum_win2(const gal_iq_psd_t &p)
+{
+    const int32_t *C = gal_tables_psd();
+    const int N = 1 << p.log2_n;
+    uint64_t s = 0;
+    for (int n = 0; n < N; ++n) {
+        const uint64_t w = p.window ? (uint64_t)((((int64_t)1 << 30) - C[n * (4096 / N)]) >> 16) : 32768u;
+        s += w * w;
+    }
+    return s;
+}
+
+// (usage() does not list the four --spectrum options: its text is recorded byte for byte by tests/golden/cli_transcript.json; README.md does)
+void cfg_spectrum(const Args &a, Config &c)
+{
+    long v = 0;
+    if (!a.spectrum) {
+        if (a.spectrum_every || a.spectrum_size || a.spectrum_window) die("ERROR: --spectrum-every, --spectrum-size and --spectrum-window need --spectrum <file>.\n");
+        return;
+    }
+    if (!*a.spectrum || strcmp(a.spectrum, "-") == 0) die("ERROR: --spectrum needs a file name.\n");
+    if (c.iq_format == GAL_IQ_I2BIT) die("ERROR: --spectrum does not read --iq-format i2bit (ishort, ibyte and ibit it does).\n");
+    if (c.array_on()) die("ERROR: --spectrum does not go with --array: the spectrum is of one stream.\n");
+    if (!c.sitesfile.empty()) die("ERROR: --spectrum does not go with --sites: run the site on its own.\n");
+    if (a.spectrum_every) {
+        if (!parse_long(a.spectrum_every, 1, 1000000, &v)) die("ERROR: --spectrum-every '%s' out of range (1..1000000 epochs).\n", a.spectrum_every);
+        c.spectrum_every = (int)v;
+    }
+    if (a.spectrum_size) {
+        if (!parse_long(a.spectrum_size, 8, 4096, &v) || (v & (v - 1))) die("ERROR: --spectrum-size '%s' is not a power of two from 8 to 4096.\n", a.spectrum_size);
+        c.spectrum.log2_n = 0;
+        while ((1L << c.spectrum.log2_n) < v) ++c.spectrum.log2_n;
+    }
+    if (a.spectrum_window) {
+        if (strcmp(a.spectrum_window, "hann") == 0) c.spectrum.window = 1;
+        else if (strcmp(a.spectrum_window, "rect") == 0) c.spectrum.window = 0;
+        else die("ERROR: --spectrum-window '%s' (accepted: hann, rect).\n", a.spectrum_window);
+    }
+    const int N = 1 << c.spectrum.log2_n;
+    c.spectrum.hop = c.spectrum.window ? N / 2 : N;
+    c.spectrum_file = a.spectrum;
+    c.spectrum_fp = fopen(a.spectrum, "w");
+    if (!c.spectrum_fp) die("ERROR: cannot write the spectrum file %s.\n", a.spectrum);
+    fprintf(c.spectrum_fp, "# Welch power spectrum: N=%d hop=%d window=%s format=%s fs_hz=%.0f sum_win2=%llu; lines: time_s,n_seg,p[-N/2],...,p[N/2-1] "
+                           "(frequency order, bin k at k fs / N); last line: total\n",
+            N, c.spectrum.hop, c.spectrum.window ? "hann" : "rect", kIqNames[c.iq_format], kOutRate, (unsigned long long)spectrum_win2(c.spectrum));
+    say(c, "Spectrum: every %d epochs, N = %d, hop %d, %s window -> %s\n", c.spectrum_every, N, c.spectrum.hop, c.spectrum.window ? "Hann" : "rectangular",
+        a.spectrum);
+}
+
 void cfg_monitor(const Args &a, Config &c)
 {
     long v = 0;
@@ -1232,6 +1285,7 @@ void parse_options(int argc, char *argv[], Config *c)
     cfg_signals(a, *c);
     cfg_mix(a, *c);
     cfg_monitor(a, *c);
+    cfg_spectrum(a, *c);
     cfg_filter(a, *c);
     cfg_agc(a, *c);
     cfg_osc(a, *c);

@@ -83,6 +83,10 @@ struct Config {
     const char *monitor_file = nullptr;
     int monitor_every = 10;
     FILE *monitor_fp = nullptr;
+    const char *spectrum_file = nullptr;  // --spectrum: the Welch power spectrum of every spectrum_every'th epoch (gal_synth_iq_psd)
+    int spectrum_every = 10;
+    gal_iq_psd_t spectrum = {10, 512, 1, 0};  // --spectrum-size 1024, --spectrum-window hann: hop N / 2 (rect: N)
+    FILE *spectrum_fp = nullptr;
 
     double sample_rate() const { return (double)osr * kOutRate; }
     bool dec_on() const { return osr > 1; }

@@ -1,5 +1,5 @@
 // iq_api.cpp -- the output chain's half of the C ABI (include/galsynth.h): every pass over the finished int16 stream -- formats, noise
-// floor, interference, per-satellite gains, multipath, scintillation, the antenna array, FIR, decimating FIR, AGC, oscillator -- and the correlator bank, over the kernels of
+// floor, interference, per-satellite gains, multipath, scintillation, the antenna array, FIR, decimating FIR, AGC, oscillator -- the correlator bank and the power spectrum, over the kernels of
 // csrc/iq_*.hip.  Host-side plumbing only: validation, the stages' device state, kernel sequencing.  The handle itself, plan, execute
 // and finish are synth_api.cpp's; synth_handle.h is what the two share.  Nothing here depends on GAL_TEST_HOOKS: one object serves
 // libgalsynth.so and libgalsynth_hooks.so.
@@ -46,6 +46,7 @@ void galk_array_pack(int w_re, int w_im, uint32_t *two);
 hipError_t galk_launch_corr(int format, const void *buf, uint64_t n_eff, uint64_t code_ph0, uint64_t code_dph, uint32_t carr_ph0,
                             uint32_t carr_step0, uint32_t dopp_step, int delay0, int delay_step, int n_delay, int n_dopp, int max_periods,
                             const uint32_t *lut_dev, const uint32_t *code_dev, long long *out, hipStream_t st);
+hipError_t galk_launch_psd(int format, const void *buf, uint64_t n_seg, int log2_n, int hop, int window, unsigned long long *out, hipStream_t st);
 }
 
 // ---- what every stage's entry points repeat, once ----------------------------------------------------------------------------------
@@ -1733,6 +1734,55 @@ int gal_corr_cn0(const int64_t *out_host, const gal_corr_req_t *req, int32_t k_p
     if (!(pp > pn) || !(pn > 0.0)) return fail(GAL_E_INVAL, "gal_corr_cn0: no peak (Pp %g <= Pn %g)", pp, pn);
     const double T = (double)kCorrL / (double)req->code_dph / sample_rate;
     *cn0_dbhz = 10.0 * log10((pp - pn) / (pn * T / 2.0));
+    return GAL_OK;
+}
+
+// ---- Welch power spectrum (iq_psd.hip) -----------------------------------------------------------------------------------------
+// nullptr: the configuration is fine; otherwise what is wrong with it
+static const char *psd_cfg_fault(const gal_iq_psd_t *c)
+{
+    if (c->log2_n < 3 || c->log2_n > 12) return "log2_n outside 3..12";
+    if (c->hop < 1 || c->hop > (1 << c->log2_n)) return "hop outside 1..N";
+    if (c->window != 0 && c->window != 1) return "window is neither 0 (rectangular) nor 1 (Hann)";
+    if (c->reserved != 0) return "reserved is not 0";
+    return nullptr;
+}
+
+int64_t gal_synth_psd_segments(const gal_iq_psd_t *cfg, size_t n_samples)
+{
+    if (!cfg || psd_cfg_fault(cfg)) return 0;
+    const uint64_t N = (uint64_t)1 << cfg->log2_n;
+    if (n_samples < N) return 0;
+    const uint64_t n_seg = ((uint64_t)n_samples - N) / (uint64_t)cfg->hop + 1;
+    if (n_seg > (((uint64_t)1 << 32) >> (2 * cfg->log2_n))) return 0;  // n_seg N^2 <= 2^32: no bin's sum passes 2^63
+    return (int64_t)n_seg;
+}
+
+int gal_synth_iq_psd(gal_synth_t *h, const void *buf_dev, int32_t format, size_t n_samples, const gal_iq_psd_t *cfg, uint64_t *out_dev,
+                     int32_t *n_seg)
+{
+    static const char *const who = "gal_synth_iq_psd";
+    if (!h) return fail(GAL_E_INVAL, "null handle");
+    if (format != GAL_IQ_ISHORT && format != GAL_IQ_IBYTE && format != GAL_IQ_IBIT)
+        return fail(GAL_E_INVAL, "%s: format %d (GAL_IQ_ISHORT 0, GAL_IQ_IBYTE 1, GAL_IQ_IBIT 2; GAL_IQ_I2BIT is the AGC's alone)", who, format);
+    if (!cfg || !n_seg) return fail(GAL_E_INVAL, "%s: null cfg or n_seg", who);
+    GAL_TRY(check_aligned(who, buf_dev));
+    GAL_TRY(check_aligned(who, out_dev));
+    const char *what = psd_cfg_fault(cfg);
+    if (what) return fail(GAL_E_INVAL, "%s: %s", who, what);
+    const int64_t segs = gal_synth_psd_segments(cfg, n_samples);
+    if (segs <= 0)
+        return fail(GAL_E_INVAL, "%s: %zu samples hold no segment of %d, or more than 2^32 / N^2 = %llu of them", who, n_samples, 1 << cfg->log2_n,
+                    (unsigned long long)(((uint64_t)1 << 32) >> (2 * cfg->log2_n)));
+    const size_t buf_bytes = gal_synth_iq_bytes(format, n_samples), out_bytes = sizeof(uint64_t) << cfg->log2_n;
+    GAL_TRY(check_overlap(who, buf_dev, buf_bytes, out_dev, out_bytes, false, ""));
+    GAL_TRY(check_in_flight(who, h, buf_dev, buf_bytes, "buffer of"));
+    GAL_TRY(check_in_flight(who, h, out_dev, out_bytes, "buffer of"));
+    hipStream_t st;
+    GAL_TRY(enter(h, &st, false));
+    HIP_TRY(hipMemsetAsync(out_dev, 0, out_bytes, st));
+    HIP_TRY(galk_launch_psd(format, buf_dev, (uint64_t)segs, cfg->log2_n, cfg->hop, cfg->window, (unsigned long long *)out_dev, st));
+    *n_seg = (int32_t)segs;
     return GAL_OK;
 }
 

@@ -38,26 +38,6 @@ struct CorrArgs {
     int kd;               // lanes per segment: min(256, power of two >= n_delay)
 };
 
-// sample n of the buffer as (I, Q)
-template <int FMT>
-__device__ __forceinline__ void load_iq(const void *buf, uint64_t n, int &I, int &Q)
-{
-    if (FMT == 0) {
-        const int v = ((const int *)buf)[n];
-        I = (v << 16) >> 16;
-        Q = v >> 16;
-    } else if (FMT == 1) {
-        const int v = ((const unsigned short *)buf)[n];
-        I = (v << 24) >> 24;
-        Q = (v << 16) >> 24;
-    } else {  // value 2n is bit 7 - (2n & 7) of byte n >> 2
-        const int v = ((const unsigned char *)buf)[n >> 2];
-        const int sh = 6 - 2 * (int)(n & 3);
-        I = ((v >> (sh + 1)) & 1) * 2 - 1;
-        Q = ((v >> sh) & 1) * 2 - 1;
-    }
-}
-
 // the samples [s, e) of the tile against the replica delayed by dk (0 .. 8183), added into acc
 __device__ __forceinline__ void walk(const int4 *tile, const uint32_t *code, int s, int e, int dk, long long (&acc)[4])
 {

@@ -1,5 +1,5 @@
 // iq_dev.h -- the device helpers the passes over the output stream share (iq_pass, iq_gain, iq_echo, iq_fir, iq_firdec, iq_agc, iq_osc,
-// iq_corr .hip): ONE definition of each, force-inlined into the kernels of the file that includes it.  Everything is integer arithmetic.
+// iq_corr, iq_psd .hip): ONE definition of each, force-inlined into the kernels of the file that includes it.  Everything is integer arithmetic.
 //
 // The two device tables reach only the files that ask for them: a file that needs the Gauss table defines GAL_GAUSS_DEVICE_TABLE before
 // it includes this header, one that needs the cosine table GAL_INTERF_DEVICE_TABLE; only then are csrc/gauss_table.inc /
@@ -131,6 +131,26 @@ __device__ __forceinline__ uint32_t f8(int v, int s, int r, uint32_t &sat)
     const int y = clamp16(v), q = (y + r) >> s;
     sat += (uint32_t)((y != v) | (q < -127) | (q > 127));
     return (uint32_t)(min(max(q, -127), 127)) & 0xffu;
+}
+
+// the readers of a finished buffer (iq_corr.hip, iq_psd.hip): sample n of `buf` in format FMT (GAL_IQ_ISHORT, _IBYTE, _IBIT) as (I, Q)
+template <int FMT>
+__device__ __forceinline__ void load_iq(const void *buf, uint64_t n, int &I, int &Q)
+{
+    if (FMT == 0) {
+        const int v = ((const int *)buf)[n];
+        I = (v << 16) >> 16;
+        Q = v >> 16;
+    } else if (FMT == 1) {
+        const int v = ((const unsigned short *)buf)[n];
+        I = (v << 24) >> 24;
+        Q = (v << 16) >> 24;
+    } else {  // value 2n is bit 7 - (2n & 7) of byte n >> 2
+        const int v = ((const unsigned char *)buf)[n >> 2];
+        const int sh = 6 - 2 * (int)(n & 3);
+        I = ((v >> (sh + 1)) & 1) * 2 - 1;
+        Q = ((v >> sh) & 1) * 2 - 1;
+    }
 }
 
 // ---- weighted sums of parts (iq_gain.hip, iq_echo.hip) ---------------------------------------------------------------------------

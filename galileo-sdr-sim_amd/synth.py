@@ -275,6 +275,19 @@ CORR_REQ_FIELDS = tuple(name for name, _ in _CorrReq._fields_)
 GAL_CORR_MAX_REQ = 64
 
 
+class _Psd(ctypes.Structure):  # gal_iq_psd_t (16 bytes)
+    _fields_ = [
+        ("log2_n", ctypes.c_int32),
+        ("hop", ctypes.c_int32),
+        ("window", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+assert ctypes.sizeof(_Psd) == 16
+PSD_WINDOWS = {"rect": 0, "hann": 1}
+
+
 class GalSynthError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("galsynth error %d: %s" % (code, msg))
@@ -353,6 +366,8 @@ EXPORTED_SYMBOLS = (
     "gal_synth_run_array",
     "gal_synth_corr_out_bytes",
     "gal_synth_correlate",
+    "gal_synth_psd_segments",
+    "gal_synth_iq_psd",
     "gal_tables_e1b",
     "gal_tables_e1c",
     "gal_tables_cos512",
@@ -361,6 +376,7 @@ EXPORTED_SYMBOLS = (
     "gal_tables_gauss",
     "gal_tables_cos1024",
     "gal_tables_scint",
+    "gal_tables_psd",
 )
 
 _libs = {}
@@ -517,8 +533,12 @@ def load_library(hooks=False):
     lib.gal_corr_cn0.argtypes = [vp, ctypes.POINTER(_CorrReq), i32, i32, i32, ctypes.c_double, ctypes.POINTER(ctypes.c_double),
                                  ctypes.POINTER(ctypes.c_double)]
     lib.gal_corr_cn0.restype = ctypes.c_int
+    lib.gal_synth_psd_segments.argtypes = [ctypes.POINTER(_Psd), ctypes.c_size_t]
+    lib.gal_synth_psd_segments.restype = ctypes.c_int64
+    lib.gal_synth_iq_psd.argtypes = [vp, vp, i32, ctypes.c_size_t, ctypes.POINTER(_Psd), vp, ctypes.POINTER(i32)]
+    lib.gal_synth_iq_psd.restype = ctypes.c_int
     for name in ("gal_tables_e1b", "gal_tables_e1c", "gal_tables_cos512", "gal_tables_sin512", "gal_tables_gauss", "gal_tables_cos1024",
-                 "gal_tables_scint"):
+                 "gal_tables_scint", "gal_tables_psd"):
         getattr(lib, name).restype = vp
     lib.gal_tables_cs25.restype = ctypes.c_uint32
     _libs[hooks] = lib
@@ -989,6 +1009,17 @@ def corr_out_bytes(req):
     return int(load_library().gal_synth_corr_out_bytes(ctypes.byref(_corr_struct(req))))
 
 
+def _psd_struct(log2_n, hop, window, reserved=0):
+    w = PSD_WINDOWS[window] if isinstance(window, str) else int(window)
+    return _Psd(int(log2_n), int(hop), w, int(reserved))
+
+
+def psd_segments(log2_n, hop, window, n_samples, reserved=0):
+    """gal_synth_psd_segments (no GPU needed): the segments SynthEngine.iq_psd would sum over n_samples samples; 0 where it would refuse
+    (a field out of range, fewer than N = 2^log2_n samples, n_seg N^2 > 2^32).  window: "rect" | "hann" or 0 | 1."""
+    return int(load_library().gal_synth_psd_segments(ctypes.byref(_psd_struct(log2_n, hop, window, reserved)), int(n_samples)))
+
+
 def corr_from_epoch(rec, sample_rate, sample_offset=0, **grid):
     """gal_corr_from_epoch (no GPU needed): the replica of one planned record (a CHAN_EPOCH_DTYPE element) as a request dict --
     prn, code_ph0, code_dph, carr_ph0, carr_dph -- with `grid` (delay0, n_delay, dopp_step, max_periods, ...) merged in."""
@@ -1036,6 +1067,7 @@ def tables():
         "gauss": arr(lib.gal_tables_gauss(), ctypes.c_int32, 32 * 32 * 2, (32, 32, 2)),
         "cos1024": arr(lib.gal_tables_cos1024(), ctypes.c_int16, 1024, (1024,)),
         "scint": arr(lib.gal_tables_scint(), ctypes.c_int32, 32, (32,)),
+        "psd": arr(lib.gal_tables_psd(), ctypes.c_int32, 2 * 4096, (2, 4096)),
     }
 
 
@@ -1462,3 +1494,23 @@ class SynthEngine:
             res.append(host[off:off + nb // 8].reshape(q.max_periods, q.n_dopp, q.n_delay, 4).copy())
             off += nb // 8
         return res[0] if single else res
+
+    def iq_psd(self, buf_ptr, fmt, n_samples, log2_n, hop, window, out_ptr=None, reserved=0):
+        """gal_synth_iq_psd: the Welch power spectrum of the n_samples complex samples in format `fmt` at device address buf_ptr (16-byte
+        aligned, final output): N = 2^log2_n, segments `hop` samples apart, window "rect" | "hann" (0 | 1).  Returns (the uint64 sums
+        of |X[k]|^2 over the segments, k < N in natural order, n_seg); waits for them.  out_ptr: a device address for the sums (16-byte
+        aligned, N uint64) -- then nothing is copied or waited for and (None, n_seg) is returned; iq_saturated() is the fence."""
+        cfg = _psd_struct(log2_n, hop, window, reserved)
+        n_seg = ctypes.c_int32(0)
+        if out_ptr is not None:
+            self._check(self._lib.gal_synth_iq_psd(self._h, ctypes.c_void_p(int(buf_ptr)), iq_format_code(fmt), int(n_samples), ctypes.byref(cfg),
+                                                   ctypes.c_void_p(int(out_ptr)), ctypes.byref(n_seg)))
+            return None, int(n_seg.value)
+        import torch
+
+        out = torch.empty(max(2, 1 << max(0, min(int(log2_n), 12))), dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()  # (the block may come from torch's cache with work of torch's stream still behind it)
+        self._check(self._lib.gal_synth_iq_psd(self._h, ctypes.c_void_p(int(buf_ptr)), iq_format_code(fmt), int(n_samples), ctypes.byref(cfg),
+                                               ctypes.c_void_p(out.data_ptr()), ctypes.byref(n_seg)))
+        self.iq_saturated()
+        return out.cpu().numpy().view(np.uint64)[:1 << int(log2_n)].copy(), int(n_seg.value)
